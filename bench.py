@@ -8,8 +8,15 @@ build (tfidf_commit: tokenise + per-doc TF rows + DF + inverted postings) of
 the HBM-resident corpus on every rank; with N > 1 GPUs each rank owns its own
 1M-doc shard (weak scaling, BASELINE cfg 3 layout) and a step also runs the
 GLOBAL-statistics exchange (vocabulary all-gather + DF all-reduce over RCCL).
-Query throughput is measured after the timed region: cfg-2 single 3-term
-queries (top-10 and all-hits) and cfg-4 batched 10k queries (top-10).
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds everything else, after the timed region: query throughput (cfg-2
+single 3-term queries, top-10 and all-hits, and cfg-4 batched 10k queries,
+top-10), the PCIe-inclusive end-to-end build, the CPU baseline and the
+device-copy bandwidth the roofline is also quoted against.  --dump-outputs DIR
+writes the index the last timed step built, as its caller sees it, to
+DIR/<name>.npy (dump_outputs below); the corpus is seeded, so two builds of
+the library run with the same arguments can be compared array for array.
 
 Launch: python bench.py [--gpus N --steps K --warmup W].  N > 1 runs one
 process per GPU (RCCL): under torch.distributed.run (WORLD_SIZE must equal N),
@@ -32,7 +39,8 @@ sys.path.insert(0, REPO)
 import numpy as np  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8.0 TB/s spec
-
+DUMP_SEED = 20251019       # --dump-outputs: the sampled documents
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all arrays together
 
 
 def default_cap(vocab):
@@ -77,7 +85,18 @@ def parse():
                     help="skip the PCIe-inclusive (host corpus -> HBM -> index) measurement")
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "r06", "traffic.json"),
                     help="per-kernel HBM bytes from tools/prof_round.sh (rocprofv3 PMC passes of this workload)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure queries, the end-to-end build, the CPU baseline and "
+                         "the device-copy bandwidth (each still subject to its own --no-* / --cpu-sample switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run does only what `value` needs
+        args.no_queries, args.e2e, args.cpu_sample = True, False, 0
+    return args
 
 
 def launcher_cmd(n_gpus, argv, port=None):
@@ -222,6 +241,63 @@ def measured_copy_GBs(dev, nbytes=1 << 30, reps=5):
     return 2 * nbytes / (ms * 1e-3) / 1e9
 
 
+def write_dump(dirname, arrays, prefix=""):
+    """--dump-outputs: arrays (name -> float32 / float64 ndarray) as DIR/<prefix><name>.npy."""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "dump of %d bytes" % total
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, prefix + name + ".npy"), a)
+
+
+def dump_outputs(dirname, idx, args, prefix=""):
+    """What the timed path (tfidf_commit) leaves its caller: the committed
+    index, read back through the calls a caller has.  Everything is fixed by
+    the arguments (seeded samples), and nothing depends on how the library
+    lays the index out:
+      stats         f64 [7]      num_docs, doc_count, sum_ttf, num_terms, nnz, text_bytes, long_docs
+      df            f64 [R, 3]   synthetic word rank, its local df, the df in force (every rank up
+                                 to 2^17 words, a seeded sample of a larger vocabulary)
+      doc_len       f64 [D, 3]   doc, length in tokens, norm byte (D = 4096 seeded documents)
+      doc_terms     f64 [T, 3]   doc, CRC-32 of the term, tf: the TF rows of the first 64 of those
+                                 documents, terms in byte order
+      top10_docs    f64 [Q, 10]  1024 seeded 3-term queries, top 10 (score desc, doc asc),
+      top10_scores  f32 [Q, 10]  unused places 0
+      top10_counts  f64 [Q]
+      hits<i>_docs, hits<i>_scores   every hit of query i < 4 in rank order (the first 500 000)
+    """
+    import zlib
+    from tfidf_amd import synth
+    st = idx.stats()
+    N = st["num_docs"]
+    out = {"stats": np.array([st[k] for k in ("num_docs", "doc_count", "sum_ttf", "num_terms", "nnz", "text_bytes",
+                                              "long_docs")], np.float64)}
+    rng = np.random.default_rng(DUMP_SEED)
+    if args.vocab <= 1 << 17:
+        ranks = np.arange(1, args.vocab + 1)
+    else:
+        ranks = np.sort(rng.choice(args.vocab, 1 << 17, replace=False)) + 1
+    out["df"] = np.array([(r,) + idx.df(synth.word(r)) for r in ranks.tolist()], np.float64).reshape(-1, 3)
+    docs = np.sort(rng.choice(N, min(N, 4096), replace=False)).tolist()
+    out["doc_len"] = np.array([(d,) + idx.doc_len(d) for d in docs], np.float64).reshape(-1, 3)
+    rows = []
+    for d in docs[:64]:
+        rows += [(d, zlib.crc32(t), tf) for t, tf in sorted(idx.doc_terms(d).items())]
+    out["doc_terms"] = np.array(rows, np.float64).reshape(-1, 3)
+    qs = synth.queries(1024)
+    d10, s10, c10 = idx.search_batch(qs, 10)
+    out["top10_docs"] = d10.astype(np.float64)
+    out["top10_scores"] = s10.astype(np.float32)
+    out["top10_counts"] = c10.astype(np.float64)
+    for i, q in enumerate(qs[:4]):
+        d, s = idx.search_all_arrays(q)
+        out["hits%d_docs" % i] = d[:500_000].astype(np.float64)
+        out["hits%d_scores" % i] = s[:500_000].astype(np.float32)
+    write_dump(dirname, out, prefix)
+
+
 def bench_node(args):
     """TFIDF_BENCH_NODE=1: process model (1) of include/tfidf.h — ONE process
     owns --gpus N devices through tfidf_node (device mask (1 << N) - 1, RCCL
@@ -259,6 +335,14 @@ def bench_node(args):
         t = L.CommitTiming()
         L.check(lib.tfidf_get_commit_timing(node.shard(g), C.byref(t)))
         per_shard.append(t.ms_total)
+    if args.dump_outputs:
+        # the node's committed index through the node-level calls: statistics and top-10 merges
+        d10, s10, c10 = node.search_batch(synth.queries(1024), 10)
+        write_dump(args.dump_outputs, {
+            "stats": np.array([st[k] for k in ("n_shards", "num_docs", "doc_count", "sum_ttf", "num_terms")],
+                              np.float64),
+            "top10_docs": d10.astype(np.float64), "top10_scores": s10.astype(np.float32),
+            "top10_counts": c10.astype(np.float64)})
     out = {
         "metric": "docs indexed/sec + queries scored/sec (node) at 1/2/4/8 GPUs; % HBM roofline",
         "value": st["num_docs"] * args.steps / elapsed, "unit": "docs/s", "n_gpus": G, "steps": args.steps,
@@ -387,9 +471,12 @@ def main():
     st = idx.stats()
     timing = idx.commit_timing()
     text_bytes, nnz, N = st["text_bytes"], st["nnz"], st["num_docs"]
+    if args.dump_outputs:
+        # before --full's legs, which rebuild the index (end_to_end); each rank dumps its own shard
+        dump_outputs(args.dump_outputs, idx, args, prefix="rank%d_" % rank if world > 1 else "")
 
     # ---- roofline of the dominant kernel (algorithmic bytes) ----
-    copy_gbs = measured_copy_GBs(dev)
+    copy_gbs = measured_copy_GBs(dev) if args.full else None     # a run of its own
     C_slots = 1 << cap
     n_blocks = (N + 8191) // 8192
     if st["term_major"]:
@@ -451,7 +538,8 @@ def main():
             "parallelism": "dp%d (document shards)" % world},
         "roofline": {"bound": "hbm", "kernel": dom.replace("ms_", ""), "achieved": achieved, "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "measured_copy_GBs": copy_gbs, "frac_of_measured_copy": achieved / copy_gbs,
+                     "measured_copy_GBs": copy_gbs,
+                     "frac_of_measured_copy": achieved / copy_gbs if copy_gbs else None,
                      "traffic_source": traffic_src, "alg_bytes_per_launch": alg[dom], "avg_launch_ms": dom_ms},
         "phases_ms": phases,
         "phases_alg_GBs": phase_gbs,

@@ -20,7 +20,7 @@ run() {   # name, timeout, args...
   tail -1 $O/$n.log > $O/$n.json
   python3 -c "import json; r=json.load(open('$O/$n.json')); print('$n', round(r['value']/1e6, 2), 'M docs/s', round(r['ms_per_step'], 3), 'ms', {k: round(v, 3) for k, v in r['phases_ms'].items() if v > 0.01})"
 }
-run bench_line 400 --traffic-json $TJ
+run bench_line 400 --full --traffic-json $TJ
 run bench_line_cfg5_shape 300 --steps 5 --warmup 2 --docs 6250000 --len-min 48 --len-max 80 --vocab 5000000 --no-queries --no-e2e --cpu-sample 0
 run bench_line_book_shape 200 --steps 10 --warmup 2 --docs 300 --len-min 80000 --len-max 120000 --no-queries --no-e2e --cpu-sample 0
 run bench_line_book_unicode 200 --steps 10 --warmup 2 --docs 300 --len-min 80000 --len-max 120000 --unicode-every 2048 --no-queries --no-e2e --cpu-sample 0
@@ -30,7 +30,7 @@ run bench_line_cfg2_unicode100 300 --steps 3 --warmup 1 --unicode-frac 1.0 --no-
 run bench_line_cfg2_prose 300 --steps 10 --warmup 2 --prose 1 --no-queries --no-e2e --cpu-sample 0
 TFIDF_NO_UNIFIRST=1 run bench_line_cfg2_prose_ascii_first 300 --steps 10 --warmup 2 --prose 1 --no-queries --no-e2e --cpu-sample 0
 TFIDF_NO_UNIWAVE=1 run bench_line_cfg2_prose_uwave_only 300 --steps 5 --warmup 1 --prose 1 --no-queries --no-e2e --cpu-sample 0
-TFIDF_BENCH_NODE=1 run bench_line_node1 300 --steps 5 --warmup 2 --cpu-sample 0 --no-e2e
+TFIDF_BENCH_NODE=1 run bench_line_node1 300 --full --steps 5 --warmup 2 --cpu-sample 0 --no-e2e
 run bench_line_books_prose 200 --steps 10 --warmup 2 --docs 300 --len-min 80000 --len-max 120000 --prose 1 --no-queries --no-e2e --cpu-sample 0
 # cfg-5 PMC: one build, FETCH / WRITE passes, kernel summary
 P=$R/gpurun_out/prof_cfg5_$TAG; mkdir -p $P
@@ -42,6 +42,6 @@ timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --kernel-include-regex "k_" -d $P
 python3 $R/tools/summarize_prof.py $P --json $P/traffic.json > $P/summary.txt 2>&1 || true
 head -12 $P/summary.txt
 cd $R
-TFIDF_BENCH_DIST=1 timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --steps 5 --warmup 2 --cpu-sample 0 --no-e2e --batch-queries 2000 > $O/bench_dist1.log 2> $O/bench_dist1.err || { echo "dist failed"; tail -5 $O/bench_dist1.err; exit 1; }
+TFIDF_BENCH_DIST=1 timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --steps 5 --warmup 2 --cpu-sample 0 --no-e2e --batch-queries 2000 > $O/bench_dist1.log 2> $O/bench_dist1.err || { echo "dist failed"; tail -5 $O/bench_dist1.err; exit 1; }
 tail -1 $O/bench_dist1.log > $O/bench_line_dist1_rccl.json
 echo "evidence ok"

@@ -1,14 +1,15 @@
 #!/bin/bash
-# Kernel trace of the cfg-2 batch (bench with queries) under query-path knobs:
+# Kernel trace of the cfg-2 batch (bench --full: with queries) under query-path knobs:
 # SETS="name:VAR=val ..." (name only = defaults); prints each batch chunk's kernels.
+# Output: $OUT_DIR (default bench_out/).
 set -o pipefail
 export TFIDF_DEBUG=1
-R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; mkdir -p gpurun_out; export TMPDIR=/tmp
+R=$(cd "$(dirname "$0")/.." && pwd); cd $R; O=${OUT_DIR:-bench_out}; mkdir -p $O; export TMPDIR=/tmp
 for spec in ${SETS:-base}; do
   n=${spec%%:*}; e=""; [ "$n" != "$spec" ] && e=${spec#*:}
   env_args=${e//,/ }
-  ( [ -n "$env_args" ] && export $env_args; timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/ktb_$n -o kt -- python -u bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-e2e > gpurun_out/ktb_$n.log 2>&1 ) || { echo "$n failed"; tail -3 gpurun_out/ktb_$n.log; exit 1; }
-  f=$(find gpurun_out/ktb_$n -name '*kernel_trace.csv' | head -1)
+  ( [ -n "$env_args" ] && export $env_args; timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/ktb_$n -o kt -- python -u bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-e2e > $O/ktb_$n.log 2>&1 ) || { echo "$n failed"; tail -3 $O/ktb_$n.log; exit 1; }
+  f=$(find $O/ktb_$n -name '*kernel_trace.csv' | head -1)
   python3 - "$f" "$n" <<'PY'
 import csv, sys
 r = list(csv.DictReader(open(sys.argv[1])))

@@ -10,7 +10,7 @@ TAG=${TAG:-r01}
 O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py ${BENCH_ARGS:-}"
+BENCH="python3 $R/bench.py --full ${BENCH_ARGS:-}"
 if [ -z "${NO_KT:-}" ]; then
   timeout -s KILL 300 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- $BENCH > $O/kt_bench.log 2>&1 || { echo "kt failed"; tail -5 $O/kt_bench.log; exit 1; }
   echo "kt ok"
