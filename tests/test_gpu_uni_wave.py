@@ -262,6 +262,57 @@ def test_uni_first_recommit_equals_oracle(monkeypatch, unifirst):
     o.close()
 
 
+def ascii_doc_of(rng, n_bytes):
+    """A pure-ASCII document of exactly n_bytes bytes (synth words, spaces)."""
+    buf = bytearray()
+    while len(buf) < n_bytes:
+        buf += synth.word(rng.randint(1, 3000)) + b" "
+    return bytes(buf[:n_bytes - 1]) + b"x"
+
+
+@pytest.mark.parametrize("unifirst", [True, False])
+def test_uni_first_counts_ascii_near_window(monkeypatch, unifirst):
+    """ASCII documents of 4081 to 4096 bytes under a UNI-first re-commit.  The
+    wave window stages a document from the 16-byte line its text starts in, so
+    one that starts `shift` bytes into the line fits only while shift + L <=
+    4096: the UNI wave pass leaves the others flagged and k_tokenize_uwave
+    meets an ASCII document.  It must do with it what the ASCII pass does (the
+    long path, not counted as non-ASCII), or `unicode_docs` — which decides
+    the next commit's mode — and `long_docs` depend on which pass ran first.
+    Sixteen consecutive lengths: whatever the alignment of the first, several
+    of them overflow the window; two more follow an odd-length document."""
+    if not unifirst:
+        monkeypatch.setenv("TFIDF_NO_UNIFIRST", "1")
+    rng = random.Random(113)
+    texts = [doc(rng, rng.randint(20, 500), rng.randint(1, 12), PROSE + WORDS + JOIN) for _ in range(700)]
+    texts += [doc(rng, rng.randint(20, 300), 2, PROSE) + " 中文".encode() for _ in range(60)]
+    texts += synth.corpus(300, V=3000, len_min=50, len_max=400)                       # ASCII
+    texts += [(" ".join(synth.word(rng.randint(1, 3000)).decode() for _ in range(2500))).encode()]   # > 4 KB
+    texts += [b"bad \xff byte", ("word " * 820).encode(), prose_edge_docs()[7]]
+    rng.shuffle(texts)
+    texts += [ascii_doc_of(rng, n) for n in range(4081, 4097)]
+    texts += [b"odd", ascii_doc_of(rng, 4090), b"seven b", ascii_doc_of(rng, 4096)]
+    want_uni = sum(1 for t in texts if len(t) <= 4096 and any(b >= 0x80 for b in t))
+    g, o = build_pair(texts)
+    st1 = g.stats()
+    # both conditions of a UNI-first re-commit (tfidf_capi.hip: one document
+    # per window, most documents non-ASCII)
+    assert st1["pack_docs"] == 1 and st1["unicode_docs"] * 2 > st1["num_docs"] == len(texts)
+    check(g, o, texts)
+    g.commit()                                        # the same documents again: UNI-first unless disabled
+    st2 = g.stats()
+    check(g, o, texts)
+    for k in ("unicode_docs", "unicode_wave_docs", "long_docs", "nnz", "num_terms"):
+        assert st1[k] == st2[k], (k, st1[k], st2[k])
+    assert st1["unicode_docs"] == st2["unicode_docs"] == want_uni
+    for q in ["don’t", "québec", "中文", synth.word(11).decode(), "word", "x"]:
+        qb = q.encode()
+        for kk in (0, 10):
+            assert_hits_equal(g.search(qb, kk), o.search(qb, kk))
+    g.close()
+    o.close()
+
+
 def test_prose_chars_cut_by_chunk_windows_equal_oracle():
     """Round 6: a book unit's window (64 B before its 2 KB core, 320 B after)
     that cuts a multi-byte character in its margin blanks the cut bytes

@@ -3011,11 +3011,21 @@ hipError_t launch_verify_deferred(const BuildParams &p, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_tokenize_wave(const BuildParams &p, int grid, hipStream_t s) {
 #ifndef TFIDF_G4_BITS
 #define TFIDF_G4_BITS 21
 #endif
-  const bool g4 = (uint64_t)p.cap_mask + 1 >= (1ull << TFIDF_G4_BITS);   // dictionary beyond L2: 4-slot probe groups
+// Dictionary beyond L2 (>= 2^TFIDF_G4_BITS slots): 4-slot probe groups.
+// TFIDF_TEST_G4_BITS (tests; read at every launch): another threshold, so the
+// G4 kernels run on a small dictionary at high load (never below 2^4 slots:
+// their retry queue probes aligned 16-slot windows).
+static bool use_g4(const BuildParams &p) {
+  uint32_t bits = TFIDF_G4_BITS;
+  if (const char *e = knob("TFIDF_TEST_G4_BITS")) bits = (uint32_t)std::max(4, std::min(atoi(e), 32));
+  return (uint64_t)p.cap_mask + 1 >= (1ull << bits);
+}
+
+hipError_t launch_tokenize_wave(const BuildParams &p, int grid, hipStream_t s) {
+  const bool g4 = use_g4(p);
   if (p.pack > 1) {
     if (g4) hipLaunchKernelGGL((k_tokenize_wave<true, true>), dim3(grid), dim3(64), 0, s, p);
     else hipLaunchKernelGGL((k_tokenize_wave<true, false>), dim3(grid), dim3(64), 0, s, p);
@@ -3028,7 +3038,7 @@ hipError_t launch_tokenize_wave(const BuildParams &p, int grid, hipStream_t s) {
 // The flagged (non-ASCII) documents by the wave rules where they allow
 // (k_tokenize_wave<UNI>); before k_tokenize_uwave, which takes the rest.
 hipError_t launch_tokenize_wave_uni(const BuildParams &p, int grid, hipStream_t s) {
-  const bool g4 = (uint64_t)p.cap_mask + 1 >= (1ull << TFIDF_G4_BITS);
+  const bool g4 = use_g4(p);
   if (g4) hipLaunchKernelGGL((k_tokenize_wave<false, true, true>), dim3(grid), dim3(64), 0, s, p);
   else hipLaunchKernelGGL((k_tokenize_wave<false, false, true>), dim3(grid), dim3(64), 0, s, p);
   return hipGetLastError();

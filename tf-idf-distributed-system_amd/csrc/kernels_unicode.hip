@@ -447,21 +447,52 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) k_
     const uint64_t src = p.live_map ? p.live_map[d] : d;
     const uint64_t s0 = p.offsets[src];
     const uint64_t L = p.offsets[src + 1] - s0;
-    if (L > kUwWindow || R > kUwMaxRanges) {                // wave-uniform
+    if (L > kUwWindow) {                                    // wave-uniform
       if (lane == 0) p.long_list[atomicAdd(p.long_count, 1u)] = d;
-      if (L > kUwWindow) my_uni--;                          // (UNI-first builds flag long documents too: a long
+      my_uni--;                                             // (UNI-first builds flag long documents too: a long
                                                             // document is not counted as non-ASCII, as the ASCII pass has it)
       continue;
     }
-    // ---- stage (aligned 16 B loads); the table is empty here
+    // ---- stage (aligned 16 B loads); the table is empty here.  A layout of
+    // more ranges than this kernel takes (every document to the long path) is
+    // read for the non-ASCII count only: nothing is staged
+    const bool stage = R <= kUwMaxRanges;                   // wave-uniform
     const uintptr_t a = reinterpret_cast<uintptr_t>(p.text + s0);
     const uint32_t shift = (uint32_t)(a & 15);
     const uint32_t nchunks = (uint32_t)((shift + L + 15) >> 4);
     const uint4 *gsrc = reinterpret_cast<const uint4 *>(a - shift);
     uint4 *dst = reinterpret_cast<uint4 *>(sm.text);
-    for (uint32_t c = lane; c < nchunks; c += 64) dst[c] = gsrc[c];
+    uint32_t hx = 0;                                        // a byte >= 0x80 inside the document
+    for (uint32_t c = lane; c < nchunks; c += 64) {
+      const uint4 val = gsrc[c];
+      if (stage) dst[c] = val;
+      const uint32_t w4[4] = {val.x, val.y, val.z, val.w};
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        uint32_t m = 0x80808080u;
+        if (c == 0 || c == nchunks - 1) {                   // the edge chunks hold the neighbours' bytes too
+          const uint32_t o = 16 * c + 4 * (uint32_t)j;      // window offset of the word's first byte
+          m = 0;
+#pragma unroll
+          for (int b = 0; b < 4; b++)
+            if (o + b >= shift && o + b < shift + (uint32_t)L) m |= 0x80u << (8 * b);
+        }
+        hx |= w4[j] & m;
+      }
+    }
     sm.rcnt[lane] = 0;
     __syncthreads();
+    // A flagged document with no byte >= 0x80: only a UNI-first build has one
+    // (every document starts flagged there), and k_tokenize_wave<UNI> left it
+    // because its window or its tables cannot take it.  The ASCII pass sends
+    // such a document to the long path and does not count it as non-ASCII;
+    // the same here, so the counts do not depend on which pass ran first.
+    const bool ascii = !__any(hx != 0);                     // wave-uniform
+    if (ascii) my_uni--;
+    if (ascii || !stage) {                                  // wave-uniform
+      if (lane == 0) p.long_list[atomicAdd(p.long_count, 1u)] = d;
+      continue;
+    }
     if (p.debug_stop == 10) continue;                       // profiling only: phase stops 10..13
     const uint8_t *doc = sm.text + shift;
     bool ubad = false, overflow = false, at_end = false, collide = false;

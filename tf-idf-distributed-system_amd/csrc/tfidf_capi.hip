@@ -1266,7 +1266,8 @@ static int commit_once(tfidf_index *ix, Snapshot &S) {
   S.nnz = hctr[2];
   S.NC = S.term_major ? 0u : (uint32_t)hctr[7];
   if (!S.term_major) HIP_TRY(S.blk.reserve((size_t)(S.n_blocks + 1) * S.NC * 4 + 16));
-  // CSR tf escapes (rare: block-major only for tf >= 2^17): sorted by entry
+  // CSR tf escapes (rare: block-major only for tf >= 65 535, the all-ones
+  // value of the 16-bit field, csr_esc_value(kRangeBits)): sorted by entry
   // index for the binary searches of the inversion and tfidf_doc_terms
   {
     const uint64_t n_esc = (uint32_t)hctr[9];

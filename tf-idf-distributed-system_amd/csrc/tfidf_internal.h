@@ -110,9 +110,12 @@ __host__ __device__ inline uint64_t csr_row_base(const uint64_t *offsets, uint64
 // segment it sits in names the range, rsplit), bits [range_shift, 32) = tf.
 // A tf the field cannot hold stores the all-ones escape there and the exact
 // value goes to the escape list ((entry index << 24) | tf, sorted by the host
-// after the build, binary-searched).  Block-major ranges are 2^15 slots, so
-// the field is 17 bits and only book-sized documents can escape; term-major
-// rows keep the whole slot (range_shift = log2 C).  A word is never 0 (tf >= 1).
+// after the build, binary-searched).  Block-major ranges are 2^16 slots
+// (kRangeSlots; the whole dictionary when it is smaller), so the field is 16
+// bits, escapes at tf >= 65 535 and only book-sized documents can escape;
+// term-major rows keep the whole slot (range_shift = log2 C), so their field
+// is 32 - log2 C bits (escape 16 383 at 2^18 slots, 511 at 2^23).  A word is
+// never 0 (tf >= 1).
 __host__ __device__ inline uint32_t csr_esc_value(uint32_t range_shift) { return 0xFFFFFFFFu >> range_shift; }
 __host__ __device__ inline uint32_t csr_local(uint32_t e, uint32_t range_shift) {
   return e & ((1u << range_shift) - 1u);
