@@ -15,7 +15,7 @@
  *       (called from the Files.walk loop Worker.java:77-86 and upload Worker.java:136-139)
  *   tfidf_commit
  *       Worker.java:88 and :138 indexWriter.commit() (+ DirectoryReader.open at :223 sees it)
- *   tfidf_search / tfidf_search_batch
+ *   tfidf_search / tfidf_search_batch / tfidf_search_batch_all
  *       Worker.java:222-241 searchIndex: QueryParser("contents", StandardAnalyzer)
  *       .parse(QueryParser.escape(q)); searcher.search(query, Integer.MAX_VALUE)
  *   tfidf_doc_key
@@ -188,15 +188,29 @@ int tfidf_search(tfidf_index *ix, const uint8_t *q, uint64_t q_len, uint32_t k, 
                  float *scores, uint64_t cap, uint64_t *n_out);
 /* n_q queries; query i = q_utf8[q_offsets[i] .. q_offsets[i+1]).  1 <= k <= 1024.
  * Outputs are n_q x k (row i holds counts[i] valid hits). */
-/* Concurrent single top-k searches (Worker.processDocuments on concurrent
- * request threads, Worker.java:175-186): same arguments and results as
- * tfidf_search with 1 <= k <= 1024, but callers arriving together are served
- * by ONE batched scoring launch (the first waits wait_us for companions).
+/* Concurrent single searches (Worker.processDocuments on concurrent request
+ * threads, Worker.java:175-186): same arguments and results as tfidf_search
+ * with k <= 1024, but callers arriving together are served by ONE batched
+ * scoring launch per kind (the first waits wait_us for companions): the top-k
+ * requests by tfidf_search_batch, the all-hits requests (k == 0, what every
+ * reference request asks for, Worker.java:230) by tfidf_search_batch_all.  A
+ * k == 0 caller whose cap is below its hit count gets TFIDF_E_BUFFER with
+ * *n_out set, like tfidf_search; the batch's other callers are unaffected.
  * Thread-safe; a caller blocks until its own results are written. */
 int tfidf_search_coalesced(tfidf_index *ix, const uint8_t *q, uint64_t q_len, uint32_t k, uint32_t *doc_ids,
                            float *scores, uint64_t cap, uint64_t *n_out, uint32_t wait_us);
 int tfidf_search_batch(tfidf_index *ix, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
                        uint32_t k, uint32_t *doc_ids, float *scores, uint32_t *counts);
+/* Every hit of each of n_q queries (tfidf_search with k == 0, per query):
+ * query i's hits are doc_ids/scores[hit_offsets[i] .. hit_offsets[i+1]), ordered
+ * (score desc, doc asc); hit_offsets has n_q + 1 entries and is always written
+ * in full.  *n_out = hit_offsets[n_q].  TFIDF_E_BUFFER when that exceeds cap
+ * (nothing is promised about doc_ids/scores then; call again with the size).
+ * A query that does not parse has no hits, as in tfidf_search_batch.
+ * Worker.java:230 for a batch of requests (cfg 4).  The device scratch is
+ * bounded: the queries are scored and merged in chunks. */
+int tfidf_search_batch_all(tfidf_index *ix, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                           uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out);
 /* Readers (Worker.java:223 DirectoryReader.open per request; the hits' stored
  * "path" fields are read from the same reader, :234-238): a reader pins the
  * snapshot published when it is opened, so doc ids it returns map to keys
@@ -211,6 +225,10 @@ int tfidf_reader_close(tfidf_reader *rd);
 int tfidf_reader_info(const tfidf_reader *rd, uint64_t *generation, uint64_t *num_docs);
 int tfidf_reader_search(tfidf_reader *rd, const uint8_t *q, uint64_t q_len, uint32_t k, uint32_t *doc_ids,
                         float *scores, uint64_t cap, uint64_t *n_out);
+/* tfidf_search_batch_all on the reader's snapshot. */
+int tfidf_reader_search_batch_all(tfidf_reader *rd, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                                  uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                                  uint64_t *n_out);
 int tfidf_reader_doc_key(const tfidf_reader *rd, uint64_t doc, uint8_t *buf, uint64_t cap, uint64_t *n_out);
 /* tfidf_doc_keys of the reader's snapshot (offsets[num_docs + 1] of tfidf_reader_info). */
 int tfidf_reader_doc_keys(const tfidf_reader *rd, uint8_t *buf, uint64_t cap, uint64_t *offsets, uint64_t *n_bytes);

@@ -332,6 +332,9 @@ __global__ void __launch_bounds__(kScoreThreads) k_score_blocks(QueryParams p) {
     const uint32_t t0 = q_off_of(p, q), t1 = q_off_of(p, q + 1);
     const uint32_t ngroups = kOps ? (q_meta_of(p, q) & 0xFFFFu) : 0u;
     bool alive = true;                                     // kOps: a document still meets every MUST clause
+    // kAll: some scoring term of the query has a posting in this block
+    bool some = false;
+    auto scores = [&](uint32_t j) { return !kOps || (q_role_of(p, j) >> 24) != kRoleNot; };
     if (p.toff) {
       // term-major layout: wave j finds term j's segment for this block in the
       // term's doc-sorted list (two 64-ary searches)
@@ -341,6 +344,7 @@ __global__ void __launch_bounds__(kScoreThreads) k_score_blocks(QueryParams p) {
         uint64_t a = 0, z = 0;
         if (slot != kInvalidSlot) term_block_range(p, slot, (uint32_t)d0, &a, &z);
         if ((tid & 63) == 0) { sm.tlo[wv] = a; sm.thi[wv] = z; sm.tw[wv] = q_w_of(p, t0 + wv); }
+        if (kAll) some = z > a && scores(t0 + wv);
       }
     } else if (tid < t1 - t0 && tid < kQTermsFast) {
       // block-major layout: all terms' ranges in one round trip (thread j fetches term j)
@@ -353,8 +357,36 @@ __global__ void __launch_bounds__(kScoreThreads) k_score_blocks(QueryParams p) {
       sm.tlo[tid] = a;
       sm.thi[tid] = z;
       sm.tw[tid] = q_w_of(p, t0 + tid);
+      if (kAll) some = z > a && scores(t0 + tid);
     }
-    __syncthreads();
+    if (kAll) {
+      // A pair in which no scoring term of the query has a posting (most pairs
+      // of a batch on a vocabulary-heavy corpus) leaves its empty run here,
+      // before any posting is read or the run is sorted; the test rides on the
+      // barrier the ranges need anyway.  Terms past the prefetched ones are
+      // looked up again when they are scored.
+      if (t1 - t0 > kQTermsFast) {
+        const uint32_t step = p.toff ? blockDim.x >> 6 : blockDim.x;
+        for (uint32_t j = t0 + kQTermsFast + (p.toff ? tid >> 6 : tid); j < t1; j += step) {
+          const uint32_t slot = q_slot_of(p, j);
+          if (slot == kInvalidSlot || !scores(j)) continue;      // term-major: j is wave-uniform
+          uint64_t a, z;
+          if (p.toff) {
+            term_block_range(p, slot, (uint32_t)d0, &a, &z);
+          } else {
+            a = row[slot];
+            z = slot + 1 < p.C ? row[slot + 1] : bend - bb;
+          }
+          some |= z > a;
+        }
+      }
+      if (!__syncthreads_or(some)) {
+        if (tid == 0) p.hits_n[q * p.hits_R2 + b] = 0;
+        continue;
+      }
+    } else {
+      __syncthreads();
+    }
     // first chunk of every term's postings in flight before any is consumed
     PostW<kTerm> pre[kQTermsFast];
 #pragma unroll
@@ -467,7 +499,7 @@ __global__ void __launch_bounds__(kScoreThreads) k_score_blocks(QueryParams p) {
     const uint32_t nhit = sm.nhit;
     const uint32_t bits = (sm.hitbits[tid >> 1] >> (16 * (tid & 1))) & 0xFFFFu;
     if (kAll) {
-      // all-hits mode (single query): the block's hit keys (score bits << 32 |
+      // all-hits mode: the block's hit keys (score bits << 32 |
       // ~doc), compacted and sorted descending in LDS (bitonic over the
       // accumulator's 64 KiB) -> one sorted run per block for k_merge_runs
       uint64_t kv[kDocsPerThread];
@@ -498,8 +530,9 @@ __global__ void __launch_bounds__(kScoreThreads) k_score_blocks(QueryParams p) {
           __syncthreads();
         }
       }
-      for (uint32_t i = tid; i < nhit; i += blockDim.x) p.hits[(size_t)b * kBlockDocs + i] = keys[i];
-      if (tid == 0) p.hits_n[b] = nhit;
+      const uint32_t run = q * p.hits_R2 + b;              // batch: query q's runs start at q * R2
+      for (uint32_t i = tid; i < nhit; i += blockDim.x) p.hits[(size_t)run * kBlockDocs + i] = keys[i];
+      if (tid == 0) p.hits_n[run] = nhit;
       __syncthreads();
       continue;
     }
@@ -1667,6 +1700,67 @@ hipError_t launch_hits_order(const uint64_t *hits, const uint32_t *hits_n, uint3
     mp.dst = mp.final && keys_out ? keys_out : bufs[L & 1];
     mp.out_doc = mp.final && !keys_out ? out_doc : nullptr;
     mp.out_score = mp.final && !keys_out ? out_score : nullptr;
+    hipLaunchKernelGGL(k_merge_runs, dim3(grid), dim3(256), 0, s, mp);
+    src = bufs[L & 1];
+  }
+  return hipGetLastError();
+}
+
+// Batched all hits: the runs of a chunk of n_q queries, query q's block b being
+// run q * R2 + b (R2 a power of two >= 2; runs R .. R2 - 1 of each query are
+// empty).  One prefix sum over all n_q * R2 runs gives every run's output
+// offset, and P[q * R2] is query q's offset in the chunk's contiguous output,
+// so the hit counts come out of the same scan.  Merge level l pairs runs
+// [2^(l+1) m, 2^(l+1) (m + 1)): for l < log2(R2) a pair lies inside one query,
+// so the single-query kernels merge the whole chunk unchanged and stop after
+// log2(R2) levels.  The 8-run group merge needs R2 >= 8 (a group of a smaller
+// R2 would span queries): below that the pairwise levels run.
+__global__ void k_query_offsets(const uint64_t *P, uint32_t R2, uint32_t n_q, uint64_t *q_off) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q <= n_q) q_off[q] = P[(uint64_t)q * R2];
+}
+
+hipError_t launch_hits_order_batch(uint64_t *hits, const uint32_t *hits_n, uint32_t n_q, uint32_t R, uint64_t *P,
+                                   uint64_t *tmp0, uint64_t *tmp2, uint32_t *out_doc, float *out_score,
+                                   uint64_t *q_off, uint64_t hits_bound, int grid, hipStream_t s) {
+  const uint32_t R2 = hits_runs_per_query(R), RT = n_q * R2;
+  hipLaunchKernelGGL(k_hits_prefix, dim3(1), dim3(1024), 0, s, hits_n, RT, P);
+  hipLaunchKernelGGL(k_query_offsets, dim3(n_q / 256 + 1), dim3(256), 0, s, P, R2, n_q, q_off);
+  uint32_t levels = 1;
+  while ((1u << levels) < R2) levels++;
+  MergeRunsParams mp{};
+  mp.P = P;
+  mp.R = RT;
+  const uint64_t *src = hits;
+  uint64_t *bufs[2] = {tmp0, hits};
+  uint32_t L0 = 0;
+  // the group merge is chosen for the chunk: its queries' hit bounds averaged
+  // over its groups (launch_hits_order's rule for one query)
+  bool groups = hits_bound * kGroupRuns <= (uint64_t)n_q * R * kHitsGroupAvg;
+  if (knob("TFIDF_HITS_PAIRWISE")) groups = false;
+  if (knob("TFIDF_HITS_GROUPS")) groups = true;
+  if (groups && R2 >= kGroupRuns) {
+    static std::atomic<uint64_t> big{0};
+    allow_dyn_lds((const void *)k_merge_group, 2 * kGroupCap * 8, big);
+    mp.src = hits;
+    mp.gapped = 1;
+    mp.final = levels <= 3;
+    mp.dst = tmp0;
+    mp.out_doc = mp.final ? out_doc : nullptr;
+    mp.out_score = mp.final ? out_score : nullptr;
+    hipLaunchKernelGGL(k_merge_group, dim3(RT / kGroupRuns), dim3(kGroupThreads), 2 * kGroupCap * 8, s, mp, tmp2);
+    if (mp.final) return hipGetLastError();
+    src = tmp0;
+    L0 = 3;
+  }
+  for (uint32_t L = L0; L < levels; L++) {
+    mp.src = src;
+    mp.level = L;
+    mp.gapped = L == 0;
+    mp.final = L + 1 == levels;
+    mp.dst = bufs[L & 1];
+    mp.out_doc = mp.final ? out_doc : nullptr;
+    mp.out_score = mp.final ? out_score : nullptr;
     hipLaunchKernelGGL(k_merge_runs, dim3(grid), dim3(256), 0, s, mp);
     src = bufs[L & 1];
   }

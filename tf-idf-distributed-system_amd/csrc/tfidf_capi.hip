@@ -1844,8 +1844,10 @@ static int scoring_done() {
   return fail(TFIDF_E_HIP, "injected scoring failure (TFIDF_TEST_FAIL_SCORING)");
 }
 
+// all_R2 (k == 0, a batch): runs per query of the batched all-hits layout
+// (launch_hits_order_batch); 0: one query's runs, one per block.
 static int run_scoring(tfidf_index *ix, Snapshot &S, StatsView &V, SearchCtx &X, hipStream_t s, const QueryBatch &qb,
-                       uint32_t n_q, uint32_t k) {
+                       uint32_t n_q, uint32_t k, uint32_t all_R2 = 0) {
   const std::vector<uint32_t> &qoff = qb.off, &slots = qb.slot;
   const size_t ns = slots.size(), nr = qb.ops ? ns + qb.meta.size() : 0;
   const size_t npairs = (size_t)n_q * S.n_blocks;
@@ -1957,6 +1959,14 @@ static int run_scoring(tfidf_index *ix, Snapshot &S, StatsView &V, SearchCtx &X,
     qp.out_doc = X.res_doc;
     qp.out_score = X.res_score;
     qp.out_n = X.res_n;
+  } else if (all_R2) {
+    const size_t runs = (size_t)n_q * all_R2;
+    HIP_TRY(X.hits.reserve(runs * kBlockDocs * 8 + 8));
+    HIP_TRY(X.hits_n.reserve(runs * 4 + 4));
+    qp.hits = X.hits.as<uint64_t>();
+    qp.hits_n = X.hits_n.as<uint32_t>();
+    qp.hits_R2 = all_R2;
+    HIP_TRY(hipMemsetAsync(qp.hits_n, 0, runs * 4, s));   // the padding runs stay empty
   } else {
     HIP_TRY(X.hits.reserve((size_t)S.n_blocks * kBlockDocs * 8 + 8));
     HIP_TRY(X.hits_n.reserve((size_t)S.n_blocks * 4 + 4));
@@ -2340,14 +2350,138 @@ extern "C" int tfidf_search_batch(tfidf_index *ix, const uint8_t *q_utf8, const 
   return TFIDF_OK;
 }
 
+// Every hit of each query of a batch (tfidf_search_batch_all): the queries are
+// prepared together, then scored and merged in chunks (launch_hits_order_batch)
+// whose scratch stays under kAllHitsBudget however many queries the batch
+// holds.  Per chunk: the gapped runs take R2 x 64 KiB per query (8 MiB at 1 M
+// documents), the two compact merge buffers and the (doc, score) output 8 B
+// each per possible hit (a query's hits are bounded by the sum of its scoring
+// terms' df).  1 GiB: about 120 mid-frequency queries per chunk at 1 M
+// documents, so the chunk's one upload, ~6 launches and two syncs are spread
+// over two orders of magnitude more queries than the single search's, while
+// sixteen concurrent callers' contexts together stay near 5 % of the 288 GB.
+// A chunk always holds at least one query.  TFIDF_ALLHITS_CHUNK=<queries>
+// fixes the chunk size (tests).
+constexpr uint64_t kAllHitsBudget = 1ull << 30;
+
+static int batch_all_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *q_utf8, const uint64_t *q_offsets,
+                        uint32_t n_q, uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                        uint64_t *n_out) {
+  for (uint32_t i = 0; i <= n_q; i++) hit_offsets[i] = 0;
+  *n_out = 0;
+  if (n_q == 0 || S.n_docs == 0) return TFIDF_OK;
+  CtxLease lease(ix);
+  if (lease.rc) return lease.rc;
+  SearchCtx &X = *lease.c;
+  const hipStream_t s = lease.stream();
+  DeviceGuard g(ix->cfg.device);
+  QueryBatch qb;
+  if (int e = prepare_batch(ix, S, V, q_utf8, q_offsets, n_q, &qb)) return e;
+  const uint32_t R = S.n_blocks, R2 = hits_runs_per_query(R);
+  const uint64_t gap_bytes = (uint64_t)R2 * kBlockDocs * 8;
+  uint32_t fixed = 0;
+  if (const char *e = knob("TFIDF_ALLHITS_CHUNK")) fixed = (uint32_t)std::max(1, atoi(e));
+  const uint32_t max_q = std::max(1u, (1u << 30) / R2);     // run indices stay in 32 bits
+  std::vector<uint64_t> qoff_h;
+  uint64_t total = 0;
+  bool any = false, fits = true;
+  for (uint32_t a = 0; a < n_q;) {
+    // chunk [a, z): queries while the chunk's scratch stays in the budget
+    uint32_t z = a;
+    uint64_t bound = 0, bytes = 0;
+    while (z < n_q && z - a < max_q) {
+      uint64_t hb = 0;
+      for (uint32_t t = qb.off[z]; t < qb.off[z + 1]; t++)
+        if ((qb.role[t] >> 24) != kRoleNot) hb += qb.ldf[t];
+      hb = std::min<uint64_t>(hb, S.n_docs);
+      if (z > a && (fixed ? z - a >= fixed : bytes + gap_bytes + hb * 24 > kAllHitsBudget)) break;
+      bound += hb;
+      bytes += gap_bytes + hb * 24;
+      z++;
+    }
+    const uint32_t nc = z - a;
+    const uint32_t t0 = qb.off[a], t1 = qb.off[z];
+    if (t1 > t0) {
+      QueryBatch sub;
+      sub.off.resize(nc + 1);
+      for (uint32_t i = 0; i <= nc; i++) sub.off[i] = qb.off[a + i] - t0;
+      sub.slot.assign(qb.slot.begin() + t0, qb.slot.begin() + t1);
+      sub.w.assign(qb.w.begin() + t0, qb.w.begin() + t1);
+      sub.role.assign(qb.role.begin() + t0, qb.role.begin() + t1);
+      sub.ldf.assign(qb.ldf.begin() + t0, qb.ldf.begin() + t1);
+      sub.meta.assign(qb.meta.begin() + a, qb.meta.begin() + z);
+      for (uint32_t m : sub.meta) sub.ops |= m != 0;
+      X.q_rec_start = !any;
+      const int rc = run_scoring(ix, S, V, X, s, sub, nc, 0, R2);
+      X.q_rec_start = true;
+      if (rc) return rc;
+      any = true;
+      const size_t runs = (size_t)nc * R2;
+      HIP_TRY(X.hits_c.reserve(bound * 8 + 8));
+      HIP_TRY(X.hits_s.reserve(bound * 8 + 8));
+      HIP_TRY(X.hits_P.reserve((runs + 1 + nc + 1) * 8));
+      HIP_TRY(X.out_doc.reserve(bound * 4 + 4));
+      HIP_TRY(X.out_score.reserve(bound * 4 + 4));
+      uint64_t *d_qoff = X.hits_P.as<uint64_t>() + runs + 1;
+      HIP_TRY(launch_hits_order_batch(X.hits.as<uint64_t>(), X.hits_n.as<uint32_t>(), nc, R, X.hits_P.as<uint64_t>(),
+                                      X.hits_c.as<uint64_t>(), X.hits_s.as<uint64_t>(), X.out_doc.as<uint32_t>(),
+                                      X.out_score.as<float>(), d_qoff, bound, ix->num_cus * 4, s));
+      if (X.q_timing) HIP_TRY(hipEventRecord(X.ev[QEV_2], s));
+      qoff_h.resize(nc + 1);
+      HIP_TRY(hipMemcpyAsync(qoff_h.data(), d_qoff, ((size_t)nc + 1) * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      X.q_in_pending = false;
+      const uint64_t H = qoff_h[nc];
+      for (uint32_t i = 1; i <= nc; i++) hit_offsets[a + i] = total + qoff_h[i];
+      fits = fits && total + H <= cap;
+      if (fits && H) {
+        // the chunk's hits, contiguous, at the batch's running offset
+        HIP_TRY(hipMemcpyAsync(doc_ids + total, X.out_doc.p, H * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(scores + total, X.out_score.p, H * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+      }
+      total += H;
+    } else {
+      for (uint32_t i = 1; i <= nc; i++) hit_offsets[a + i] = total;     // no term of the chunk is present
+    }
+    a = z;
+  }
+  *n_out = total;
+  set_last_ms(ix, any ? qev_ms(X, QEV_0, QEV_1) : 0.0f, any ? qev_ms(X, QEV_0, QEV_2) : 0.0f);
+  if (!fits) return fail(TFIDF_E_BUFFER, "need %llu result slots", (unsigned long long)total);
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_search_batch_all(tfidf_index *ix, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                                      uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                                      uint64_t *n_out) {
+  if (!ix || !hit_offsets || !n_out || (n_q && !q_offsets) || (cap && (!doc_ids || !scores)))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::shared_ptr<StatsView> view;
+  const std::shared_ptr<Snapshot> snap = current(ix, &view);
+  if (!snap) return fail(TFIDF_E_STATE, "search before commit");
+  return batch_all_on(ix, *snap, *view, q_utf8, q_offsets, n_q, doc_ids, scores, cap, hit_offsets, n_out);
+}
+
+extern "C" int tfidf_reader_search_batch_all(tfidf_reader *rd, const uint8_t *q_utf8, const uint64_t *q_offsets,
+                                             uint32_t n_q, uint32_t *doc_ids, float *scores, uint64_t cap,
+                                             uint64_t *hit_offsets, uint64_t *n_out) {
+  if (!rd || !hit_offsets || !n_out || (n_q && !q_offsets) || (cap && (!doc_ids || !scores)))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  return batch_all_on(rd->ix, *rd->S, *rd->V, q_utf8, q_offsets, n_q, doc_ids, scores, cap, hit_offsets, n_out);
+}
+
 // Concurrent single searches (the reference's Worker.processDocuments runs on
 // concurrent request threads, Worker.java:175-186).  Requests queue up; the
 // first caller to find no batch forming leads one: it waits wait_us for
 // companions, takes every queued request (up to cq_max), runs them
-// through the batched scorer (tfidf_search_batch: one launch for all) and
-// hands each caller its own top-k; callers arriving meanwhile form the next
-// batch.  Results are those of tfidf_search(k) for each query, including its
-// errors (a query that does not parse gets TFIDF_E_QUERY_SYNTAX, not []).
+// through the batched scorers (top-k requests: tfidf_search_batch, one launch
+// for all; all-hits requests, k == 0, the shape every reference request has,
+// Worker.java:230: tfidf_search_batch_all) and hands each caller its own
+// hits; callers arriving meanwhile form the next batch.  Results are those of
+// tfidf_search(k) for each query, including its errors (a query that does not
+// parse gets TFIDF_E_QUERY_SYNTAX, not []; a k == 0 caller whose cap is below
+// its hit count gets TFIDF_E_BUFFER with *n_out set, the others unaffected).
 struct CoalesceReq {
   const uint8_t *q;
   uint64_t len;
@@ -2363,11 +2497,12 @@ struct CoalesceReq {
 };
 
 // One coalesced batch: queries that do not parse answer as tfidf_search
-// would; the rest go through one tfidf_search_batch launch.
+// would; the top-k requests go through one tfidf_search_batch launch, the
+// all-hits requests (k == 0) through one tfidf_search_batch_all.
 static void coalesced_run(tfidf_index *ix, const std::vector<CoalesceReq *> &batch) {
-  std::vector<CoalesceReq *> run;
-  std::vector<uint8_t> text;
-  std::vector<uint64_t> offs{0};
+  std::vector<CoalesceReq *> run, run_all;
+  std::vector<uint8_t> text, text_all;
+  std::vector<uint64_t> offs{0}, offs_all{0};
   uint32_t kmax = 0;
   for (CoalesceReq *c : batch) {
     QueryPlan plan;
@@ -2379,25 +2514,61 @@ static void coalesced_run(tfidf_index *ix, const std::vector<CoalesceReq *> &bat
       *c->n_out = 0;
       continue;
     }
-    run.push_back(c);
-    text.insert(text.end(), c->q, c->q + c->len);
-    offs.push_back(text.size());
+    std::vector<uint8_t> &tx = c->k ? text : text_all;
+    tx.insert(tx.end(), c->q, c->q + c->len);
+    (c->k ? offs : offs_all).push_back(tx.size());
+    (c->k ? run : run_all).push_back(c);
     kmax = std::max(kmax, c->k);
   }
-  if (run.empty()) return;
-  std::vector<uint32_t> docs((size_t)run.size() * kmax), counts(run.size());
-  std::vector<float> sc((size_t)run.size() * kmax);
-  const int rc = tfidf_search_batch(ix, text.data(), offs.data(), (uint32_t)run.size(), kmax, docs.data(), sc.data(),
-                                    counts.data());
-  const std::string err = rc != TFIDF_OK ? std::string(tfidf_last_error()) : std::string();
-  for (size_t i = 0; i < run.size(); i++) {
-    CoalesceReq *c = run[i];
-    if (rc != TFIDF_OK) { c->rc = rc; c->err = err; *c->n_out = 0; continue; }
-    const uint64_t n = std::min<uint64_t>(counts[i], c->k);     // a prefix of the kmax list = the top-k
-    *c->n_out = n;
-    if (n > c->cap) { c->rc = TFIDF_E_BUFFER; c->err = "result buffer too small"; continue; }
-    memcpy(c->docs, docs.data() + i * kmax, n * 4);
-    memcpy(c->scores, sc.data() + i * kmax, n * 4);
+  if (!run.empty()) {
+    std::vector<uint32_t> docs((size_t)run.size() * kmax), counts(run.size());
+    std::vector<float> sc((size_t)run.size() * kmax);
+    const int rc = tfidf_search_batch(ix, text.data(), offs.data(), (uint32_t)run.size(), kmax, docs.data(), sc.data(),
+                                      counts.data());
+    const std::string err = rc != TFIDF_OK ? std::string(tfidf_last_error()) : std::string();
+    for (size_t i = 0; i < run.size(); i++) {
+      CoalesceReq *c = run[i];
+      if (rc != TFIDF_OK) { c->rc = rc; c->err = err; *c->n_out = 0; continue; }
+      const uint64_t n = std::min<uint64_t>(counts[i], c->k);     // a prefix of the kmax list = the top-k
+      *c->n_out = n;
+      if (n > c->cap) { c->rc = TFIDF_E_BUFFER; c->err = "result buffer too small"; continue; }
+      memcpy(c->docs, docs.data() + i * kmax, n * 4);
+      memcpy(c->scores, sc.data() + i * kmax, n * 4);
+    }
+  }
+  if (!run_all.empty()) {
+    // the batch's own buffer: sized by the callers' capacities first, by the
+    // reported size when some caller's hits exceed its capacity
+    const uint32_t n = (uint32_t)run_all.size();
+    uint64_t cap = 0, total = 0;
+    const std::shared_ptr<Snapshot> snap = current(ix);
+    const uint64_t n_docs = snap ? snap->n_docs : 0;
+    for (CoalesceReq *c : run_all) cap += std::min(c->cap, n_docs);
+    std::vector<uint32_t> docs(cap);
+    std::vector<float> sc(cap);
+    std::vector<uint64_t> ho(n + 1);
+    int rc = tfidf_search_batch_all(ix, text_all.data(), offs_all.data(), n, docs.data(), sc.data(), cap, ho.data(),
+                                    &total);
+    if (rc == TFIDF_E_BUFFER) {
+      docs.resize(total);
+      sc.resize(total);
+      rc = tfidf_search_batch_all(ix, text_all.data(), offs_all.data(), n, docs.data(), sc.data(), total, ho.data(),
+                                  &total);
+    }
+    const std::string err = rc != TFIDF_OK ? std::string(tfidf_last_error()) : std::string();
+    for (uint32_t i = 0; i < n; i++) {
+      CoalesceReq *c = run_all[i];
+      if (rc != TFIDF_OK) { c->rc = rc; c->err = err; *c->n_out = 0; continue; }
+      const uint64_t h = ho[i + 1] - ho[i];
+      *c->n_out = h;
+      if (h > c->cap) {
+        c->rc = TFIDF_E_BUFFER;
+        c->err = "need " + std::to_string(h) + " result slots";
+        continue;
+      }
+      memcpy(c->docs, docs.data() + ho[i], h * 4);
+      memcpy(c->scores, sc.data() + ho[i], h * 4);
+    }
   }
 }
 
@@ -2405,7 +2576,7 @@ static void coalesced_run(tfidf_index *ix, const std::vector<CoalesceReq *> &bat
 extern "C" int tfidf_search_coalesced(tfidf_index *ix, const uint8_t *q, uint64_t q_len, uint32_t k, uint32_t *doc_ids,
                                       float *scores, uint64_t cap, uint64_t *n_out, uint32_t wait_us) {
   if (!ix || (!q && q_len) || !n_out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
-  if (k == 0 || k > 1024) return fail(TFIDF_E_INVALID_ARG, "coalesced search needs 1 <= k <= 1024 (all hits: tfidf_search)");
+  if (k > 1024) return fail(TFIDF_E_INVALID_ARG, "coalesced search needs k <= 1024 (0 = all hits)");
   CoalesceReq r{q, q_len, k, doc_ids, scores, cap, n_out, TFIDF_OK, std::string(), false, false};
   std::unique_lock<std::mutex> lk(ix->cq_mu);
   ix->cq.push_back(&r);

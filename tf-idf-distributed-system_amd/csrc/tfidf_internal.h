@@ -353,6 +353,7 @@ struct QueryParams {
   // all-hits mode
   uint64_t *hits;             // [n_blocks * kBlockDocs] keys (score bits << 32 | ~doc)
   uint32_t *hits_n;           // [n_blocks]
+  uint32_t hits_R2;           // batched all hits: query q's block b is run q * hits_R2 + b (0: one query)
   // wave-per-pair path (k > 0): pairs it leaves to k_score_blocks (nullptr = dense grid mode)
   uint32_t *ovf_list;         // pair ids q * n_blocks + b
   uint32_t *ovf_count;        // zeroed before k_score_pairs
@@ -397,6 +398,20 @@ hipError_t launch_hits_order(const uint64_t *hits, const uint32_t *hits_n, uint3
                              uint64_t *tmp1, uint64_t *tmp2, uint32_t *out_doc, float *out_score, uint64_t *keys_out,
                              uint64_t doc_base, uint64_t hits_bound, int grid, hipStream_t s);
 constexpr uint64_t kHitsGroupAvg = 6144;   // all hits: 8-run LDS group merge when hits per group average <= this
+// all hits of a chunk of n_q queries: runs indexed q * R2 + b (R2 = hits_runs_per_query(R):
+// a power of two >= 2, the padding runs empty with hits_n = 0), so no merge level spans two
+// queries.  P: n_q * R2 + 1 u64; q_off [n_q + 1]: each query's offset in out_doc / out_score
+// (q_off[n_q] = the chunk's hits).  hits holds n_q * R2 * kBlockDocs u64 (gapped runs) and is
+// reused as a merge buffer; tmp0 / tmp2 hold the chunk's hits (hits_bound: an upper bound of
+// them, summed over the chunk's queries).
+constexpr uint32_t hits_runs_per_query(uint32_t R) {
+  uint32_t r2 = 2;
+  while (r2 < R) r2 <<= 1;
+  return r2;
+}
+hipError_t launch_hits_order_batch(uint64_t *hits, const uint32_t *hits_n, uint32_t n_q, uint32_t R, uint64_t *P,
+                                   uint64_t *tmp0, uint64_t *tmp2, uint32_t *out_doc, float *out_score,
+                                   uint64_t *q_off, uint64_t hits_bound, int grid, hipStream_t s);
 
 // --- GLOBAL statistics by term ownership (kernels_vocab.hip) ---
 hipError_t vocab_count(const uint64_t *dict, uint32_t C, uint32_t G, uint32_t *counts, hipStream_t s);

@@ -26,6 +26,34 @@ def term_key(term: bytes):
     return lo.value, hi.value
 
 
+def _batch_all_arrays(fn, handle, queries, cap):
+    """tfidf_search_batch_all / tfidf_reader_search_batch_all: one call with
+    ``cap`` result slots, and once more with the size the library reports when
+    that was too small.  -> (docs uint32[], scores float32[], offsets uint64[n_q + 1])."""
+    nq = len(queries)
+    offs = np.zeros(nq + 1, np.uint64)
+    if nq:
+        offs[1:] = np.cumsum([len(q) for q in queries], dtype=np.uint64)
+    blob = b"".join(queries)
+    hit_offs = np.zeros(nq + 1, np.uint64)
+    n = C.c_uint64()
+    for _ in range(2):
+        docs = np.empty(max(cap, 1), np.uint32)
+        scores = np.empty(max(cap, 1), np.float32)
+        rc = fn(handle, blob, L.ptr(offs, C.c_uint64), nq, L.ptr(docs, C.c_uint32), L.ptr(scores, C.c_float), cap,
+                L.ptr(hit_offs, C.c_uint64), C.byref(n))
+        if rc != L.E_BUFFER:
+            break
+        cap = n.value
+    L.check(rc)
+    return docs[:n.value], scores[:n.value], hit_offs
+
+
+def _hit_lists(docs, scores, offs):
+    d, s, o = docs.tolist(), scores.tolist(), offs.tolist()
+    return [list(zip(d[o[i]:o[i + 1]], s[o[i]:o[i + 1]])) for i in range(len(o) - 1)]
+
+
 class ShardIndex:
     def __init__(self, device=0, k1=1.2, b=0.75, vocab_capacity_log2=18, stats_mode=L.STATS_SHARD,
                  inversion=L.INVERSION_AUTO):
@@ -138,16 +166,35 @@ class ShardIndex:
         """A Reader on the snapshot published now (tfidf_reader_open)."""
         return Reader(self)
 
-    def search_coalesced(self, query: bytes, k, wait_us=50):
-        """Thread-safe top-k search that shares one batched scoring launch with
-        the searches other threads issue at the same time (tfidf_search_coalesced)."""
-        docs = np.zeros(k, np.uint32)
-        scores = np.zeros(k, np.float32)
+    def search_coalesced(self, query: bytes, k, wait_us=50, cap=None):
+        """Thread-safe search that shares one batched scoring launch with the
+        searches other threads issue at the same time (tfidf_search_coalesced).
+        k == 0: all hits (the reference's request shape, Worker.java:230), in
+        ``cap`` result slots (default: the documents committed now)."""
+        if cap is None:
+            cap = k if k else max(self.stats()["num_docs"], 1)
+        docs = np.empty(max(cap, 1), np.uint32)
+        scores = np.empty(max(cap, 1), np.float32)
         n = C.c_uint64()
         L.check(L.load().tfidf_search_coalesced(self._h, query, len(query), k, L.ptr(docs, C.c_uint32),
-                                                L.ptr(scores, C.c_float), k, C.byref(n), wait_us))
+                                                L.ptr(scores, C.c_float), cap, C.byref(n), wait_us))
         m = n.value
         return list(zip(docs[:m].tolist(), scores[:m].tolist()))
+
+    def search_batch_all_arrays(self, queries, cap=None):
+        """Every hit of each query in one pass (tfidf_search_batch_all):
+        (docs uint32[], scores float32[], offsets uint64[n_q + 1]); query i's
+        hits are [offsets[i], offsets[i + 1]), in (score desc, doc asc).  ``cap``:
+        result slots of the first attempt; the call is repeated once with the
+        size the library reports when they do not suffice."""
+        if cap is None:
+            cap = min(65536 * max(len(queries), 1), 1 << 24)
+        return _batch_all_arrays(L.load().tfidf_search_batch_all, self._h, queries, cap)
+
+    def search_batch_all(self, queries):
+        """[search(q, 0) for q in queries] in one pass; a query that does not
+        parse has no hits (as in search_batch)."""
+        return _hit_lists(*self.search_batch_all_arrays(queries))
 
     def search_all_arrays(self, query: bytes):
         """All hits as (doc uint32[], score float32[]) in (score desc, doc asc)
@@ -383,6 +430,15 @@ class Reader:
     def search(self, query: bytes, k=0):
         d, s = self.search_arrays(query, k)
         return list(zip(d.tolist(), s.tolist()))
+
+    def search_batch_all_arrays(self, queries, cap=None):
+        """ShardIndex.search_batch_all_arrays on this reader's snapshot."""
+        if cap is None:
+            cap = min(65536 * max(len(queries), 1), 1 << 24)
+        return _batch_all_arrays(L.load().tfidf_reader_search_batch_all, self._h, queries, cap)
+
+    def search_batch_all(self, queries):
+        return _hit_lists(*self.search_batch_all_arrays(queries))
 
     def doc_key(self, doc):
         buf = C.create_string_buffer(4096)

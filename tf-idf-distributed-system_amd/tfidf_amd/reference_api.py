@@ -148,6 +148,30 @@ class Worker:
         except Exception:
             return []
 
+    # /worker/process for the requests of concurrent threads (Worker.java:175-186,
+    # cfg 4) in one pass: process_documents(q) for each query, every hit of all
+    # of them from one batched all-hits search on one reader
+    def process_documents_batch(self, search_queries):
+        out = [[] for _ in search_queries]
+        enc, at = [], []
+        for i, q in enumerate(search_queries):
+            try:
+                enc.append(q.encode())
+                at.append(i)
+            except Exception:
+                pass                          # that request's exception -> its empty list
+        try:
+            with self.index.reader() as rd:
+                names = {}
+                for i, hits in zip(at, rd.search_batch_all(enc)):
+                    for d, _ in hits:
+                        if d not in names:
+                            names[d] = rd.doc_key(d).decode()
+                    out[i] = [document_score_info(names[d], s) for d, s in hits]
+        except Exception:
+            return [[] for _ in search_queries]
+        return out
+
     def close(self):
         self.index.close()
 
