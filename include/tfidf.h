@@ -89,8 +89,11 @@ typedef struct tfidf_config {
   float b;                      /* BM25 b,  default 0.75f */
   int32_t stats_mode;           /* TFIDF_STATS_SHARD (default) or TFIDF_STATS_GLOBAL */
   int32_t device;               /* HIP device ordinal */
-  uint32_t vocab_capacity_log2; /* dictionary slots = 2^x, x in [10, 26]; default 18 (<= ~200k terms);
-                                   x > 21 implies the term-major inversion */
+  uint32_t vocab_capacity_log2; /* dictionary slots = 2^x, x in [10, 26]; default 18.  A shard holds at most
+                                   2^x distinct terms, exactly: a commit of 2^x terms succeeds on every
+                                   tokenizer path, one of 2^x + 1 returns TFIDF_E_CAPACITY (see
+                                   tfidf_commit).  The default is meant for <= ~200k terms (probes get
+                                   longer as the table fills); x > 21 implies the term-major inversion */
   uint32_t max_token_len;       /* StandardAnalyzer.DEFAULT_MAX_TOKEN_LENGTH = 255 (only value supported) */
   int32_t inversion;            /* TFIDF_INVERSION_AUTO (default), _BLOCK or _TERM */
 } tfidf_config;
@@ -161,6 +164,25 @@ int tfidf_clear(tfidf_index *ix);
 int tfidf_add_docs_device(tfidf_index *ix, const void *d_utf8, const void *d_offsets, uint64_t n_docs,
                           uint64_t total_bytes);
 
+/* Build the index of the staged documents and publish it (IndexWriter.commit).
+ * A commit that fails publishes nothing:
+ *   - it returns the error (TFIDF_E_CAPACITY: more than 2^vocab_capacity_log2
+ *     distinct terms, tfidf_last_error names the slot count;
+ *     TFIDF_E_UNSUPPORTED_INPUT: a term more than 2^24 - 1 times in one
+ *     document, which tf 2^24 - 1 itself is not);
+ *   - searches, readers (those open and those opened afterwards), tfidf_stats'
+ *     index fields, tfidf_term_df, tfidf_doc_* and tfidf_malformed_docs keep
+ *     serving the last successful commit, bit for bit, and no commit
+ *     generation is used up; before the first successful commit the index
+ *     answers as a new one does (searches and tfidf_reader_open:
+ *     TFIDF_E_STATE; tfidf_stats: num_docs 0);
+ *   - every staged document stays staged (tfidf_stats.text_bytes and
+ *     device_bytes count the staged corpus, not the published one), so
+ *     calling tfidf_commit again fails the same way;
+ *   - to recover, replace the offending documents by key (tfidf_add_docs with
+ *     their keys) or tfidf_clear and add a corpus that fits, then commit: the
+ *     result is that of a new index given the same documents.  The index may
+ *     also be destroyed and created again with a larger vocab_capacity_log2. */
 int tfidf_commit(tfidf_index *ix);
 /* GLOBAL statistics match terms across shards by their keys, so every shard
  * must hash its long / non-ASCII terms with one seed.  A commit tries seed

@@ -25,8 +25,9 @@ Bar: every document's terms and lengths, DF, the index statistics and hits
 tfs equal the counts the corpus was built with; again after save / load into
 a fresh index.
 
-Out of scope: the kMaxTf limit (2^24 - 1, tfidf_common.h) needs a single
-document of 33 MB; it is not tested here.
+Out of scope here: the kMaxTf limit (2^24 - 1, tfidf_common.h), which needs
+a single document of 33 MB; test_gpu_capacity.py pins it on both sides
+(test_tf_at_and_past_the_limit).
 """
 import collections
 import random
