@@ -30,6 +30,10 @@
  *   tfidf_node_* / tfidf_dist_* / tfidf_comm_*
  *       Leader.java:39-92 start (fan-out :51-70 over Worker.java:222-241, merge :73-88)
  *       with the workers as GPU shards and RCCL collectives in place of HTTP
+ *   tfidf_node_search_batch_all / tfidf_dist_search_batch_all (GLOBAL),
+ *   tfidf_node_search_names_batch / tfidf_dist_shard_search_batch (SHARD)
+ *       the same for a batch of requests (Worker.java:230: every request asks
+ *       for all hits), every hit of every query in one pass over the shards
  *
  * Conventions: every call returns an int status (TFIDF_OK == 0); the message
  * of the last failure on the calling thread is tfidf_last_error().  Buffers
@@ -494,6 +498,39 @@ int tfidf_dist_search_batch(tfidf_index *ix, tfidf_comm *c, uint64_t doc_base, c
 int tfidf_dist_shard_commit(tfidf_index *ix, tfidf_comm *c, uint64_t *n_names);
 int tfidf_dist_shard_search(tfidf_index *ix, tfidf_comm *c, const uint8_t *q, uint64_t q_len, uint64_t *n_out,
                             uint64_t *n_bytes);
+/* All-hits batches (Worker.java:230 for a batch of requests, over the ranks).
+ * tfidf_dist_search_batch_all (GLOBAL): tfidf_search_batch_all's contract with
+ *   global doc ids: query i's hits are doc_ids/scores[hit_offsets[i] ..
+ *   hit_offsets[i+1]) in (score desc, doc asc) order over all ranks;
+ *   hit_offsets (n_q + 1 entries) and *n_out are always written in full;
+ *   TFIDF_E_BUFFER when the total exceeds cap (nothing is promised about
+ *   doc_ids / scores then).  A query that does not parse has no hits and does
+ *   not fail the batch.  Collective: every rank takes part in every collective
+ *   whatever its own cap; a rank called with cap == 0 gets the offsets only
+ *   (no result merge, no copy-out).  The first collective carries every rank's
+ *   status and per-query hit bounds: a stale GLOBAL generation fails on every
+ *   rank with TFIDF_E_STATE, overlapping doc ranges with TFIDF_E_INVALID_ARG,
+ *   as tfidf_dist_search.  The batch is served in node chunks of queries whose
+ *   boundaries every rank derives from the gathered bounds alone; each chunk's
+ *   count row carries the rank's status, so a rank that fails inside a chunk
+ *   (TFIDF_E_HIP, TFIDF_E_OOM) fails the call on every rank at that chunk.
+ * tfidf_dist_shard_search_batch (SHARD): tfidf_dist_shard_search's result for
+ *   each query (distinct names in String.compareTo order, each the double sum
+ *   of its hits' float scores in rank order), searched once; *n_out names in
+ *   all, *n_bytes of name text.  tfidf_dist_last_names_batch reads what the
+ *   communicator kept (no collective, no second search): the names of all
+ *   queries concatenated, query i's entries [name_offsets[i], name_offsets[i+1]).
+ *   A rank that cannot serve at the first collective is skipped for the whole
+ *   batch (tfidf_dist_last_failed); one that fails inside a chunk fails the
+ *   call on every rank together.  A query that does not parse has no names. */
+int tfidf_dist_search_batch_all(tfidf_index *ix, tfidf_comm *c, uint64_t doc_base, const uint8_t *q_utf8,
+                                const uint64_t *q_offsets, uint32_t n_q, uint64_t *doc_ids, float *scores,
+                                uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out);
+int tfidf_dist_shard_search_batch(tfidf_index *ix, tfidf_comm *c, const uint8_t *q_utf8, const uint64_t *q_offsets,
+                                  uint32_t n_q, uint64_t *n_out, uint64_t *n_bytes);
+int tfidf_dist_last_names_batch(const tfidf_comm *c, uint8_t *buf, uint64_t cap, uint64_t *offsets, double *scores,
+                                uint64_t n_cap, uint64_t *name_offsets /* n_q + 1 */, uint64_t *n_out,
+                                uint64_t *n_bytes);
 /* Results of the communicator's last search (local copies, no collective). */
 int tfidf_dist_last_hits(const tfidf_comm *c, uint64_t *doc_ids, float *scores, uint64_t cap, uint64_t *n_out);
 /* Ranks skipped by the last SHARD search (bit r = rank r; 0 = every rank answered). */
@@ -535,7 +572,20 @@ int tfidf_node_search_batch(tfidf_node *n, const uint8_t *q_utf8, const uint64_t
  * and tfidf_last_error() their reasons. */
 int tfidf_node_search_names(tfidf_node *n, const uint8_t *q, uint64_t q_len, uint8_t *buf, uint64_t cap,
                             uint64_t *offsets, double *scores, uint64_t n_cap, uint64_t *n_out, uint64_t *n_bytes);
-/* Shards skipped by the last tfidf_node_search_names (bit g = shard g). */
+/* All-hits batches over the node's shards: tfidf_dist_search_batch_all (GLOBAL
+ * mode) and tfidf_dist_shard_search_batch (SHARD mode) run on every shard at
+ * once; shard 0 delivers.  tfidf_node_search_names_batch searches once and
+ * reports the sizes; tfidf_node_last_names_batch then reads the kept result
+ * (TFIDF_E_BUFFER with the sizes when a buffer is too small). */
+int tfidf_node_search_batch_all(tfidf_node *n, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                                uint64_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                                uint64_t *n_out);
+int tfidf_node_search_names_batch(tfidf_node *n, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                                  uint64_t *n_out, uint64_t *n_bytes);
+int tfidf_node_last_names_batch(const tfidf_node *n, uint8_t *buf, uint64_t cap, uint64_t *offsets, double *scores,
+                                uint64_t n_cap, uint64_t *name_offsets /* n_q + 1 */, uint64_t *n_out,
+                                uint64_t *n_bytes);
+/* Shards skipped by the last tfidf_node_search_names / _names_batch (bit g = shard g). */
 int tfidf_node_last_failed(const tfidf_node *n, uint64_t *shard_mask);
 /* Global doc id -> its document key (Worker.java:235-236, across shards). */
 int tfidf_node_doc_key(tfidf_node *n, uint64_t doc, uint8_t *buf, uint64_t cap, uint64_t *n_out);

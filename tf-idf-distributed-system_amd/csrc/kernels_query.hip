@@ -1722,7 +1722,8 @@ __global__ void k_query_offsets(const uint64_t *P, uint32_t R2, uint32_t n_q, ui
 
 hipError_t launch_hits_order_batch(uint64_t *hits, const uint32_t *hits_n, uint32_t n_q, uint32_t R, uint64_t *P,
                                    uint64_t *tmp0, uint64_t *tmp2, uint32_t *out_doc, float *out_score,
-                                   uint64_t *q_off, uint64_t hits_bound, int grid, hipStream_t s) {
+                                   uint64_t *q_off, uint64_t *keys_out, uint64_t doc_base, uint64_t hits_bound,
+                                   int grid, hipStream_t s) {
   const uint32_t R2 = hits_runs_per_query(R), RT = n_q * R2;
   hipLaunchKernelGGL(k_hits_prefix, dim3(1), dim3(1024), 0, s, hits_n, RT, P);
   hipLaunchKernelGGL(k_query_offsets, dim3(n_q / 256 + 1), dim3(256), 0, s, P, R2, n_q, q_off);
@@ -1731,6 +1732,7 @@ hipError_t launch_hits_order_batch(uint64_t *hits, const uint32_t *hits_n, uint3
   MergeRunsParams mp{};
   mp.P = P;
   mp.R = RT;
+  mp.doc_base = doc_base;
   const uint64_t *src = hits;
   uint64_t *bufs[2] = {tmp0, hits};
   uint32_t L0 = 0;
@@ -1745,9 +1747,9 @@ hipError_t launch_hits_order_batch(uint64_t *hits, const uint32_t *hits_n, uint3
     mp.src = hits;
     mp.gapped = 1;
     mp.final = levels <= 3;
-    mp.dst = tmp0;
-    mp.out_doc = mp.final ? out_doc : nullptr;
-    mp.out_score = mp.final ? out_score : nullptr;
+    mp.dst = mp.final && keys_out ? keys_out : tmp0;
+    mp.out_doc = mp.final && !keys_out ? out_doc : nullptr;
+    mp.out_score = mp.final && !keys_out ? out_score : nullptr;
     hipLaunchKernelGGL(k_merge_group, dim3(RT / kGroupRuns), dim3(kGroupThreads), 2 * kGroupCap * 8, s, mp, tmp2);
     if (mp.final) return hipGetLastError();
     src = tmp0;
@@ -1758,9 +1760,9 @@ hipError_t launch_hits_order_batch(uint64_t *hits, const uint32_t *hits_n, uint3
     mp.level = L;
     mp.gapped = L == 0;
     mp.final = L + 1 == levels;
-    mp.dst = bufs[L & 1];
-    mp.out_doc = mp.final ? out_doc : nullptr;
-    mp.out_score = mp.final ? out_score : nullptr;
+    mp.dst = mp.final && keys_out ? keys_out : bufs[L & 1];
+    mp.out_doc = mp.final && !keys_out ? out_doc : nullptr;
+    mp.out_score = mp.final && !keys_out ? out_score : nullptr;
     hipLaunchKernelGGL(k_merge_runs, dim3(grid), dim3(256), 0, s, mp);
     src = bufs[L & 1];
   }

@@ -2364,6 +2364,83 @@ extern "C" int tfidf_search_batch(tfidf_index *ix, const uint8_t *q_utf8, const 
 // fixes the chunk size (tests).
 constexpr uint64_t kAllHitsBudget = 1ull << 30;
 
+// chunk [a, *z) of a prepared batch's queries [a, end): queries while the
+// chunk's scratch stays in the budget (fixed: TFIDF_ALLHITS_CHUNK); *bound =
+// the chunk's hit bound
+static void all_hits_chunk(const QueryBatch &qb, const Snapshot &S, uint32_t a, uint32_t end, uint32_t fixed,
+                           uint32_t *z_out, uint64_t *bound_out) {
+  const uint32_t R2 = hits_runs_per_query(S.n_blocks);
+  const uint64_t gap_bytes = (uint64_t)R2 * kBlockDocs * 8;
+  const uint32_t max_q = std::max(1u, (1u << 30) / R2);     // run indices stay in 32 bits
+  uint32_t z = a;
+  uint64_t bound = 0, bytes = 0;
+  while (z < end && z - a < max_q) {
+    uint64_t hb = 0;
+    for (uint32_t t = qb.off[z]; t < qb.off[z + 1]; t++)
+      if ((qb.role[t] >> 24) != kRoleNot) hb += qb.ldf[t];
+    hb = std::min<uint64_t>(hb, S.n_docs);
+    if (z > a && (fixed ? z - a >= fixed : bytes + gap_bytes + hb * 24 > kAllHitsBudget)) break;
+    bound += hb;
+    bytes += gap_bytes + hb * 24;
+    z++;
+  }
+  *z_out = z;
+  *bound_out = bound;
+}
+
+static uint32_t all_hits_fixed_chunk() {
+  if (const char *e = knob("TFIDF_ALLHITS_CHUNK")) return (uint32_t)std::max(1, atoi(e));
+  return 0;
+}
+
+// Scores chunk [a, z) of a prepared batch and orders its hits, query-major and
+// contiguous: into X.out_doc / X.out_score, or as merge keys with doc_base into
+// keys_out (room for `bound` keys).  qoff_h: the queries' offsets in the chunk
+// (nc + 1, read back: the stream is idle on return); left empty when no term of
+// the chunk is present.
+static int all_hits_score_chunk(tfidf_index *ix, Snapshot &S, StatsView &V, SearchCtx &X, hipStream_t s,
+                                const QueryBatch &qb, uint32_t a, uint32_t z, uint64_t bound, bool *any,
+                                uint64_t *keys_out, uint64_t doc_base, std::vector<uint64_t> *qoff_h) {
+  qoff_h->clear();
+  const uint32_t nc = z - a, R = S.n_blocks, R2 = hits_runs_per_query(R);
+  const uint32_t t0 = qb.off[a], t1 = qb.off[z];
+  if (t1 == t0) return TFIDF_OK;
+  QueryBatch sub;
+  sub.off.resize(nc + 1);
+  for (uint32_t i = 0; i <= nc; i++) sub.off[i] = qb.off[a + i] - t0;
+  sub.slot.assign(qb.slot.begin() + t0, qb.slot.begin() + t1);
+  sub.w.assign(qb.w.begin() + t0, qb.w.begin() + t1);
+  sub.role.assign(qb.role.begin() + t0, qb.role.begin() + t1);
+  sub.ldf.assign(qb.ldf.begin() + t0, qb.ldf.begin() + t1);
+  sub.meta.assign(qb.meta.begin() + a, qb.meta.begin() + z);
+  for (uint32_t m : sub.meta) sub.ops |= m != 0;
+  X.q_rec_start = !*any;
+  const int rc = run_scoring(ix, S, V, X, s, sub, nc, 0, R2);
+  X.q_rec_start = true;
+  if (rc) return rc;
+  *any = true;
+  const size_t runs = (size_t)nc * R2;
+  HIP_TRY(X.hits_c.reserve(bound * 8 + 8));
+  HIP_TRY(X.hits_s.reserve(bound * 8 + 8));
+  HIP_TRY(X.hits_P.reserve((runs + 1 + nc + 1) * 8));
+  if (!keys_out) {
+    HIP_TRY(X.out_doc.reserve(bound * 4 + 4));
+    HIP_TRY(X.out_score.reserve(bound * 4 + 4));
+  }
+  uint64_t *d_qoff = X.hits_P.as<uint64_t>() + runs + 1;
+  HIP_TRY(launch_hits_order_batch(X.hits.as<uint64_t>(), X.hits_n.as<uint32_t>(), nc, R, X.hits_P.as<uint64_t>(),
+                                  X.hits_c.as<uint64_t>(), X.hits_s.as<uint64_t>(),
+                                  keys_out ? nullptr : X.out_doc.as<uint32_t>(),
+                                  keys_out ? nullptr : X.out_score.as<float>(), d_qoff, keys_out, doc_base, bound,
+                                  ix->num_cus * 4, s));
+  if (X.q_timing) HIP_TRY(hipEventRecord(X.ev[QEV_2], s));
+  qoff_h->resize(nc + 1);
+  HIP_TRY(hipMemcpyAsync(qoff_h->data(), d_qoff, ((size_t)nc + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  X.q_in_pending = false;
+  return TFIDF_OK;
+}
+
 static int batch_all_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *q_utf8, const uint64_t *q_offsets,
                         uint32_t n_q, uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
                         uint64_t *n_out) {
@@ -2377,60 +2454,17 @@ static int batch_all_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_
   DeviceGuard g(ix->cfg.device);
   QueryBatch qb;
   if (int e = prepare_batch(ix, S, V, q_utf8, q_offsets, n_q, &qb)) return e;
-  const uint32_t R = S.n_blocks, R2 = hits_runs_per_query(R);
-  const uint64_t gap_bytes = (uint64_t)R2 * kBlockDocs * 8;
-  uint32_t fixed = 0;
-  if (const char *e = knob("TFIDF_ALLHITS_CHUNK")) fixed = (uint32_t)std::max(1, atoi(e));
-  const uint32_t max_q = std::max(1u, (1u << 30) / R2);     // run indices stay in 32 bits
+  const uint32_t fixed = all_hits_fixed_chunk();
   std::vector<uint64_t> qoff_h;
   uint64_t total = 0;
   bool any = false, fits = true;
   for (uint32_t a = 0; a < n_q;) {
-    // chunk [a, z): queries while the chunk's scratch stays in the budget
     uint32_t z = a;
-    uint64_t bound = 0, bytes = 0;
-    while (z < n_q && z - a < max_q) {
-      uint64_t hb = 0;
-      for (uint32_t t = qb.off[z]; t < qb.off[z + 1]; t++)
-        if ((qb.role[t] >> 24) != kRoleNot) hb += qb.ldf[t];
-      hb = std::min<uint64_t>(hb, S.n_docs);
-      if (z > a && (fixed ? z - a >= fixed : bytes + gap_bytes + hb * 24 > kAllHitsBudget)) break;
-      bound += hb;
-      bytes += gap_bytes + hb * 24;
-      z++;
-    }
+    uint64_t bound = 0;
+    all_hits_chunk(qb, S, a, n_q, fixed, &z, &bound);
     const uint32_t nc = z - a;
-    const uint32_t t0 = qb.off[a], t1 = qb.off[z];
-    if (t1 > t0) {
-      QueryBatch sub;
-      sub.off.resize(nc + 1);
-      for (uint32_t i = 0; i <= nc; i++) sub.off[i] = qb.off[a + i] - t0;
-      sub.slot.assign(qb.slot.begin() + t0, qb.slot.begin() + t1);
-      sub.w.assign(qb.w.begin() + t0, qb.w.begin() + t1);
-      sub.role.assign(qb.role.begin() + t0, qb.role.begin() + t1);
-      sub.ldf.assign(qb.ldf.begin() + t0, qb.ldf.begin() + t1);
-      sub.meta.assign(qb.meta.begin() + a, qb.meta.begin() + z);
-      for (uint32_t m : sub.meta) sub.ops |= m != 0;
-      X.q_rec_start = !any;
-      const int rc = run_scoring(ix, S, V, X, s, sub, nc, 0, R2);
-      X.q_rec_start = true;
-      if (rc) return rc;
-      any = true;
-      const size_t runs = (size_t)nc * R2;
-      HIP_TRY(X.hits_c.reserve(bound * 8 + 8));
-      HIP_TRY(X.hits_s.reserve(bound * 8 + 8));
-      HIP_TRY(X.hits_P.reserve((runs + 1 + nc + 1) * 8));
-      HIP_TRY(X.out_doc.reserve(bound * 4 + 4));
-      HIP_TRY(X.out_score.reserve(bound * 4 + 4));
-      uint64_t *d_qoff = X.hits_P.as<uint64_t>() + runs + 1;
-      HIP_TRY(launch_hits_order_batch(X.hits.as<uint64_t>(), X.hits_n.as<uint32_t>(), nc, R, X.hits_P.as<uint64_t>(),
-                                      X.hits_c.as<uint64_t>(), X.hits_s.as<uint64_t>(), X.out_doc.as<uint32_t>(),
-                                      X.out_score.as<float>(), d_qoff, bound, ix->num_cus * 4, s));
-      if (X.q_timing) HIP_TRY(hipEventRecord(X.ev[QEV_2], s));
-      qoff_h.resize(nc + 1);
-      HIP_TRY(hipMemcpyAsync(qoff_h.data(), d_qoff, ((size_t)nc + 1) * 8, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      X.q_in_pending = false;
+    if (int rc = all_hits_score_chunk(ix, S, V, X, s, qb, a, z, bound, &any, nullptr, 0, &qoff_h)) return rc;
+    if (!qoff_h.empty()) {
       const uint64_t H = qoff_h[nc];
       for (uint32_t i = 1; i <= nc; i++) hit_offsets[a + i] = total + qoff_h[i];
       fits = fits && total + H <= cap;
@@ -2726,6 +2760,78 @@ int tfidf::reader_batch_keys_device(tfidf_reader *rd, const uint8_t *q_utf8, con
 int tfidf::reader_all_keys_device(tfidf_reader *rd, const uint8_t *q, uint64_t q_len, uint64_t doc_base, void *d_keys,
                                   uint64_t cap, uint64_t *n_out) {
   return all_keys_on(rd->ix, *rd->S, *rd->V, q, q_len, doc_base, d_keys, cap, n_out);
+}
+
+// A batch prepared once on a reader's snapshot (parse, analysis, dictionary
+// lookups, weights), for the node-level all-hits batches: they score it in
+// node chunks, each through reader_batch_all_keys_device.
+struct tfidf::PreparedAllHits {
+  QueryBatch qb;
+};
+
+int tfidf::reader_prepare_all_hits(tfidf_reader *rd, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                                   PreparedAllHits **out, uint64_t *bounds) {
+  if (!rd || !out || (n_q && (!q_offsets || !bounds))) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  *out = nullptr;
+  std::unique_ptr<PreparedAllHits> pb(new PreparedAllHits());
+  Snapshot &S = *rd->S;
+  if (n_q && S.n_docs) {
+    if (int e = prepare_batch(rd->ix, S, *rd->V, q_utf8, q_offsets, n_q, &pb->qb)) return e;
+  } else {
+    pb->qb.off.assign((size_t)n_q + 1, 0);
+    pb->qb.meta.assign(n_q, 0);
+  }
+  const QueryBatch &qb = pb->qb;
+  for (uint32_t i = 0; i < n_q; i++) {
+    uint64_t hb = 0;
+    for (uint32_t t = qb.off[i]; t < qb.off[i + 1]; t++)
+      if ((qb.role[t] >> 24) != kRoleNot) hb += qb.ldf[t];
+    bounds[i] = std::min<uint64_t>(hb, S.n_docs);
+  }
+  *out = pb.release();
+  return TFIDF_OK;
+}
+
+void tfidf::free_prepared_all_hits(PreparedAllHits *pb) { delete pb; }
+
+int tfidf::reader_batch_all_keys_device(tfidf_reader *rd, const PreparedAllHits *pb, uint32_t a, uint32_t z,
+                                        uint64_t doc_base, void *d_keys, uint64_t cap, uint64_t *counts,
+                                        uint64_t *n_out) {
+  if (!rd || !pb || !n_out || a > z || (size_t)z + 1 > pb->qb.off.size() || (z > a && !counts))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument or query range out of the batch");
+  *n_out = 0;
+  for (uint32_t i = 0; i < z - a; i++) counts[i] = 0;
+  tfidf_index *ix = rd->ix;
+  Snapshot &S = *rd->S;
+  if (z == a || S.n_docs == 0) return TFIDF_OK;
+  CtxLease lease(ix);
+  if (lease.rc) return lease.rc;
+  SearchCtx &X = *lease.c;
+  const hipStream_t s = lease.stream();
+  DeviceGuard g(ix->cfg.device);
+  const uint32_t fixed = all_hits_fixed_chunk();
+  std::vector<uint64_t> qoff_h;
+  uint64_t total = 0;
+  bool any = false;
+  for (uint32_t la = a; la < z;) {
+    uint32_t lz = la;
+    uint64_t bound = 0;
+    all_hits_chunk(pb->qb, S, la, z, fixed, &lz, &bound);
+    if (total + bound > cap || (bound && !d_keys))
+      return fail(TFIDF_E_BUFFER, "the key buffer needs the range's hit bounds (%llu entries)",
+                  (unsigned long long)(total + bound));
+    if (int rc = all_hits_score_chunk(ix, S, *rd->V, X, s, pb->qb, la, lz, bound, &any,
+                                      static_cast<uint64_t *>(d_keys) + total, doc_base, &qoff_h))
+      return rc;
+    if (!qoff_h.empty()) {
+      for (uint32_t i = 0; i < lz - la; i++) counts[la - a + i] = qoff_h[i + 1] - qoff_h[i];
+      total += qoff_h[lz - la];                    // the local chunks append
+    }
+    la = lz;
+  }
+  *n_out = total;
+  set_last_ms(ix, any ? qev_ms(X, QEV_0, QEV_1) : 0.0f, any ? qev_ms(X, QEV_0, QEV_2) : 0.0f);
+  return TFIDF_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -25,6 +25,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <functional>
 #include <memory>
@@ -323,6 +324,11 @@ struct tfidf_comm {
   std::vector<uint32_t> last_name;
   std::vector<double> last_sum;
   uint64_t last_name_bytes = 0;
+  // last SHARD batch (tfidf_dist_last_names_batch): every query's names, concatenated
+  std::vector<uint32_t> batch_name;
+  std::vector<double> batch_sum;
+  std::vector<uint64_t> batch_qoff{0};    // [n_q + 1] query i's entries in batch_name / batch_sum
+  uint64_t batch_name_bytes = 0;
 };
 
 namespace {
@@ -457,6 +463,101 @@ __global__ void k_seg_sums(const uint32_t *k, const uint32_t *v, const uint32_t 
   for (uint64_t j = i + 1; j < n && k[j] == k[i]; j++) s += (double)__uint_as_float(v[j]);
   out_name[pos[i]] = k[i];
   out_sum[pos[i]] = s;
+}
+
+// All-hits batches: k_merge_lists from a fixed stride to CSR segments.  The
+// gathered keys are [world][maxn]; rank r's row holds its chunk's hits
+// query-major, query q's run at roff[r][q] .. roff[r][q + 1] (roff: [world][nc +
+// 1]), each run sorted descending.  One thread per candidate key: its query by
+// binary search in its rank's offsets, its output rank = its index in its own
+// run + the keys above it in every other rank's run of the same query (binary
+// search; keys are distinct: the doc ranges were checked disjoint).  Written
+// decoded at out_off[q] + rank: global doc id (u64) and score (f32).  A wave's
+// lanes hold consecutive keys of one run, so their searches in another run
+// converge on neighbouring lines.
+__global__ void __launch_bounds__(256) k_merge_segments(const uint64_t *keys, uint64_t maxn, uint32_t world,
+                                                        uint32_t nc, const uint64_t *roff, const uint64_t *out_off,
+                                                        uint64_t *out_doc, float *out_score) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= maxn * world) return;
+  const uint32_t r = (uint32_t)(t / maxn);
+  const uint64_t i = t - (uint64_t)r * maxn;
+  const uint64_t *mo = roff + (uint64_t)r * (nc + 1);
+  if (i >= mo[nc]) return;                        // the row's padding
+  uint32_t lo = 0, hi = nc - 1;                   // last q with mo[q] <= i: mo[q] <= i < mo[q + 1]
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (mo[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  const uint32_t q = lo;
+  const uint64_t x = keys[t];
+  uint64_t rank = i - mo[q];
+  for (uint32_t o = 0; o < world; o++) {
+    if (o == r) continue;
+    const uint64_t *oo = roff + (uint64_t)o * (nc + 1);
+    const uint64_t *l = keys + (uint64_t)o * maxn + oo[q];
+    uint64_t a = 0, z = oo[q + 1] - oo[q];        // first index whose key is < x (keys above x: [0, a))
+    while (a < z) {
+      const uint64_t m = (a + z) >> 1;
+      if (l[m] > x) a = m + 1; else z = m;
+    }
+    rank += a;
+  }
+  const uint64_t at = out_off[q] + rank;
+  out_doc[at] = (uint64_t)(~(uint32_t)x);
+  out_score[at] = __uint_as_float((uint32_t)(x >> 32));
+}
+
+// SHARD batches: gathered [world][maxn] (name id << 32 | score bits) records, rank
+// r's row query-major (roff as in k_merge_segments) -> key (query in chunk << 32 |
+// name id) / value (score bits) arrays in rank order
+__global__ void k_split_records_q(const uint64_t *all, uint64_t maxn, uint32_t world, uint32_t nc,
+                                  const uint64_t *roff, const uint64_t *row_base, uint64_t *kk, uint32_t *vv) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= maxn * world) return;
+  const uint32_t r = (uint32_t)(t / maxn);
+  const uint64_t i = t - (uint64_t)r * maxn;
+  const uint64_t *mo = roff + (uint64_t)r * (nc + 1);
+  if (i >= mo[nc]) return;
+  uint32_t lo = 0, hi = nc - 1;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (mo[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  const uint64_t x = all[t];
+  kk[row_base[r] + i] = ((uint64_t)lo << 32) | (x >> 32);
+  vv[row_base[r] + i] = (uint32_t)x;
+}
+
+__global__ void k_seg_heads64(const uint64_t *k, uint64_t n, uint32_t *head) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) head[i] = (i == 0 || k[i] != k[i - 1]) ? 1u : 0u;
+}
+
+// k_seg_sums on (query, name) keys: per query and name, the double sum in rank
+// order; the distinct keys (for the per-query bounds) and their name ids
+__global__ void k_seg_sums64(const uint64_t *k, const uint32_t *v, const uint32_t *pos, uint64_t n, uint64_t *out_key,
+                             uint32_t *out_name, double *out_sum) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || (i > 0 && k[i] == k[i - 1])) return;
+  double s = (double)__uint_as_float(v[i]);
+  for (uint64_t j = i + 1; j < n && k[j] == k[i]; j++) s += (double)__uint_as_float(v[j]);
+  out_key[pos[i]] = k[i];
+  out_name[pos[i]] = (uint32_t)k[i];
+  out_sum[pos[i]] = s;
+}
+
+// per-query counts from the sorted distinct keys: bounds[q] = the first entry
+// whose query is >= q (q = 0 .. nc), so query q's names are [bounds[q], bounds[q + 1])
+__global__ void k_query_bounds(const uint64_t *keys, uint64_t n, uint32_t nc, uint64_t *bounds) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q > nc) return;
+  uint64_t a = 0, z = n;
+  while (a < z) {
+    const uint64_t m = (a + z) >> 1;
+    if ((keys[m] >> 32) < q) a = m + 1; else z = m;
+  }
+  bounds[q] = a;
 }
 
 inline unsigned grid_of(uint64_t n, unsigned b = 256) { return (unsigned)((n + b - 1) / b); }
@@ -1141,6 +1242,363 @@ extern "C" int tfidf_dist_shard_search(tfidf_index *ix, tfidf_comm *c, const uin
   return shard_partial(c, lrc, lmsg);
 }
 
+// ---------------------------------------------------------------------------
+// all-hits batches (Worker.java:230 for a batch of requests, over the ranks)
+
+namespace {
+
+// Node chunks of an all-hits batch.  The first collective gathers every rank's
+// per-query hit bound (the sum of the query's scoring terms' df, at most the
+// shard's document count), so every rank derives the same chunk boundaries
+// from the gathered bounds, `world` and this constant, never from a local
+// value.  With B_r = rank r's bounds summed over the chunk's queries, a chunk
+// takes queries while
+//   world * max_r(B_r) * 8     the gathered buffer [world][longest row]
+// + sum_r(B_r) * 12            the merged output (u64 doc + f32 score per hit;
+//                              SHARD mode's sort buffers are charged the same)
+// + max_r(B_r) * 8             the local key buffer (also the padded send row)
+// stays within kDistAllHitsBudget, and while world * max_r(B_r) < 2^31 records.
+// A chunk always holds at least one query.  1 GiB, as kAllHitsBudget bounds
+// the local chunks inside it.  TFIDF_DIST_ALLHITS_CHUNK=<queries> fixes the
+// chunk size (tests).
+constexpr uint64_t kDistAllHitsBudget = 1ull << 30;
+
+struct PreparedHolder {
+  PreparedAllHits *p = nullptr;
+  PreparedHolder() = default;
+  PreparedHolder(const PreparedHolder &) = delete;
+  PreparedHolder &operator=(const PreparedHolder &) = delete;
+  ~PreparedHolder() { free_prepared_all_hits(p); }
+};
+
+struct BatchAll {
+  tfidf_index *ix;
+  tfidf_comm *c;
+  hipStream_t s;
+  uint32_t n_q;
+  size_t stride;                      // words per rank in rows: kHdr + n_q
+  Pinned pin;
+  PreparedHolder pb;
+  std::vector<uint64_t> rows;         // [world][kHdr + n_q]: every rank's status header and hit bounds
+  int lrc = TFIDF_OK;                 // this rank's status at the first collective
+  std::string lmsg;
+  uint32_t fixed = 0;
+  std::vector<uint64_t> B;            // [world] the current chunk's bounds per rank
+  uint64_t maxB = 0, sumB = 0;
+
+  // first collective: {rc, doc_base, n_docs, 0} + bounds; the verdict of every rank alike
+  int first(uint64_t doc_base, bool global, const uint8_t *q_utf8, const uint64_t *q_offsets) {
+    stride = kHdr + n_q;
+    std::vector<uint64_t> mine(stride, 0);
+    lrc = local_search_status(pin, ix, c, doc_base, global);
+    if (!lrc) lrc = reader_prepare_all_hits(pin.rd, q_utf8, q_offsets, n_q, &pb.p, mine.data() + kHdr);
+    lmsg = lrc ? tfidf_last_error() : "";
+    if (lrc) std::fill(mine.begin() + kHdr, mine.end(), 0);      // a failing rank sends zeros
+    mine[0] = (uint64_t)lrc;
+    mine[1] = doc_base;
+    mine[2] = lrc ? 0 : pin.nd;
+    if (int rc = gather_rows(c, s, mine, &rows)) return rc;
+    if (const char *e = knob("TFIDF_DIST_ALLHITS_CHUNK")) fixed = (uint32_t)std::max(1, atoi(e));
+    B.assign(c->world, 0);
+    return status_verdict(c, rows.data(), stride, lrc, lmsg, global, &c->last_failed);
+  }
+
+  // chunk [a, *z) from the gathered bounds (B, maxB, sumB: its per-rank bounds)
+  int chunk(uint32_t a, uint32_t *z_out) {
+    const int ws = c->world;
+    std::fill(B.begin(), B.end(), 0);
+    maxB = sumB = 0;
+    uint32_t z = a;
+    while (z < n_q) {
+      uint64_t mx = 0, sum = 0;
+      for (int r = 0; r < ws; r++) {
+        const uint64_t b = B[r] + rows[(size_t)r * stride + kHdr + z];
+        mx = std::max(mx, b);
+        sum += b;
+      }
+      const bool records_ok = (uint64_t)ws * mx < (1ull << 31);
+      if (z > a && (!records_ok || (fixed ? z - a >= fixed
+                                          : (uint64_t)ws * mx * 8 + sum * 12 + mx * 8 > kDistAllHitsBudget)))
+        break;
+      if (!records_ok) return errf(TFIDF_E_CAPACITY, "query %u alone may have 2^31 hit records over the ranks", z);
+      for (int r = 0; r < ws; r++) B[r] += rows[(size_t)r * stride + kHdr + z];
+      maxB = mx;
+      sumB = sum;
+      z++;
+    }
+    *z_out = z;
+    return TFIDF_OK;
+  }
+
+  // The chunk's count row: {rc} + this rank's per-query counts, gathered.  A
+  // local failure since the first collective rides in it: every rank returns it
+  // together here, before the data collective.  -> crow [world][1 + nc]
+  int counts(uint32_t nc, int crc, const std::string &cmsg, const std::vector<uint64_t> &cnt,
+             std::vector<uint64_t> *crow) {
+    std::vector<uint64_t> mine(1 + (size_t)nc, 0);
+    mine[0] = (uint64_t)crc;
+    if (!crc) std::copy(cnt.begin(), cnt.begin() + nc, mine.begin() + 1);
+    if (int rc = gather_rows(c, s, mine, crow)) return rc;
+    for (int r = 0; r < c->world; r++)
+      if ((*crow)[(size_t)r * (1 + nc)]) {
+        if (r == c->rank) return set_error(crc, cmsg.c_str());
+        return errf((int)(*crow)[(size_t)r * (1 + nc)], "rank %d failed inside the batch", r);
+      }
+    return TFIDF_OK;
+  }
+};
+
+// offsets tables of a chunk from its count rows: roff [world][nc + 1] (each
+// rank's per-query run starts within its row), per-rank totals, the longest row
+void chunk_tables(const std::vector<uint64_t> &crow, int ws, uint32_t nc, std::vector<uint64_t> *roff,
+                  std::vector<uint64_t> *row_n, uint64_t *maxn) {
+  roff->assign((size_t)ws * (nc + 1), 0);
+  row_n->assign(ws, 0);
+  *maxn = 0;
+  for (int r = 0; r < ws; r++) {
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < nc; i++) {
+      (*roff)[(size_t)r * (nc + 1) + i] = at;
+      at += crow[(size_t)r * (1 + nc) + 1 + i];
+    }
+    (*roff)[(size_t)r * (nc + 1) + nc] = at;
+    (*row_n)[r] = at;
+    *maxn = std::max(*maxn, at);
+  }
+}
+
+}  // namespace
+
+extern "C" int tfidf_dist_search_batch_all(tfidf_index *ix, tfidf_comm *c, uint64_t doc_base, const uint8_t *q_utf8,
+                                           const uint64_t *q_offsets, uint32_t n_q, uint64_t *doc_ids, float *scores,
+                                           uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out) {
+  if (!ix || !c || !hit_offsets || !n_out || (n_q && !q_offsets) || (cap && (!doc_ids || !scores)))
+    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  for (uint32_t i = 0; i <= n_q; i++) hit_offsets[i] = 0;
+  *n_out = 0;
+  if (n_q == 0) return TFIDF_OK;                       // every rank knows: no collective
+  DevGuard g(index_device(ix));
+  BatchAll b{ix, c, index_stream(ix), n_q};
+  hipStream_t s = b.s;
+  const int ws = c->world;
+  if (int rc = b.first(doc_base, true, q_utf8, q_offsets)) return rc;
+  std::vector<uint64_t> cnt, crow, roff, row_n, tab;
+  uint64_t total = 0;
+  bool fits = true;
+  for (uint32_t a = 0; a < n_q;) {
+    uint32_t z = a;
+    if (int rc = b.chunk(a, &z)) return rc;
+    const uint32_t nc = z - a;
+    // every allocation of the chunk, sized by the bounds, before the count row
+    const bool deliver = cap > 0 && fits;
+    int crc = TFIDF_OK;
+    if (b.sumB) {
+      bool ok = c->d_keys.reserve(b.maxB * 8) == hipSuccess && c->d_all.reserve((size_t)ws * b.maxB * 8) == hipSuccess;
+      if (ok && deliver)
+        ok = c->d_out.reserve(b.sumB * 8) == hipSuccess && c->d_tmp.reserve(b.sumB * 4) == hipSuccess &&
+             c->d_seg.reserve(((size_t)ws + 1) * (nc + 1) * 8) == hipSuccess;
+      if (!ok) crc = errf(TFIDF_E_OOM, "all-hits batch: out of device memory");
+    }
+    cnt.assign(nc, 0);
+    uint64_t h = 0;
+    if (!crc && b.sumB)
+      crc = reader_batch_all_keys_device(b.pin.rd, b.pb.p, a, z, doc_base, c->d_keys.p, b.maxB, cnt.data(), &h);
+    const std::string cmsg = crc ? tfidf_last_error() : "";
+    if (int rc = b.counts(nc, crc, cmsg, cnt, &crow)) return rc;
+    uint64_t maxn = 0;
+    chunk_tables(crow, ws, nc, &roff, &row_n, &maxn);
+    uint64_t H = 0;
+    tab.assign(roff.begin(), roff.end());               // roff, then the chunk's output offsets
+    for (uint32_t i = 0; i <= nc; i++) {
+      tab.push_back(H);
+      hit_offsets[a + i] = total + H;
+      if (i < nc)
+        for (int r = 0; r < ws; r++) H += crow[(size_t)r * (1 + nc) + 1 + i];
+    }
+    fits = fits && total + H <= cap;
+    if (maxn) {
+      // the key rows, padded to the longest rank's (like gather_var)
+      if (maxn > h) DHIP(hipMemsetAsync(c->d_keys.as<uint64_t>() + h, 0, (maxn - h) * 8, s));
+      if (int rc = coll_gather(c, s, c->d_keys.p, c->d_all.p, maxn * 8, true)) return rc;
+      if (cap > 0 && fits) {
+        uint64_t *d_tab = c->d_seg.as<uint64_t>();
+        DHIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_merge_segments, dim3(grid_of(maxn * ws)), dim3(256), 0, s, c->d_all.as<uint64_t>(), maxn,
+                           (uint32_t)ws, nc, d_tab, d_tab + (size_t)ws * (nc + 1), c->d_out.as<uint64_t>(),
+                           c->d_tmp.as<float>());
+        DHIP(hipGetLastError());
+        // the chunk's (doc, score) arrays straight into the caller's, at the running offset
+        DHIP(hipMemcpyAsync(doc_ids + total, c->d_out.p, H * 8, hipMemcpyDeviceToHost, s));
+        DHIP(hipMemcpyAsync(scores + total, c->d_tmp.p, H * 4, hipMemcpyDeviceToHost, s));
+      }
+      DHIP(hipStreamSynchronize(s));                    // the chunk's buffers are free again
+    }
+    total += H;
+    a = z;
+  }
+  hit_offsets[n_q] = total;
+  *n_out = total;
+  if (!fits) return errf(TFIDF_E_BUFFER, "need %llu result slots", (unsigned long long)total);
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_dist_shard_search_batch(tfidf_index *ix, tfidf_comm *c, const uint8_t *q_utf8,
+                                             const uint64_t *q_offsets, uint32_t n_q, uint64_t *n_out,
+                                             uint64_t *n_bytes) {
+  if (!ix || !c || !n_out || (n_q && !q_offsets)) return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  *n_out = 0;
+  if (n_bytes) *n_bytes = 0;
+  c->batch_name.clear();
+  c->batch_sum.clear();
+  c->batch_qoff.assign((size_t)n_q + 1, 0);
+  c->batch_name_bytes = 0;
+  c->last_failed = 0;
+  if (n_q == 0) return TFIDF_OK;
+  DevGuard g(index_device(ix));
+  BatchAll b{ix, c, index_stream(ix), n_q};
+  hipStream_t s = b.s;
+  const int ws = c->world;
+  // a rank that cannot serve here is skipped for the whole batch (a failed
+  // worker, Leader.java:67-69): it sends zero bounds, then zero counts
+  // profiling only (TFIDF_HOST_TIMING): wall time of the call's stages on this rank
+  using clk = std::chrono::steady_clock;
+  const bool timing = knob("TFIDF_HOST_TIMING") != nullptr;
+  double t_stage[5] = {0, 0, 0, 0, 0};          // first collective, local search, collectives, device merge, read-back
+  clk::time_point t_at = clk::now();
+  auto lap = [&](int stage) {
+    if (!timing) return;
+    const clk::time_point t = clk::now();
+    t_stage[stage] += std::chrono::duration<double, std::milli>(t - t_at).count();
+    t_at = t;
+  };
+  if (int rc = b.first(0, false, q_utf8, q_offsets)) return rc;
+  lap(0);
+  if (c->last_failed == (ws >= 64 ? ~0ull : (1ull << ws) - 1)) return shard_partial(c, b.lrc, b.lmsg);
+  std::vector<uint64_t> cnt, crow, roff, row_n, tab, qb;
+  for (uint32_t a = 0; a < n_q;) {
+    uint32_t z = a;
+    if (int rc = b.chunk(a, &z)) return rc;
+    const uint32_t nc = z - a;
+    uint32_t qbits = 1;
+    while ((1ull << qbits) < nc) qbits++;
+    const uint64_t N = b.sumB;                          // at most this many records in the chunk
+    int crc = TFIDF_OK;
+    size_t tcap = 0;
+    if (N) {
+      size_t t1 = 0, t2 = 0;
+      hipcub::DeviceRadixSort::SortPairs(nullptr, t1, (const uint64_t *)nullptr, (uint64_t *)nullptr,
+                                         (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)N, 0, (int)(32 + qbits), s);
+      hipcub::DeviceScan::ExclusiveSum(nullptr, t2, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)N, s);
+      tcap = (std::max(t1, t2) + 255) & ~(size_t)255;
+      const bool ok = c->d_keys.reserve(b.maxB * 8) == hipSuccess && c->d_out.reserve(b.maxB * 8) == hipSuccess &&
+                      c->d_all.reserve((size_t)ws * b.maxB * 8) == hipSuccess &&
+                      c->d_srt_k.reserve(N * 16) == hipSuccess && c->d_srt_v.reserve(N * 8) == hipSuccess &&
+                      c->d_seg.reserve(N * 20) == hipSuccess && c->d_tmp.reserve(tcap + N * 8) == hipSuccess &&
+                      c->d_got.reserve((((size_t)ws + 2) * (nc + 1) + ws) * 8) == hipSuccess;
+      if (!ok) crc = errf(TFIDF_E_OOM, "all-hits batch: out of device memory");
+    }
+    cnt.assign(nc, 0);
+    uint64_t h = 0;
+    if (!crc && !b.lrc && b.B[c->rank])
+      crc = reader_batch_all_keys_device(b.pin.rd, b.pb.p, a, z, 0, c->d_keys.p, b.maxB, cnt.data(), &h);   // local ids
+    if (!crc && h) {                                    // (name id << 32 | score bits) records -> the send row
+      hipLaunchKernelGGL(k_name_records, dim3(grid_of(h)), dim3(256), 0, s, c->d_keys.as<uint64_t>(), h,
+                         c->d_name_of_doc.as<uint32_t>(), c->d_out.as<uint64_t>());
+      if (hipGetLastError() != hipSuccess) crc = errf(TFIDF_E_HIP, "name records: launch failed");
+    }
+    const std::string cmsg = crc ? tfidf_last_error() : "";
+    lap(1);
+    if (int rc = b.counts(nc, crc, cmsg, cnt, &crow)) return rc;
+    uint64_t maxn = 0, n = 0;
+    chunk_tables(crow, ws, nc, &roff, &row_n, &maxn);
+    if (maxn) {
+      if (maxn > h) DHIP(hipMemsetAsync(c->d_out.as<uint64_t>() + h, 0, (maxn - h) * 8, s));
+      if (int rc = coll_gather(c, s, c->d_out.p, c->d_all.p, maxn * 8, true)) return rc;
+      lap(2);
+      tab.assign(roff.begin(), roff.end());             // roff, then every rank's first record in rank order
+      for (int r = 0; r < ws; r++) { tab.push_back(n); n += row_n[r]; }
+      uint64_t *d_tab = c->d_got.as<uint64_t>();
+      DHIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, s));
+      // rank-order (query, name) / score pairs -> stable sort -> per (query, name) sums in rank order
+      uint64_t *k0 = c->d_srt_k.as<uint64_t>(), *k1 = k0 + n;
+      uint32_t *v0 = c->d_srt_v.as<uint32_t>(), *v1 = v0 + n;
+      uint64_t *out_key = c->d_seg.as<uint64_t>();
+      uint32_t *head = reinterpret_cast<uint32_t *>(out_key + n), *pos = head + n, *out_name = pos + n;
+      double *out_sum = reinterpret_cast<double *>(c->d_tmp.as<uint8_t>() + tcap);
+      uint64_t *d_qb = d_tab + tab.size();
+      hipLaunchKernelGGL(k_split_records_q, dim3(grid_of(maxn * ws)), dim3(256), 0, s, c->d_all.as<uint64_t>(), maxn,
+                         (uint32_t)ws, nc, d_tab, d_tab + (size_t)ws * (nc + 1), k0, v0);
+      DHIP(hipGetLastError());
+      size_t tb = 0;
+      DHIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, k0, k1, v0, v1, (int)n, 0, (int)(32 + qbits), s));
+      if (tb > tcap) return errf(TFIDF_E_HIP, "name sort: temporary storage beyond the chunk's reservation");
+      tb = tcap;
+      DHIP(hipcub::DeviceRadixSort::SortPairs(c->d_tmp.p, tb, k0, k1, v0, v1, (int)n, 0, (int)(32 + qbits), s));
+      hipLaunchKernelGGL(k_seg_heads64, dim3(grid_of(n)), dim3(256), 0, s, k1, n, head);
+      tb = tcap;
+      DHIP(hipcub::DeviceScan::ExclusiveSum(c->d_tmp.p, tb, head, pos, (int)n, s));
+      hipLaunchKernelGGL(k_seg_sums64, dim3(grid_of(n)), dim3(256), 0, s, k1, v1, pos, n, out_key, out_name, out_sum);
+      DHIP(hipGetLastError());
+      uint32_t last[2] = {0, 0};
+      DHIP(hipMemcpyAsync(&last[0], pos + n - 1, 4, hipMemcpyDeviceToHost, s));
+      DHIP(hipMemcpyAsync(&last[1], head + n - 1, 4, hipMemcpyDeviceToHost, s));
+      DHIP(hipStreamSynchronize(s));
+      const uint64_t nu = (uint64_t)last[0] + last[1];
+      lap(3);
+      // name ids and sums straight into the kept result; the per-query counts from the device
+      hipLaunchKernelGGL(k_query_bounds, dim3(grid_of((uint64_t)nc + 1)), dim3(256), 0, s, out_key, nu, nc, d_qb);
+      DHIP(hipGetLastError());
+      const size_t at = c->batch_name.size();
+      c->batch_name.resize(at + nu);
+      c->batch_sum.resize(at + nu);
+      qb.resize((size_t)nc + 1);
+      DHIP(hipMemcpyAsync(c->batch_name.data() + at, out_name, nu * 4, hipMemcpyDeviceToHost, s));
+      DHIP(hipMemcpyAsync(c->batch_sum.data() + at, out_sum, nu * 8, hipMemcpyDeviceToHost, s));
+      DHIP(hipMemcpyAsync(qb.data(), d_qb, ((size_t)nc + 1) * 8, hipMemcpyDeviceToHost, s));
+      DHIP(hipStreamSynchronize(s));
+      for (uint32_t i = 0; i < nc; i++) c->batch_qoff[a + i + 1] = qb[i + 1] - qb[i];
+      for (uint64_t i = 0; i < nu; i++) {
+        const uint32_t id = c->batch_name[at + i];
+        c->batch_name_bytes += c->name_off[id + 1] - c->name_off[id];
+      }
+      lap(4);
+    }
+    a = z;
+  }
+  for (uint32_t i = 0; i < n_q; i++) c->batch_qoff[i + 1] += c->batch_qoff[i];
+  *n_out = c->batch_name.size();
+  if (n_bytes) *n_bytes = c->batch_name_bytes;
+  if (timing)
+    fprintf(stderr, "shard batch %u, rank %d: first collective %.3f  local search %.3f  collectives %.3f  "
+            "device merge %.3f  read-back %.3f ms\n", n_q, c->rank, t_stage[0], t_stage[1], t_stage[2], t_stage[3],
+            t_stage[4]);
+  return shard_partial(c, b.lrc, b.lmsg);
+}
+
+extern "C" int tfidf_dist_last_names_batch(const tfidf_comm *c, uint8_t *buf, uint64_t cap, uint64_t *offsets,
+                                           double *scores, uint64_t n_cap, uint64_t *name_offsets, uint64_t *n_out,
+                                           uint64_t *n_bytes) {
+  if (!c || !name_offsets || !n_out || !n_bytes) return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t n = c->batch_name.size();
+  *n_out = n;
+  *n_bytes = c->batch_name_bytes;
+  for (size_t i = 0; i < c->batch_qoff.size(); i++) name_offsets[i] = c->batch_qoff[i];
+  if (n > n_cap || c->batch_name_bytes > cap || (n && (!offsets || !scores)) || (c->batch_name_bytes && !buf))
+    return errf(TFIDF_E_BUFFER, "%llu names of %llu bytes", (unsigned long long)n,
+                (unsigned long long)c->batch_name_bytes);
+  uint64_t p = 0;
+  if (offsets) offsets[0] = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint32_t id = c->batch_name[i];
+    const uint64_t a = c->name_off[id], z = c->name_off[id + 1];
+    memcpy(buf + p, c->names.data() + a, z - a);
+    p += z - a;
+    offsets[i + 1] = p;
+    scores[i] = c->batch_sum[i];
+  }
+  return TFIDF_OK;
+}
+
 extern "C" int tfidf_dist_last_hits(const tfidf_comm *c, uint64_t *doc_ids, float *scores, uint64_t cap,
                                     uint64_t *n_out) {
   if (!c || !n_out) return errf(TFIDF_E_INVALID_ARG, "NULL argument");
@@ -1163,7 +1621,7 @@ extern "C" int tfidf_dist_last_names(const tfidf_comm *c, uint8_t *buf, uint64_t
     return errf(TFIDF_E_BUFFER, "%llu names of %llu bytes", (unsigned long long)n,
                 (unsigned long long)c->last_name_bytes);
   uint64_t p = 0;
-  offsets[0] = 0;
+  if (offsets) offsets[0] = 0;                     // (no names: the size query passes no arrays)
   for (uint64_t i = 0; i < n; i++) {
     const uint32_t id = c->last_name[i];
     const uint64_t a = c->name_off[id], z = c->name_off[id + 1];
@@ -1461,6 +1919,74 @@ extern "C" int tfidf_node_search_names(tfidf_node *n, const uint8_t *q, uint64_t
     set_error(TFIDF_OK, m.c_str());
   }
   return rc;
+}
+
+extern "C" int tfidf_node_search_batch_all(tfidf_node *n, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                                           uint64_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                                           uint64_t *n_out) {
+  if (!n || !hit_offsets || !n_out || (n_q && !q_offsets) || (cap && (!doc_ids || !scores)))
+    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lk(n->mu);
+  for (uint32_t i = 0; i <= n_q; i++) hit_offsets[i] = 0;
+  *n_out = 0;
+  if (!n->committed) return errf(TFIDF_E_STATE, "search before tfidf_node_commit");
+  if (n->cfg.stats_mode != TFIDF_STATS_GLOBAL)
+    return errf(TFIDF_E_STATE, "GLOBAL mode only (tfidf_node_search_names_batch)");
+  // shard 0 writes the caller's arrays; the others take part with cap == 0 (offsets only)
+  std::vector<std::vector<uint64_t>> ho(n->shards.size());
+  int rc0 = TFIDF_OK;
+  std::string msg0;
+  const int rc = n->pool->run([&](uint32_t g) {
+    if (g == 0) {
+      rc0 = tfidf_dist_search_batch_all(n->shards[0], n->comms[0], n->doc_base[0], q_utf8, q_offsets, n_q, doc_ids,
+                                        scores, cap, hit_offsets, n_out);
+      if (rc0 == TFIDF_E_BUFFER) msg0 = tfidf_last_error();
+      return rc0 == TFIDF_E_BUFFER ? TFIDF_OK : rc0;
+    }
+    ho[g].assign((size_t)n_q + 1, 0);
+    uint64_t m = 0;
+    const int r = tfidf_dist_search_batch_all(n->shards[g], n->comms[g], n->doc_base[g], q_utf8, q_offsets, n_q,
+                                              nullptr, nullptr, 0, ho[g].data(), &m);
+    return r == TFIDF_E_BUFFER ? TFIDF_OK : r;
+  });
+  if (rc) return rc;
+  return rc0 == TFIDF_E_BUFFER ? set_error(TFIDF_E_BUFFER, msg0.c_str()) : TFIDF_OK;
+}
+
+extern "C" int tfidf_node_search_names_batch(tfidf_node *n, const uint8_t *q_utf8, const uint64_t *q_offsets,
+                                             uint32_t n_q, uint64_t *n_out, uint64_t *n_bytes) {
+  if (!n || !n_out || (n_q && !q_offsets)) return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lk(n->mu);
+  *n_out = 0;
+  if (n_bytes) *n_bytes = 0;
+  if (!n->committed) return errf(TFIDF_E_STATE, "search before tfidf_node_commit");
+  if (n->cfg.stats_mode != TFIDF_STATS_SHARD)
+    return errf(TFIDF_E_STATE, "SHARD mode only (tfidf_node_search_batch_all)");
+  std::vector<std::string> why(n->shards.size());
+  std::vector<uint64_t> m(n->shards.size(), 0), b(n->shards.size(), 0);
+  if (int rc = n->pool->run([&](uint32_t g) {
+        const int r = tfidf_dist_shard_search_batch(n->shards[g], n->comms[g], q_utf8, q_offsets, n_q, &m[g], &b[g]);
+        if (r == TFIDF_OK && n->comms[g]->last_failed) why[g] = tfidf_last_error();
+        return r;
+      }))
+    return rc;
+  *n_out = m[0];
+  if (n_bytes) *n_bytes = b[0];
+  if (n->comms[0]->last_failed) {                          // partial answer: say which shards were skipped
+    std::string msg = why[0];
+    for (size_t g = 0; g < why.size(); g++)
+      if ((n->comms[0]->last_failed >> g) & 1u) msg += "; shard " + std::to_string(g) + ": " + why[g];
+    set_error(TFIDF_OK, msg.c_str());
+  }
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_node_last_names_batch(const tfidf_node *n, uint8_t *buf, uint64_t cap, uint64_t *offsets,
+                                           double *scores, uint64_t n_cap, uint64_t *name_offsets, uint64_t *n_out,
+                                           uint64_t *n_bytes) {
+  if (!n || !name_offsets || !n_out || !n_bytes) return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_node *>(n)->mu);
+  return tfidf_dist_last_names_batch(n->comms[0], buf, cap, offsets, scores, n_cap, name_offsets, n_out, n_bytes);
 }
 
 extern "C" int tfidf_node_last_failed(const tfidf_node *n, uint64_t *shard_mask) {

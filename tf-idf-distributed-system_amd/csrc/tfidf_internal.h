@@ -403,7 +403,9 @@ constexpr uint64_t kHitsGroupAvg = 6144;   // all hits: 8-run LDS group merge wh
 // queries.  P: n_q * R2 + 1 u64; q_off [n_q + 1]: each query's offset in out_doc / out_score
 // (q_off[n_q] = the chunk's hits).  hits holds n_q * R2 * kBlockDocs u64 (gapped runs) and is
 // reused as a merge buffer; tmp0 / tmp2 hold the chunk's hits (hits_bound: an upper bound of
-// them, summed over the chunk's queries).
+// them, summed over the chunk's queries).  keys_out (when non-null): the last level writes
+// packed merge keys with doc_base added there instead of out_doc / out_score, as
+// launch_hits_order does.
 constexpr uint32_t hits_runs_per_query(uint32_t R) {
   uint32_t r2 = 2;
   while (r2 < R) r2 <<= 1;
@@ -411,7 +413,8 @@ constexpr uint32_t hits_runs_per_query(uint32_t R) {
 }
 hipError_t launch_hits_order_batch(uint64_t *hits, const uint32_t *hits_n, uint32_t n_q, uint32_t R, uint64_t *P,
                                    uint64_t *tmp0, uint64_t *tmp2, uint32_t *out_doc, float *out_score,
-                                   uint64_t *q_off, uint64_t hits_bound, int grid, hipStream_t s);
+                                   uint64_t *q_off, uint64_t *keys_out, uint64_t doc_base, uint64_t hits_bound,
+                                   int grid, hipStream_t s);
 
 // --- GLOBAL statistics by term ownership (kernels_vocab.hip) ---
 hipError_t vocab_count(const uint64_t *dict, uint32_t C, uint32_t G, uint32_t *counts, hipStream_t s);
@@ -438,6 +441,20 @@ int reader_batch_keys_device(tfidf_reader *rd, const uint8_t *q_utf8, const uint
                              uint32_t k, uint64_t doc_base, void *d_keys);
 int reader_all_keys_device(tfidf_reader *rd, const uint8_t *q, uint64_t q_len, uint64_t doc_base, void *d_keys,
                            uint64_t cap, uint64_t *n_out);
+// All hits of a batch as device merge keys (the node-level all-hits batches):
+// the batch is prepared once (bounds[i] = query i's local hit bound: the sum of
+// its scoring terms' df, at most num_docs; 0 for a query that does not parse),
+// then any query range [a, z) of it is scored: the range's hits as merge keys
+// (score bits << 32 | ~(doc + doc_base)), query-major and contiguous, each
+// query's run in descending key order, appended into d_keys (cap >= the sum of
+// the range's bounds) by local chunks whose scratch stays in the single-index
+// all-hits budget; counts[i] = hits of query a + i, *n_out their sum.
+struct PreparedAllHits;
+int reader_prepare_all_hits(tfidf_reader *rd, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                            PreparedAllHits **out, uint64_t *bounds);
+void free_prepared_all_hits(PreparedAllHits *pb);
+int reader_batch_all_keys_device(tfidf_reader *rd, const PreparedAllHits *pb, uint32_t a, uint32_t z,
+                                 uint64_t doc_base, void *d_keys, uint64_t cap, uint64_t *counts, uint64_t *n_out);
 // GLOBAL exchange steps without the public calls' host synchronisation (every
 // buffer is the communicator's, ordered on the index's stream)
 int vocab_partition_async(tfidf_index *ix, uint32_t n_ranks, void *d_records, uint64_t cap, void *d_counts,

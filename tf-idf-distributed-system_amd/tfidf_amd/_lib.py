@@ -142,6 +142,10 @@ SIGNATURES = {
                                           U32P]),
     "tfidf_dist_shard_commit": (C.c_int, [VP, VP, U64P]),
     "tfidf_dist_shard_search": (C.c_int, [VP, VP, C.c_char_p, C.c_uint64, U64P, U64P]),
+    "tfidf_dist_search_batch_all": (C.c_int, [VP, VP, C.c_uint64, C.c_char_p, U64P, C.c_uint32, U64P, F32P, C.c_uint64,
+                                              U64P, U64P]),
+    "tfidf_dist_shard_search_batch": (C.c_int, [VP, VP, C.c_char_p, U64P, C.c_uint32, U64P, U64P]),
+    "tfidf_dist_last_names_batch": (C.c_int, [VP, C.c_char_p, C.c_uint64, U64P, F64P, C.c_uint64, U64P, U64P, U64P]),
     "tfidf_dist_last_hits": (C.c_int, [VP, U64P, F32P, C.c_uint64, U64P]),
     "tfidf_dist_last_failed": (C.c_int, [VP, U64P]),
     "tfidf_reader_open": (C.c_int, [VP, C.POINTER(VP)]),
@@ -161,6 +165,9 @@ SIGNATURES = {
     "tfidf_node_search_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, C.c_uint32, U64P, F32P, U32P]),
     "tfidf_node_search_names": (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, U64P, F64P,
                                           C.c_uint64, U64P, U64P]),
+    "tfidf_node_search_batch_all": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U64P, F32P, C.c_uint64, U64P, U64P]),
+    "tfidf_node_search_names_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U64P, U64P]),
+    "tfidf_node_last_names_batch": (C.c_int, [VP, C.c_char_p, C.c_uint64, U64P, F64P, C.c_uint64, U64P, U64P, U64P]),
     "tfidf_node_doc_key": (C.c_int, [VP, C.c_uint64, C.c_char_p, C.c_uint64, U64P]),
     "tfidf_node_last_failed": (C.c_int, [VP, U64P]),
     "tfidf_node_stats_get": (C.c_int, [VP, VP]),

@@ -153,6 +153,50 @@ def _offsets(items):
     return offs
 
 
+def _batch_all_arrays(call, queries, cap):
+    """A node-level all-hits batch call: once with ``cap`` result slots, and
+    once more with the size the library reports when that was too small (as
+    engine._batch_all_arrays).  ``call(blob, offs, nq, docs, scores, cap,
+    hit_offs, n)`` -> status.  -> (docs int64[], scores float32[], offsets uint64[n_q + 1])."""
+    nq = len(queries)
+    offs = _offsets(queries)
+    blob = b"".join(queries)
+    hit_offs = np.zeros(nq + 1, np.uint64)
+    n = C.c_uint64()
+    for _ in range(2):
+        docs = np.empty(max(cap, 1), np.uint64)
+        scores = np.empty(max(cap, 1), np.float32)
+        rc = call(blob, L.ptr(offs, C.c_uint64), nq, L.ptr(docs, C.c_uint64), L.ptr(scores, C.c_float), cap,
+                  L.ptr(hit_offs, C.c_uint64), C.byref(n))
+        if rc != L.E_BUFFER:
+            break
+        cap = n.value
+    L.check(rc)
+    return docs[:n.value].astype(np.int64), scores[:n.value], hit_offs
+
+
+def _default_cap(queries):
+    return min(65536 * max(len(queries), 1), 1 << 24)
+
+
+def _hit_lists(docs, scores, offs):
+    d, s, o = docs.tolist(), scores.tolist(), offs.tolist()
+    return [list(zip(d[o[i]:o[i + 1]], s[o[i]:o[i + 1]])) for i in range(len(o) - 1)]
+
+
+def _last_names_batch(fn, h, nq, n, nb):
+    """The kept result of a SHARD batch -> one [(name bytes, double)] list per query."""
+    buf = C.create_string_buffer(max(nb, 1))
+    offs = np.zeros(n + 1, np.uint64)
+    sc = np.zeros(max(n, 1), np.float64)
+    qo = np.zeros(nq + 1, np.uint64)
+    m, b = C.c_uint64(), C.c_uint64()
+    L.check(fn(h, buf, max(nb, 1), L.ptr(offs, C.c_uint64), L.ptr(sc, C.c_double), n, L.ptr(qo, C.c_uint64),
+               C.byref(m), C.byref(b)))
+    raw, o, s, q = buf.raw, offs.tolist(), sc.tolist(), qo.tolist()
+    return [[(raw[o[i]:o[i + 1]], s[i]) for i in range(q[j], q[j + 1])] for j in range(nq)]
+
+
 class DistShard:
     """One rank's shard in process model (2): every method is collective
     (every rank calls it, in the same order)."""
@@ -215,7 +259,35 @@ class DistShard:
                                                  L.ptr(scores, C.c_float), L.ptr(counts, C.c_uint32)))
         return docs.astype(np.int64), scores, counts.astype(np.int64)
 
+    def search_batch_all_arrays(self, queries, cap=None):
+        """Every hit of each query over all ranks in one pass
+        (tfidf_dist_search_batch_all): (global docs int64[], scores float32[],
+        offsets uint64[n_q + 1]); query i's hits are [offsets[i], offsets[i + 1])
+        in (score desc, doc asc).  Collective, the retry included: every rank
+        passes the same ``cap``."""
+        lib = L.load()
+
+        def call(blob, offs, nq, docs, scores, cap, hit_offs, n):
+            return lib.tfidf_dist_search_batch_all(self.shard._h, self.comm._h, self.doc_base, blob, offs, nq, docs,
+                                                   scores, cap, hit_offs, n)
+
+        return _batch_all_arrays(call, queries, _default_cap(queries) if cap is None else cap)
+
+    def search_batch_all(self, queries):
+        """[search(q, 0) for q in queries] in one pass; a query that does not parse has no hits."""
+        return _hit_lists(*self.search_batch_all_arrays(queries))
+
     # -- SHARD search (Leader.start) ------------------------------------------------
+    def shard_search_batch(self, queries):
+        """[shard_search(q) for q in queries] from one search of the batch
+        (tfidf_dist_shard_search_batch); a query that does not parse has no names."""
+        lib = L.load()
+        offs = _offsets(queries)
+        n, nb = C.c_uint64(), C.c_uint64()
+        L.check(lib.tfidf_dist_shard_search_batch(self.shard._h, self.comm._h, b"".join(queries),
+                                                  L.ptr(offs, C.c_uint64), len(queries), C.byref(n), C.byref(nb)))
+        return _last_names_batch(lib.tfidf_dist_last_names_batch, self.comm._h, len(queries), n.value, nb.value)
+
     def shard_search(self, query: bytes):
         """[(name bytes, double)] in String.compareTo order."""
         n, nb = C.c_uint64(), C.c_uint64()
@@ -310,6 +382,31 @@ class Node:
                                                  L.ptr(docs, C.c_uint64), L.ptr(scores, C.c_float),
                                                  L.ptr(counts, C.c_uint32)))
         return docs.astype(np.int64), scores, counts.astype(np.int64)
+
+    def search_batch_all_arrays(self, queries, cap=None):
+        """Every hit of each query over the node's shards in one pass
+        (tfidf_node_search_batch_all): (global docs int64[], scores float32[],
+        offsets uint64[n_q + 1])."""
+        lib = L.load()
+
+        def call(blob, offs, nq, docs, scores, cap, hit_offs, n):
+            return lib.tfidf_node_search_batch_all(self._h, blob, offs, nq, docs, scores, cap, hit_offs, n)
+
+        return _batch_all_arrays(call, queries, _default_cap(queries) if cap is None else cap)
+
+    def search_batch_all(self, queries):
+        """[search(q, 0) for q in queries] in one pass; a query that does not parse has no hits."""
+        return _hit_lists(*self.search_batch_all_arrays(queries))
+
+    def search_names_batch(self, queries):
+        """[search_names(q) for q in queries] from one search of the batch
+        (tfidf_node_search_names_batch; the names are read from the kept result)."""
+        lib = L.load()
+        offs = _offsets(queries)
+        n, nb = C.c_uint64(), C.c_uint64()
+        L.check(lib.tfidf_node_search_names_batch(self._h, b"".join(queries), L.ptr(offs, C.c_uint64), len(queries),
+                                                  C.byref(n), C.byref(nb)))
+        return _last_names_batch(lib.tfidf_node_last_names_batch, self._h, len(queries), n.value, nb.value)
 
     def search_names(self, query: bytes):
         lib = L.load()

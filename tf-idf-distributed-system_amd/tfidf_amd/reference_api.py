@@ -181,8 +181,29 @@ class Leader:
     (sequentially; failed workers are skipped), sum scores per document name
     in double, return the map ordered by name."""
 
-    def __init__(self, workers):
+    def __init__(self, workers, node=None):
         self.workers = workers                # ServiceRegistry.getAllServiceAddresses()
+        self.node = node                      # a SHARD-mode distributed.Node holding the workers' shards
+
+    # /leader/start for the requests of concurrent threads in one pass:
+    # start(q) for each query.  Over a node (SHARD statistics: one shard per
+    # worker) the fan-out and the merge of the whole batch are one
+    # Node.search_names_batch; a query that fails on the workers (ParseException)
+    # merges nothing, as every worker answers [] for it (Worker.java:182-185).
+    def start_batch(self, search_queries):
+        if self.node is None:
+            return [self.start(q) for q in search_queries]
+        out = [{} for _ in search_queries]
+        enc, at = [], []
+        for i, q in enumerate(search_queries):
+            try:
+                enc.append(q.encode())
+                at.append(i)
+            except Exception:
+                pass                          # that request's exception on every worker -> {}
+        for i, merged in zip(at, self.node.search_names_batch(enc)):
+            out[i] = {name.decode(): score for name, score in merged}
+        return out
 
     def start(self, search_query: str):
         if not self.workers:
