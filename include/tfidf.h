@@ -20,6 +20,10 @@
  *       .parse(QueryParser.escape(q)); searcher.search(query, Integer.MAX_VALUE)
  *   tfidf_doc_key
  *       Worker.java:235-236 searcher.doc(sd.doc).get("path")
+ *   tfidf_delete_docs / tfidf_compact / tfidf_set_compact_threshold
+ *       IndexWriter.deleteDocuments(Term("path", key)) and the reclaiming of
+ *       deletes by Lucene's segment merges; the upload path overwrites files by
+ *       name (Worker.java:133-138 Files.copy REPLACE_EXISTING + updateDocument)
  *   tfidf_stats
  *       Worker.java:147-172 /worker/index-size (device bytes) + Lucene CollectionStatistics
  *   tfidf_vocab_* / tfidf_set_global_*
@@ -129,6 +133,10 @@ typedef struct tfidf_index_stats {
   uint64_t fused_queries;  /* tfidf_search top-k calls served by the one-launch fused path (index lifetime) */
   uint64_t unicode_wave_docs;  /* of unicode_docs: those the wave rules took (non-ASCII letters that are
                                   ALetter and lower case only); the rest went to the Unicode wave path */
+  uint64_t dead_docs;      /* staged documents replaced or deleted and not yet reclaimed (tfidf_compact) */
+  uint64_t dead_bytes;     /* their staged text bytes (part of text_bytes) */
+  uint64_t compactions;    /* tfidf_compact calls and commit-time compactions that reclaimed something (index
+                              lifetime) */
 } tfidf_index_stats;
 
 /* Per-phase device times of the last commit, measured with HIP events on the
@@ -183,11 +191,56 @@ int tfidf_add_docs_device(tfidf_index *ix, const void *d_utf8, const void *d_off
  *   - every staged document stays staged (tfidf_stats.text_bytes and
  *     device_bytes count the staged corpus, not the published one), so
  *     calling tfidf_commit again fails the same way;
- *   - to recover, replace the offending documents by key (tfidf_add_docs with
- *     their keys) or tfidf_clear and add a corpus that fits, then commit: the
+ *   - to recover, delete the offending documents (tfidf_delete_docs with their
+ *     keys; a failed commit keeps every staged document, so delete followed by
+ *     commit is the recovery path), replace them by key (tfidf_add_docs with
+ *     their keys), or tfidf_clear and add a corpus that fits, then commit: the
  *     result is that of a new index given the same documents.  The index may
- *     also be destroyed and created again with a larger vocab_capacity_log2. */
+ *     also be destroyed and created again with a larger vocab_capacity_log2.
+ * With a compaction threshold set (tfidf_set_compact_threshold) the commit
+ * first reclaims the dead documents when they hold enough of the staged text. */
 int tfidf_commit(tfidf_index *ix);
+
+/* ---- document lifecycle: delete, reclaim, read back ----
+ * tfidf_delete_docs: IndexWriter.deleteDocuments(new Term("path", key)) for
+ *   n_keys keys, key i = keys[key_offsets[i] .. key_offsets[i+1]).  A writer
+ *   call, staged like tfidf_add_docs: searches and readers keep the last
+ *   commit until the next tfidf_commit.  A key that names no live document is
+ *   not an error and is not counted (Lucene's delete-by-term); a key given
+ *   twice counts once; *n_deleted (may be NULL) = documents that went from
+ *   live to dead.  The key is forgotten: adding it later appends a new
+ *   document, as for a key never seen.  A keyless document (keys == NULL at add
+ *   time) is addressed by its key, its decimal ordinal; explicit keys are
+ *   looked up first.
+ * Keys never change: a keyless document keeps the ordinal it received when it
+ *   was added (the number of documents staged before it since create, clear
+ *   or load), whatever tfidf_compact does to the staged corpus, and later
+ *   keyless documents keep counting from there, never reusing a number.
+ * tfidf_compact: reclaim the dead documents (replaced or deleted) of the
+ *   staged corpus, as Lucene does when segments merge.  A writer call.  The
+ *   live documents are copied, in their order, into a NEW corpus buffer and
+ *   offsets buffer by one device copy kernel; the old buffers are never
+ *   written, because the published snapshot, open readers and in-flight
+ *   searches still read them, and they are freed when the last of those goes
+ *   (for the published snapshot: at the commit after the next).  Until then
+ *   both corpora are resident: the peak is old + new text, at most 2x the
+ *   staged text.  *bytes_reclaimed (may be NULL) = text bytes reclaimed;
+ *   *ms_device (may be NULL) = the copy kernel's time (HIP events on the
+ *   index's stream).  Nothing dead: no allocation, no kernel, 0 reclaimed.  On
+ *   TFIDF_E_OOM / TFIDF_E_HIP the index is exactly as before the call.  The
+ *   commit after a compaction produces the same index (doc ids, keys, scores)
+ *   as the commit without it; tfidf_save afterwards writes live documents only.
+ * tfidf_set_compact_threshold: with dead_pct in 1..100, tfidf_commit compacts
+ *   first when dead text bytes x 100 >= dead_pct x staged text bytes; 0
+ *   (default) = never.
+ * tfidf_doc_text / tfidf_reader_doc_text: the committed document's bytes as
+ *   they were added (its "stored field"), copied from the snapshot's own corpus
+ *   buffer; TFIDF_E_BUFFER with *n_out = size needed when cap is too small. */
+int tfidf_delete_docs(tfidf_index *ix, const uint8_t *keys, const uint64_t *key_offsets, uint64_t n_keys,
+                      uint64_t *n_deleted);
+int tfidf_compact(tfidf_index *ix, uint64_t *bytes_reclaimed, float *ms_device);
+int tfidf_set_compact_threshold(tfidf_index *ix, uint32_t dead_pct);
+int tfidf_doc_text(tfidf_index *ix, uint64_t doc, uint8_t *buf, uint64_t cap, uint64_t *n_out);
 /* GLOBAL statistics match terms across shards by their keys, so every shard
  * must hash its long / non-ASCII terms with one seed.  A commit tries seed
  * attempts 0, 1, 2, 3 in turn (the next one after a detected collision);
@@ -202,7 +255,10 @@ int tfidf_set_hash_attempt(tfidf_index *ix, uint32_t attempt);
  * liveness) to `path` (atomically: path.tmp, then rename).  tfidf_load stages a
  * saved file into an EMPTY index (same vocab_capacity_log2); call tfidf_commit
  * afterwards (more documents may be added first, replacing by key as usual).
- * The inverted index itself is rebuilt by the commit rather than stored. */
+ * The inverted index itself is rebuilt by the commit rather than stored.
+ * File version 1; an index whose keyless documents' keys are no longer their
+ * positions (after tfidf_compact) writes version 2, which adds their ordinals.
+ * Both load. */
 int tfidf_save(tfidf_index *ix, const char *path);
 int tfidf_load(tfidf_index *ix, const char *path);
 int tfidf_get_commit_timing(const tfidf_index *ix, tfidf_commit_timing *out);
@@ -256,6 +312,8 @@ int tfidf_reader_search_batch_all(tfidf_reader *rd, const uint8_t *q_utf8, const
                                   uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
                                   uint64_t *n_out);
 int tfidf_reader_doc_key(const tfidf_reader *rd, uint64_t doc, uint8_t *buf, uint64_t cap, uint64_t *n_out);
+/* tfidf_doc_text on the reader's snapshot (unchanged by later deletes, compactions and commits). */
+int tfidf_reader_doc_text(const tfidf_reader *rd, uint64_t doc, uint8_t *buf, uint64_t cap, uint64_t *n_out);
 /* tfidf_doc_keys of the reader's snapshot (offsets[num_docs + 1] of tfidf_reader_info). */
 int tfidf_reader_doc_keys(const tfidf_reader *rd, uint8_t *buf, uint64_t cap, uint64_t *offsets, uint64_t *n_bytes);
 /* Per-query device time of the last search call on this index (HIP events on the search's stream). */
@@ -561,6 +619,14 @@ int tfidf_node_add_docs(tfidf_node *n, int32_t shard, const uint8_t *utf8, const
                         const uint8_t *keys, const uint64_t *key_offsets);
 /* Commits every shard (in parallel), then GLOBAL statistics or the SHARD name table. */
 int tfidf_node_commit(tfidf_node *n);
+/* tfidf_delete_docs on one shard (shard >= 0) or on every shard (shard == -1:
+ * a name can live on several shards, as with Leader-routed uploads); *n_deleted
+ * (may be NULL) is summed over the shards.  tfidf_node_compact: tfidf_compact on
+ * every shard, in parallel; *bytes_reclaimed (may be NULL) summed.  Both only
+ * stage changes: the node serves its last tfidf_node_commit until the next one. */
+int tfidf_node_delete_docs(tfidf_node *n, int32_t shard, const uint8_t *keys, const uint64_t *key_offsets,
+                           uint64_t n_keys, uint64_t *n_deleted);
+int tfidf_node_compact(tfidf_node *n, uint64_t *bytes_reclaimed);
 /* GLOBAL mode; same results as tfidf_dist_search / _batch (global doc ids). */
 int tfidf_node_search(tfidf_node *n, const uint8_t *q, uint64_t q_len, uint32_t k, uint64_t *doc_ids, float *scores,
                       uint64_t cap, uint64_t *n_out);
@@ -612,6 +678,12 @@ int tfidf_device_free(int device, void *d_ptr);
  * handles do not see the library's allocations).  kind 1 = host -> device,
  * 2 = device -> host. */
 int tfidf_device_copy(int device, void *dst, const void *src, uint64_t bytes, int kind);
+/* Bench helper: `reps` contiguous device-to-device hipMemcpyAsync copies of
+ * `bytes` from d_src into a scratch buffer, each timed with HIP events on a
+ * stream of its own (ms[reps]; one untimed copy first).  The yardstick of
+ * tfidf_compact's copy kernel: a plain copy moves exactly the traffic a
+ * compaction must move. */
+int tfidf_device_copy_ms(int device, const void *d_src, uint64_t bytes, uint32_t reps, float *ms);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,7 @@
 
 #include "../../include/tfidf.h"
 #include "analysis.h"
+#include "compact_plan.h"
 #include "tfidf_common.h"
 #include "tfidf_internal.h"
 
@@ -36,6 +37,8 @@ hipError_t scatter_df_canon(const uint32_t *df, const uint32_t *canon_of_slot, u
                             hipStream_t s);
 hipError_t gather_df_canon(const uint32_t *dfc, const uint32_t *canon_of_slot, uint32_t C, uint32_t *gdf,
                            hipStream_t s);
+hipError_t launch_compact_text(const uint8_t *src, uint8_t *dst, const CompactRun *runs, uint64_t n_runs,
+                               uint64_t total, hipStream_t s);
 }  // namespace tfidf
 
 using namespace tfidf;
@@ -155,12 +158,18 @@ struct DevMem : DevBuf {
 // once a published snapshot holds them: a snapshot keeps the chunk list it was
 // committed with, the builder appends to its own last chunk (or starts a new
 // one when a snapshot shares it).  Staged id -> chunk by binary search.
+// A keyless document's key is its decimal ordinal: the number of documents
+// staged before it since create, clear or load.  That is its staged id until
+// tfidf_compact renumbers the staged ids; the ordinals stay (ord_first / ord).
 struct KeyChunk {
   uint64_t first = 0;                // staged id of the chunk's first document
+  uint64_t ord_first = 0;            // ordinal of document i = ord_first + i ...
+  std::vector<uint64_t> ord;         // ... unless listed here (after a compaction left gaps)
   std::string arena;
   std::vector<uint64_t> off{0};
-  std::vector<uint8_t> synth;        // 1 = key is the decimal staged id
+  std::vector<uint8_t> synth;        // 1 = key is the decimal ordinal
   uint64_t size() const { return synth.size(); }
+  uint64_t ordinal(uint64_t i) const { return ord.empty() ? ord_first + i : ord[i]; }
 };
 struct KeyTable {
   std::vector<std::shared_ptr<KeyChunk>> ch;
@@ -175,40 +184,66 @@ struct KeyTable {
   void key(uint64_t st, std::string *out) const {
     const KeyChunk &c = chunk_of(st);
     const uint64_t i = st - c.first;
-    if (c.synth[i]) *out = std::to_string(st);
+    if (c.synth[i]) *out = std::to_string(c.ordinal(i));
     else out->assign(c.arena.data() + c.off[i], c.off[i + 1] - c.off[i]);
   }
   uint64_t key_len(uint64_t st) const {
     const KeyChunk &c = chunk_of(st);
     const uint64_t i = st - c.first;
-    return c.synth[i] ? std::to_string(st).size() : c.off[i + 1] - c.off[i];
+    return c.synth[i] ? std::to_string(c.ordinal(i)).size() : c.off[i + 1] - c.off[i];
   }
-  // the builder's chunk to append to (a new one when a snapshot shares the last)
-  KeyChunk &tail(uint64_t n_staged) {
-    if (ch.empty() || ch.back().use_count() > 1) {
+  uint64_t ordinal(uint64_t st) const {
+    const KeyChunk &c = chunk_of(st);
+    return c.ordinal(st - c.first);
+  }
+  bool is_synth(uint64_t st) const {
+    const KeyChunk &c = chunk_of(st);
+    return c.synth[st - c.first] != 0;
+  }
+  // the builder's chunk to append the document of ordinal `ord` to (a new one
+  // when a snapshot shares the last, or when its ordinals do not continue)
+  KeyChunk &tail(uint64_t n_staged, uint64_t ord) {
+    if (ch.empty() || ch.back().use_count() > 1 ||
+        (ch.back()->ord.empty() && ch.back()->ord_first + ch.back()->size() != ord)) {
       ch.push_back(std::make_shared<KeyChunk>());
       ch.back()->first = n_staged;
+      ch.back()->ord_first = ord;
     }
+    if (!ch.back()->ord.empty()) ch.back()->ord.push_back(ord);
     return *ch.back();
   }
-  // flat copies (persistence)
-  void flatten(std::string *arena, std::vector<uint64_t> *off, std::vector<uint8_t> *synth) const {
+  // flat copies (persistence, compaction)
+  void flatten(std::string *arena, std::vector<uint64_t> *off, std::vector<uint8_t> *synth,
+               std::vector<uint64_t> *ord = nullptr) const {
     arena->clear();
     off->assign(1, 0);
     synth->clear();
+    if (ord) ord->clear();
     for (const auto &c : ch) {
       for (uint64_t i = 0; i < c->size(); i++) {
         arena->append(c->arena, c->off[i], c->off[i + 1] - c->off[i]);
         off->push_back(arena->size());
+        if (ord) ord->push_back(c->ordinal(i));
       }
       synth->insert(synth->end(), c->synth.begin(), c->synth.end());
+    }
+  }
+  // a chunk's ordinals: a base when they are consecutive, else the list
+  static void set_ordinals(KeyChunk *c, std::vector<uint64_t> &&ord) {
+    if (ordinals_contiguous(ord)) {
+      c->ord_first = ord.empty() ? 0 : ord[0];
+      c->ord.clear();
+    } else {
+      c->ord = std::move(ord);
     }
   }
   // many small chunks (one per commit of a single upload): merge them into one
   void compact() {
     if (ch.size() <= 64) return;
     auto one = std::make_shared<KeyChunk>();
-    flatten(&one->arena, &one->off, &one->synth);
+    std::vector<uint64_t> ord;
+    flatten(&one->arena, &one->off, &one->synth, &ord);
+    set_ordinals(one.get(), std::move(ord));
     ch.assign(1, one);
   }
 };
@@ -368,6 +403,10 @@ struct tfidf_index {
   std::vector<uint8_t> staged_live;
   std::unordered_map<std::string, uint64_t> key_to_staged;
   uint64_t n_dead = 0;
+  uint64_t dead_bytes = 0;             // staged text bytes of the dead documents
+  uint64_t next_ord = 0;               // documents staged since create / clear / load: the next keyless key
+  uint32_t compact_pct = 0;            // tfidf_set_compact_threshold (0 = commit never compacts)
+  uint64_t compactions = 0;            // tfidf_compact calls that reclaimed something (index lifetime)
 
   // build scratch (the commit in progress)
   uint32_t cap_log2 = 18;
@@ -576,14 +615,23 @@ static int grow_offsets(tfidf_index *ix, uint64_t extra_docs) {
   return grow_shared(ix, &ix->offsets, (ix->n_staged + extra_docs + 1) * 8, (ix->n_staged + 1) * 8, false);
 }
 
+// a staged document goes from live to dead (false: it was dead already)
+static bool kill_staged(tfidf_index *ix, uint64_t st) {
+  if (!ix->staged_live[st]) return false;
+  ix->staged_live[st] = 0;
+  ix->n_dead++;
+  ix->dead_bytes += ix->h_offsets[st + 1] - ix->h_offsets[st];
+  return true;
+}
+
 static void register_key(tfidf_index *ix, const uint8_t *k, uint64_t n, bool synth) {
   const uint64_t idx = ix->n_staged;
-  KeyChunk &c = ix->keys.tail(idx);
+  KeyChunk &c = ix->keys.tail(idx, ix->next_ord++);
   if (!synth) {
     std::string key((const char *)k, n);
     auto it = ix->key_to_staged.find(key);
     if (it != ix->key_to_staged.end()) {       // updateDocument: delete-by-term, then add
-      if (ix->staged_live[it->second]) { ix->staged_live[it->second] = 0; ix->n_dead++; }
+      kill_staged(ix, it->second);
       it->second = idx;
     } else {
       ix->key_to_staged.emplace(std::move(key), idx);
@@ -662,6 +710,8 @@ extern "C" int tfidf_clear(tfidf_index *ix) {
   ix->staged_live.clear();
   ix->key_to_staged.clear();
   ix->n_dead = 0;
+  ix->dead_bytes = 0;
+  ix->next_ord = 0;
   std::shared_ptr<Snapshot> old;
   {
     std::lock_guard<std::mutex> sl(ix->snap_mu);    // searches from now on: not committed
@@ -715,10 +765,17 @@ extern "C" int tfidf_save(tfidf_index *ix, const char *path) {
   std::string key_arena;
   std::vector<uint64_t> key_off;
   std::vector<uint8_t> key_synth;
-  ix->keys.flatten(&key_arena, &key_off, &key_synth);
+  std::vector<uint64_t> key_ord;
+  ix->keys.flatten(&key_arena, &key_off, &key_synth, &key_ord);
+  // Version 2 appends the keyless documents' ordinals (next_ord, ord[n_staged])
+  // to the metadata.  Only an index whose keyless keys are no longer their
+  // positions (tfidf_compact) needs it; every other index writes version 1.
+  bool v2 = false;
+  for (uint64_t i = 0; i < ix->n_staged; i++)
+    if (key_synth[i] && (key_ord[i] != i || ix->next_ord != ix->n_staged)) { v2 = true; break; }
   FileHeader h{};
   memcpy(h.magic, kFileMagic, 8);
-  h.version = 1;
+  h.version = v2 ? 2 : 1;
   h.k1 = ix->cfg.k1;
   h.b = ix->cfg.b;
   h.stats_mode = ix->cfg.stats_mode;
@@ -729,6 +786,10 @@ extern "C" int tfidf_save(tfidf_index *ix, const char *path) {
   h.key_bytes = key_arena.size();
   h.n_dead = ix->n_dead;
   h.meta_hash = meta_hash(ix, key_arena, key_off, key_synth);
+  if (v2) {
+    h.meta_hash = fnv1a(h.meta_hash, &ix->next_ord, 8);
+    h.meta_hash = fnv1a(h.meta_hash, key_ord.data(), key_ord.size() * 8);
+  }
   const std::string tmp = std::string(path) + ".tmp";
   FILE *f = fopen(tmp.c_str(), "wb");
   if (!f) return fail(TFIDF_E_INVALID_ARG, "cannot open %s for writing", tmp.c_str());
@@ -738,6 +799,10 @@ extern "C" int tfidf_save(tfidf_index *ix, const char *path) {
   ok = ok && (key_arena.empty() || fwrite(key_arena.data(), 1, key_arena.size(), f) == key_arena.size());
   ok = ok && (ix->n_staged == 0 || fwrite(key_synth.data(), 1, ix->n_staged, f) == ix->n_staged);
   ok = ok && (ix->n_staged == 0 || fwrite(ix->staged_live.data(), 1, ix->n_staged, f) == ix->n_staged);
+  if (v2) {
+    ok = ok && fwrite(&ix->next_ord, 8, 1, f) == 1;
+    ok = ok && fwrite(key_ord.data(), 8, key_ord.size(), f) == key_ord.size();
+  }
   // corpus text: device -> pinned staging buffer -> file, chunk by chunk
   if (ok && ix->text_bytes) {
     if (!ix->stage[0]) {
@@ -774,9 +839,10 @@ extern "C" int tfidf_load(tfidf_index *ix, const char *path) {
   FILE *f = fopen(path, "rb");
   if (!f) return fail(TFIDF_E_INVALID_ARG, "cannot open %s", path);
   FileHeader h{};
-  if (fread(&h, sizeof h, 1, f) != 1 || memcmp(h.magic, kFileMagic, 8) != 0 || h.version != 1) {
+  if (fread(&h, sizeof h, 1, f) != 1 || memcmp(h.magic, kFileMagic, 8) != 0 ||
+      (h.version != 1 && h.version != 2)) {
     fclose(f);
-    return fail(TFIDF_E_INVALID_ARG, "%s is not a tfidf index file (version 1)", path);
+    return fail(TFIDF_E_INVALID_ARG, "%s is not a tfidf index file (version 1 or 2)", path);
   }
   if (h.vocab_capacity_log2 != ix->cap_log2) {
     fclose(f);
@@ -790,6 +856,13 @@ extern "C" int tfidf_load(tfidf_index *ix, const char *path) {
   bool ok = fread(offs.data(), 8, n + 1, f) == n + 1 && fread(koff.data(), 8, n + 1, f) == n + 1;
   ok = ok && (h.key_bytes == 0 || fread(&arena[0], 1, h.key_bytes, f) == h.key_bytes);
   ok = ok && (n == 0 || (fread(synth.data(), 1, n, f) == n && fread(live.data(), 1, n, f) == n));
+  uint64_t next_ord = n;
+  std::vector<uint64_t> ord;
+  if (ok && h.version == 2) {          // ordinals: strictly increasing, below next_ord
+    ord.resize(n);
+    ok = fread(&next_ord, 8, 1, f) == 1 && (n == 0 || fread(ord.data(), 8, n, f) == n);
+    for (uint64_t i = 0; ok && i < n; i++) ok = ord[i] < next_ord && (i == 0 || ord[i] > ord[i - 1]);
+  }
   ok = ok && offs[0] == 0 && offs[n] == h.text_bytes && koff[0] == 0 && koff[n] == h.key_bytes;
   for (uint64_t i = 0; ok && i < n; i++) ok = offs[i + 1] >= offs[i] && koff[i + 1] >= koff[i];
   std::vector<uint8_t> text;
@@ -809,16 +882,24 @@ extern "C" int tfidf_load(tfidf_index *ix, const char *path) {
     one->arena = arena;
     one->off.assign(koff.begin(), koff.end());
     one->synth = synth;
+    if (h.version == 2) KeyTable::set_ordinals(one.get(), std::vector<uint64_t>(ord));
     ix->keys.ch.assign(1, one);
   }
+  ix->next_ord = next_ord;
   ix->staged_live = live;
   ix->key_to_staged.clear();
   ix->n_dead = 0;
+  ix->dead_bytes = 0;
   for (uint64_t i = 0; i < n; i++) {
-    if (!live[i]) { ix->n_dead++; continue; }
+    if (!live[i]) { ix->n_dead++; ix->dead_bytes += offs[i + 1] - offs[i]; continue; }
     if (!synth[i]) ix->key_to_staged[std::string(arena, koff[i], koff[i + 1] - koff[i])] = i;
   }
-  if (ix->n_dead != h.n_dead || meta_hash(ix, arena, koff, synth) != h.meta_hash) {
+  uint64_t mh = meta_hash(ix, arena, koff, synth);
+  if (h.version == 2) {
+    mh = fnv1a(mh, &next_ord, 8);
+    mh = fnv1a(mh, ord.data(), ord.size() * 8);
+  }
+  if (ix->n_dead != h.n_dead || mh != h.meta_hash) {
     return fail(TFIDF_E_INVALID_ARG, "%s: metadata checksum mismatch", path);
   }
   return TFIDF_OK;
@@ -881,6 +962,158 @@ extern "C" int tfidf_add_docs_device(tfidf_index *ix, const void *d_utf8, const 
     ix->n_staged++;
   }
   ix->text_bytes += total_bytes;
+  return TFIDF_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Document lifecycle: delete by key, reclaim the dead documents, read a
+// document back (IndexWriter.deleteDocuments; Lucene reclaims deletes when
+// segments merge; the stored field of a hit).
+
+// canonical decimal (no sign, no leading zero): a keyless document's key
+static bool parse_ordinal(const std::string &k, uint64_t *out) {
+  if (k.empty() || k.size() > 20 || (k[0] == '0' && k.size() > 1)) return false;
+  uint64_t v = 0;
+  for (char c : k) {
+    if (c < '0' || c > '9') return false;
+    const uint64_t d = (uint64_t)(c - '0');
+    if (v > (~0ull - d) / 10) return false;
+    v = v * 10 + d;
+  }
+  *out = v;
+  return true;
+}
+
+// staged id of the document of ordinal `ord` (ordinals ascend with the staged ids)
+static bool find_ordinal(const tfidf_index *ix, uint64_t ord, uint64_t *st) {
+  uint64_t a = 0, z = ix->n_staged;
+  while (a < z) {
+    const uint64_t m = a + (z - a) / 2;
+    if (ix->keys.ordinal(m) < ord) a = m + 1; else z = m;
+  }
+  if (a >= ix->n_staged || ix->keys.ordinal(a) != ord) return false;
+  *st = a;
+  return true;
+}
+
+extern "C" int tfidf_delete_docs(tfidf_index *ix, const uint8_t *keys, const uint64_t *key_offsets, uint64_t n_keys,
+                                 uint64_t *n_deleted) {
+  if (n_deleted) *n_deleted = 0;
+  if (!ix || (n_keys && !key_offsets)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  for (uint64_t i = 0; i < n_keys; i++)
+    if (key_offsets[i + 1] < key_offsets[i]) return fail(TFIDF_E_INVALID_ARG, "key_offsets must be non-decreasing");
+  if (n_keys && !keys && key_offsets[n_keys] != key_offsets[0]) return fail(TFIDF_E_INVALID_ARG, "NULL keys");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  uint64_t n = 0;
+  for (uint64_t i = 0; i < n_keys; i++) {
+    const uint64_t len = key_offsets[i + 1] - key_offsets[i];
+    const std::string key(len ? (const char *)keys + key_offsets[i] : "", len);
+    auto it = ix->key_to_staged.find(key);
+    if (it != ix->key_to_staged.end()) {       // an explicit key: forgotten, a later add appends
+      if (kill_staged(ix, it->second)) n++;
+      ix->key_to_staged.erase(it);
+      continue;
+    }
+    uint64_t ord = 0, st = 0;                  // a keyless document's decimal ordinal
+    if (parse_ordinal(key, &ord) && find_ordinal(ix, ord, &st) && ix->keys.is_synth(st) && kill_staged(ix, st)) n++;
+  }
+  if (n_deleted) *n_deleted = n;
+  return TFIDF_OK;
+}
+
+struct TimingEvents {
+  hipEvent_t a = nullptr, b = nullptr;
+  ~TimingEvents() {
+    if (a) hipEventDestroy(a);
+    if (b) hipEventDestroy(b);
+  }
+};
+
+// tfidf_compact under ix->mu.  Everything that can fail happens before the
+// first change to the index.
+static int compact_locked(tfidf_index *ix, uint64_t *bytes_reclaimed, float *ms_device) {
+  if (bytes_reclaimed) *bytes_reclaimed = 0;
+  if (ms_device) *ms_device = 0.0f;
+  if (!ix->n_dead) return TFIDF_OK;
+  DeviceGuard g(ix->cfg.device);
+  hipStream_t s = ix->stream;
+  CompactPlan P;
+  compact_plan(ix->staged_live.data(), ix->h_offsets.data(), ix->n_staged, &P);
+  // New buffers: published snapshots, open readers and in-flight searches
+  // share the old ones (with live_map and keys in the old staged ids).
+  auto nt = std::make_shared<DevMem>(ix->cfg.device), no = std::make_shared<DevMem>(ix->cfg.device);
+  DevMem runs(ix->cfg.device);
+  const uint64_t tcap = (P.live_bytes + 128 + ((1ull << 20) - 1)) & ~((1ull << 20) - 1);
+  const uint64_t ocap = std::max<uint64_t>(64, (P.n_live + 1) * 8);
+  if (nt->reserve(tcap) != hipSuccess || no->reserve(ocap) != hipSuccess ||
+      runs.reserve(P.runs.size() * sizeof(CompactRun)) != hipSuccess) {
+    hipGetLastError();
+    return fail(TFIDF_E_OOM, "tfidf_compact: no device memory for the compacted corpus (%llu bytes)",
+                (unsigned long long)(tcap + ocap));
+  }
+  TimingEvents ev;
+  HIP_TRY(hipEventCreate(&ev.a));
+  HIP_TRY(hipEventCreate(&ev.b));
+  // zero from the end of the live text to the capacity (the tokenizers read
+  // into that slack); the kernel writes whole 16-byte chunks below z0
+  const uint64_t z0 = (P.live_bytes + 15) & ~15ull;
+  HIP_TRY(hipMemsetAsync(nt->as<uint8_t>() + z0, 0, tcap - z0, s));
+  HIP_TRY(hipMemcpyAsync(no->p, P.new_offsets.data(), (P.n_live + 1) * 8, hipMemcpyHostToDevice, s));
+  if (!P.runs.empty())
+    HIP_TRY(hipMemcpyAsync(runs.p, P.runs.data(), P.runs.size() * sizeof(CompactRun), hipMemcpyHostToDevice, s));
+  HIP_TRY(hipEventRecord(ev.a, s));
+  HIP_TRY(launch_compact_text(ix->text->as<uint8_t>(), nt->as<uint8_t>(), runs.as<CompactRun>(), P.runs.size(),
+                              P.live_bytes, s));
+  HIP_TRY(hipEventRecord(ev.b, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  float ms = 0.0f;
+  HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+
+  // host tables: the live entries, in order; a fresh key table (snapshots share the old chunks)
+  std::string arena;
+  std::vector<uint64_t> koff, kord;
+  std::vector<uint8_t> ksynth;
+  ix->keys.flatten(&arena, &koff, &ksynth, &kord);
+  auto one = std::make_shared<KeyChunk>();
+  one->synth.reserve(P.n_live);
+  for (uint64_t i = 0; i < ix->n_staged; i++) {
+    if (!ix->staged_live[i]) continue;
+    one->arena.append(arena, koff[i], koff[i + 1] - koff[i]);
+    one->off.push_back(one->arena.size());
+    one->synth.push_back(ksynth[i]);
+  }
+  KeyTable::set_ordinals(one.get(), compact_ordinals(ix->staged_live.data(), ix->n_staged, kord.data()));
+  for (auto it = ix->key_to_staged.begin(); it != ix->key_to_staged.end();) {
+    const uint64_t nw = P.old_to_new[it->second];
+    if (nw == kCompactDead) it = ix->key_to_staged.erase(it);
+    else { it->second = nw; ++it; }
+  }
+  ix->keys.ch.assign(1, one);
+  ix->h_offsets = std::move(P.new_offsets);
+  ix->staged_live.assign(P.n_live, 1);
+  ix->n_staged = P.n_live;
+  ix->text_bytes = P.live_bytes;
+  ix->n_dead = 0;
+  ix->dead_bytes = 0;
+  ix->text = std::move(nt);
+  ix->offsets = std::move(no);
+  ix->compactions++;
+  if (bytes_reclaimed) *bytes_reclaimed = P.dead_bytes;
+  if (ms_device) *ms_device = ms;
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_compact(tfidf_index *ix, uint64_t *bytes_reclaimed, float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  return compact_locked(ix, bytes_reclaimed, ms_device);
+}
+
+extern "C" int tfidf_set_compact_threshold(tfidf_index *ix, uint32_t dead_pct) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  if (dead_pct > 100) return fail(TFIDF_E_INVALID_ARG, "dead_pct %u > 100", dead_pct);
+  std::lock_guard<std::mutex> lk(ix->mu);
+  ix->compact_pct = dead_pct;
   return TFIDF_OK;
 }
 
@@ -1506,6 +1739,11 @@ extern "C" int tfidf_commit(tfidf_index *ix) {
   if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
   std::lock_guard<std::mutex> lk(ix->mu);
   DeviceGuard g(ix->cfg.device);
+  // tfidf_set_compact_threshold: reclaim the dead documents first.  A
+  // compaction that cannot get its memory leaves the index as it was, and the
+  // commit builds through live_map as it always has.
+  if (ix->compact_pct && ix->n_dead && ix->dead_bytes * 100 >= (uint64_t)ix->compact_pct * ix->text_bytes)
+    compact_locked(ix, nullptr, nullptr);
   // The build target: the previous snapshot if no search holds it any more
   // (its buffers are reused as they are), else a new one.  The published
   // snapshot stays searchable until this build succeeds; a failed build
@@ -1577,6 +1815,9 @@ extern "C" int tfidf_stats(const tfidf_index *ix, tfidf_index_stats *out) {
     out->hash_seed = ix->hash_seed;
     out->hash_rebuilds = ix->hash_rebuilds;
     staged_bytes = ix->text->bytes + ix->offsets->bytes;
+    out->dead_docs = ix->n_dead;
+    out->dead_bytes = ix->dead_bytes;
+    out->compactions = ix->compactions;
   }
   if (S) {
     out->num_docs = S->n_docs;
@@ -2244,6 +2485,14 @@ extern "C" int tfidf_reader_doc_key(const tfidf_reader *rd, uint64_t doc, uint8_
   return TFIDF_OK;
 }
 
+static int doc_text_of(const Snapshot *S, uint64_t doc, uint8_t *buf, uint64_t cap, uint64_t *n_out);
+extern "C" int tfidf_reader_doc_text(const tfidf_reader *rd, uint64_t doc, uint8_t *buf, uint64_t cap,
+                                     uint64_t *n_out) {
+  if (!rd || !n_out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  *n_out = 0;
+  return doc_text_of(rd->S.get(), doc, buf, cap, n_out);
+}
+
 extern "C" int tfidf_search_batch(tfidf_index *ix, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
                                   uint32_t k, uint32_t *doc_ids, float *scores, uint32_t *counts) {
   if (!ix || !q_offsets || !doc_ids || !scores || !counts) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
@@ -2847,6 +3096,28 @@ extern "C" int tfidf_doc_key(const tfidf_index *ix, uint64_t doc, uint8_t *buf, 
   if (k.size() > cap) return fail(TFIDF_E_BUFFER, "key needs %zu bytes", k.size());
   if (buf && !k.empty()) memcpy(buf, k.data(), k.size());
   return TFIDF_OK;
+}
+
+// the document's bytes out of the snapshot's own corpus buffer
+static int doc_text_of(const Snapshot *S, uint64_t doc, uint8_t *buf, uint64_t cap, uint64_t *n_out) {
+  if (doc >= S->n_docs) return fail(TFIDF_E_INVALID_ARG, "doc out of range");
+  DeviceGuard g(S->dev);
+  const uint64_t st = S->staged_of(doc);
+  uint64_t o[2] = {0, 0};
+  HIP_TRY(hipMemcpy(o, S->offsets->as<uint64_t>() + st, 16, hipMemcpyDeviceToHost));
+  const uint64_t n = o[1] - o[0];
+  *n_out = n;
+  if (n > cap || (n && !buf)) return fail(TFIDF_E_BUFFER, "text needs %llu bytes", (unsigned long long)n);
+  if (n) HIP_TRY(hipMemcpy(buf, S->text->as<uint8_t>() + o[0], n, hipMemcpyDeviceToHost));
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_doc_text(tfidf_index *ix, uint64_t doc, uint8_t *buf, uint64_t cap, uint64_t *n_out) {
+  if (!ix || !n_out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  *n_out = 0;
+  const std::shared_ptr<Snapshot> S = current(ix);
+  if (!S) return fail(TFIDF_E_INVALID_ARG, "doc out of range");
+  return doc_text_of(S.get(), doc, buf, cap, n_out);
 }
 
 static int doc_keys_of(const Snapshot *S, uint8_t *buf, uint64_t cap, uint64_t *offsets, uint64_t *n_bytes) {
@@ -3464,6 +3735,36 @@ extern "C" int tfidf_device_copy(int device, void *dst, const void *src, uint64_
   DeviceGuard g(device);
   if (bytes) HIP_TRY(hipMemcpy(dst, src, bytes, kind == 1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
   return TFIDF_OK;
+}
+
+extern "C" int tfidf_device_copy_ms(int device, const void *d_src, uint64_t bytes, uint32_t reps, float *ms) {
+  if (!d_src || !bytes || !reps || !ms) return fail(TFIDF_E_INVALID_ARG, "NULL or empty argument");
+  DeviceGuard g(device);
+  DevMem dst(device);
+  if (dst.reserve(bytes) != hipSuccess) {
+    hipGetLastError();
+    return fail(TFIDF_E_OOM, "tfidf_device_copy_ms: %llu bytes", (unsigned long long)bytes);
+  }
+  hipStream_t s = nullptr;
+  HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  TimingEvents ev;
+  int rc = TFIDF_OK;
+  auto run = [&]() -> int {
+    HIP_TRY(hipEventCreate(&ev.a));
+    HIP_TRY(hipEventCreate(&ev.b));
+    for (uint32_t r = 0; r <= reps; r++) {             // round 0 warms up (first touch of dst)
+      HIP_TRY(hipEventRecord(ev.a, s));
+      HIP_TRY(hipMemcpyAsync(dst.p, d_src, bytes, hipMemcpyDeviceToDevice, s));
+      HIP_TRY(hipEventRecord(ev.b, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      if (r) HIP_TRY(hipEventElapsedTime(&ms[r - 1], ev.a, ev.b));
+    }
+    return TFIDF_OK;
+  };
+  rc = run();
+  hipStreamSynchronize(s);
+  hipStreamDestroy(s);
+  return rc;
 }
 
 // ---------------------------------------------------------------------------

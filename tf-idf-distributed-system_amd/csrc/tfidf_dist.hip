@@ -1812,6 +1812,35 @@ extern "C" int tfidf_node_add_docs(tfidf_node *n, int32_t shard, const uint8_t *
   });
 }
 
+// Deletes and compactions only stage changes: every shard keeps serving the
+// snapshot of the last tfidf_node_commit, so the node stays committed.
+extern "C" int tfidf_node_delete_docs(tfidf_node *n, int32_t shard, const uint8_t *keys, const uint64_t *key_offsets,
+                                      uint64_t n_keys, uint64_t *n_deleted) {
+  if (n_deleted) *n_deleted = 0;
+  if (!n || (n_keys && !key_offsets)) return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lk(n->mu);
+  const uint32_t G = (uint32_t)n->shards.size();
+  if (shard >= (int32_t)G || shard < -1) return errf(TFIDF_E_INVALID_ARG, "shard %d out of range", shard);
+  if (shard >= 0) return tfidf_delete_docs(n->shards[shard], keys, key_offsets, n_keys, n_deleted);
+  // a name can live on several shards (Leader-routed uploads): ask every one
+  std::vector<uint64_t> nd(G, 0);
+  int rc = n->pool->run([&](uint32_t g) { return tfidf_delete_docs(n->shards[g], keys, key_offsets, n_keys, &nd[g]); });
+  if (n_deleted)
+    for (uint64_t v : nd) *n_deleted += v;
+  return rc;
+}
+
+extern "C" int tfidf_node_compact(tfidf_node *n, uint64_t *bytes_reclaimed) {
+  if (bytes_reclaimed) *bytes_reclaimed = 0;
+  if (!n) return errf(TFIDF_E_INVALID_ARG, "NULL node");
+  std::lock_guard<std::mutex> lk(n->mu);
+  std::vector<uint64_t> nb(n->shards.size(), 0);
+  int rc = n->pool->run([&](uint32_t g) { return tfidf_compact(n->shards[g], &nb[g], nullptr); });
+  if (bytes_reclaimed)
+    for (uint64_t v : nb) *bytes_reclaimed += v;
+  return rc;
+}
+
 extern "C" int tfidf_node_commit(tfidf_node *n) {
   if (!n) return errf(TFIDF_E_INVALID_ARG, "NULL node");
   std::lock_guard<std::mutex> lk(n->mu);

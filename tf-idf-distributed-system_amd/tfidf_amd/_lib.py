@@ -44,7 +44,7 @@ class IndexStats(C.Structure):
                                           "pack_docs", "pack_retried", "unicode_docs", "long_chunked",
                                           "malformed_docs", "hash_seed", "hash_rebuilds",
                                           "coalesced_batches", "coalesced_queries", "unit_batches", "unit_count", "fused_queries",
-                                          "unicode_wave_docs")]
+                                          "unicode_wave_docs", "dead_docs", "dead_bytes", "compactions")]
 
 
 class CommitTiming(C.Structure):
@@ -90,6 +90,11 @@ SIGNATURES = {
     "tfidf_load": (C.c_int, [VP, C.c_char_p]),
     "tfidf_add_docs_device": (C.c_int, [VP, VP, VP, C.c_uint64, C.c_uint64]),
     "tfidf_commit": (C.c_int, [VP]),
+    "tfidf_delete_docs": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint64, U64P]),
+    "tfidf_compact": (C.c_int, [VP, U64P, F32P]),
+    "tfidf_set_compact_threshold": (C.c_int, [VP, C.c_uint32]),
+    "tfidf_doc_text": (C.c_int, [VP, C.c_uint64, VP, C.c_uint64, U64P]),
+    "tfidf_reader_doc_text": (C.c_int, [VP, C.c_uint64, VP, C.c_uint64, U64P]),
     "tfidf_set_hash_attempt": (C.c_int, [VP, C.c_uint32]),
     "tfidf_get_commit_timing": (C.c_int, [VP, C.POINTER(CommitTiming)]),
     "tfidf_stats": (C.c_int, [VP, C.POINTER(IndexStats)]),
@@ -161,6 +166,8 @@ SIGNATURES = {
     "tfidf_node_shard": (C.c_int, [VP, C.c_uint32, C.POINTER(VP), U32P]),
     "tfidf_node_add_docs": (C.c_int, [VP, C.c_int32, C.c_char_p, U64P, C.c_uint64, C.c_char_p, U64P]),
     "tfidf_node_commit": (C.c_int, [VP]),
+    "tfidf_node_delete_docs": (C.c_int, [VP, C.c_int32, C.c_char_p, U64P, C.c_uint64, U64P]),
+    "tfidf_node_compact": (C.c_int, [VP, U64P]),
     "tfidf_node_search": (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, U64P, F32P, C.c_uint64, U64P]),
     "tfidf_node_search_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, C.c_uint32, U64P, F32P, U32P]),
     "tfidf_node_search_names": (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, U64P, F64P,
@@ -173,6 +180,7 @@ SIGNATURES = {
     "tfidf_node_stats_get": (C.c_int, [VP, VP]),
     "tfidf_device_free": (C.c_int, [C.c_int, VP]),
     "tfidf_device_copy": (C.c_int, [C.c_int, VP, VP, C.c_uint64, C.c_int]),
+    "tfidf_device_copy_ms": (C.c_int, [C.c_int, VP, C.c_uint64, C.c_uint32, F32P]),
 }
 
 _lib = None

@@ -354,6 +354,22 @@ class Node:
     def commit(self):
         L.check(L.load().tfidf_node_commit(self._h))
 
+    def delete_documents(self, keys, shard=-1):
+        """Stage the deletion of the named documents on one shard, or on every
+        shard (-1: a name can live on several).  Returns the documents deleted."""
+        keys = list(keys)
+        koffs = _offsets(keys)
+        n = C.c_uint64()
+        L.check(L.load().tfidf_node_delete_docs(self._h, shard, b"".join(keys), L.ptr(koffs, C.c_uint64), len(keys),
+                                                C.byref(n)))
+        return n.value
+
+    def compact(self):
+        """tfidf_compact on every shard; returns the text bytes reclaimed."""
+        nb = C.c_uint64()
+        L.check(L.load().tfidf_node_compact(self._h, C.byref(nb)))
+        return nb.value
+
     def stats(self):
         s = NodeStats()
         L.check(L.load().tfidf_node_stats_get(self._h, C.byref(s)))

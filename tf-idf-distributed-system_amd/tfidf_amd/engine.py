@@ -49,6 +49,25 @@ def _batch_all_arrays(fn, handle, queries, cap):
     return docs[:n.value], scores[:n.value], hit_offs
 
 
+def _key_arrays(keys):
+    """list of bytes -> (blob, uint64 offsets[n + 1])."""
+    koffs = np.zeros(len(keys) + 1, np.uint64)
+    if len(keys):
+        koffs[1:] = np.cumsum([len(k) for k in keys], dtype=np.uint64)
+    return b"".join(keys), koffs
+
+
+def _doc_text(fn, handle, doc):
+    """tfidf_doc_text / tfidf_reader_doc_text: size first, then the bytes."""
+    n = C.c_uint64()
+    rc = fn(handle, doc, None, 0, C.byref(n))
+    if rc not in (L.OK, L.E_BUFFER):
+        L.check(rc)
+    buf = C.create_string_buffer(max(n.value, 1))
+    L.check(fn(handle, doc, buf, n.value, C.byref(n)))
+    return buf.raw[:n.value]
+
+
 def _hit_lists(docs, scores, offs):
     d, s, o = docs.tolist(), scores.tolist(), offs.tolist()
     return [list(zip(d[o[i]:o[i + 1]], s[o[i]:o[i + 1]])) for i in range(len(o) - 1)]
@@ -131,6 +150,30 @@ class ShardIndex:
 
     def commit(self):
         L.check(L.load().tfidf_commit(self._h))
+
+    # -- document lifecycle (IndexWriter.deleteDocuments / segment merges) -----
+    def delete_documents(self, keys):
+        """Stage the deletion of the documents named by keys (list of bytes;
+        a keyless document's key is its decimal ordinal).  Returns how many
+        documents went from live to dead; visible to searches after commit()."""
+        kb, koffs = _key_arrays(list(keys))
+        n = C.c_uint64()
+        L.check(L.load().tfidf_delete_docs(self._h, kb, L.ptr(koffs, C.c_uint64), len(koffs) - 1, C.byref(n)))
+        return n.value
+
+    def compact(self):
+        """Reclaim the dead documents of the staged corpus (tfidf_compact)."""
+        nb, ms = C.c_uint64(), C.c_float()
+        L.check(L.load().tfidf_compact(self._h, C.byref(nb), C.byref(ms)))
+        return {"bytes_reclaimed": nb.value, "ms_device": ms.value}
+
+    def set_compact_threshold(self, pct):
+        """commit() compacts first when dead text >= pct % of the staged text (0 = never)."""
+        L.check(L.load().tfidf_set_compact_threshold(self._h, pct))
+
+    def doc_text(self, doc):
+        """The committed document's bytes as they were added."""
+        return _doc_text(L.load().tfidf_doc_text, self._h, doc)
 
     def set_hash_attempt(self, attempt):
         """Seed attempt (0..3) the following commits start from (tfidf_set_hash_attempt)."""
@@ -445,6 +488,10 @@ class Reader:
         n = C.c_uint64()
         L.check(L.load().tfidf_reader_doc_key(self._h, doc, buf, 4096, C.byref(n)))
         return buf.raw[:n.value]
+
+    def doc_text(self, doc):
+        """The document's bytes in this reader's snapshot."""
+        return _doc_text(L.load().tfidf_reader_doc_text, self._h, doc)
 
     def doc_keys(self):
         lib = L.load()

@@ -42,11 +42,16 @@ class Worker:
     """Worker.java:42-242 — one shard: builds its index at init, answers
     /worker/process with every hit of its shard-local BM25 ranking."""
 
-    def __init__(self, documents_path=None, index_path=None, device=0, vocab_capacity_log2=18):
+    def __init__(self, documents_path=None, index_path=None, device=0, vocab_capacity_log2=18,
+                 compact_threshold_pct=0):
         # @Value("${mydocument.path}") / @Value("${lucene.index.path}") (Worker.java:48-52)
         self.DOCUMENTS_PATH = documents_path
         self.INDEX_PATH = index_path
         self.index = ShardIndex(device=device, vocab_capacity_log2=vocab_capacity_log2)
+        # uploads overwrite files by name (Worker.java:133-138): with a threshold
+        # the commit reclaims the replaced versions, as Lucene's merges do
+        if compact_threshold_pct:
+            self.index.set_compact_threshold(compact_threshold_pct)
         self._committed = False
 
     INDEX_FILE = "tfidf.idx"
