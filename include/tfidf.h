@@ -93,8 +93,12 @@ extern "C" {
 typedef struct tfidf_index tfidf_index;
 
 typedef struct tfidf_config {
-  float k1;                     /* BM25 k1, default 1.2f (BM25Similarity()) */
-  float b;                      /* BM25 b,  default 0.75f */
+  float k1;                     /* BM25 k1, default 1.2f (BM25Similarity()); finite and >= 0 */
+  float b;                      /* BM25 b,  default 0.75f; in [0, 1].  tfidf_create returns
+                                   TFIDF_E_INVALID_ARG for any other k1 / b (NaN included), as
+                                   BM25Similarity(k1, b) throws: scores must stay >= 0 and ordered.
+                                   Legal values can give scores of exactly 0.0f (tf * norm_inverse
+                                   <= 2^-24 at a large k1); such hits are returned like any other */
   int32_t stats_mode;           /* TFIDF_STATS_SHARD (default) or TFIDF_STATS_GLOBAL */
   int32_t device;               /* HIP device ordinal */
   uint32_t vocab_capacity_log2; /* dictionary slots = 2^x, x in [10, 26]; default 18.  A shard holds at most
@@ -258,7 +262,9 @@ int tfidf_set_hash_attempt(tfidf_index *ix, uint32_t attempt);
  * The inverted index itself is rebuilt by the commit rather than stored.
  * File version 1; an index whose keyless documents' keys are no longer their
  * positions (after tfidf_compact) writes version 2, which adds their ordinals.
- * Both load. */
+ * Both load.  The file records k1 and b: tfidf_load returns
+ * TFIDF_E_INVALID_ARG, and stages nothing, when their bit patterns differ from
+ * this index's configuration (the saved index's ranking is not this one's). */
 int tfidf_save(tfidf_index *ix, const char *path);
 int tfidf_load(tfidf_index *ix, const char *path);
 int tfidf_get_commit_timing(const tfidf_index *ix, tfidf_commit_timing *out);

@@ -57,6 +57,44 @@ def test_create_without_device_fails_loudly():
     assert rc in (L.E_NO_DEVICE, L.E_HIP)
 
 
+def _create(k1=None, b=None):
+    lib = L.load()
+    cfg = L.Config()
+    lib.tfidf_config_init(C.byref(cfg))
+    if k1 is not None:
+        cfg.k1 = k1
+    if b is not None:
+        cfg.b = b
+    h = C.c_void_p()
+    rc = lib.tfidf_create(C.byref(cfg), C.byref(h))
+    msg = lib.tfidf_last_error().decode() if rc else ""
+    if rc == 0:
+        lib.tfidf_destroy(h)
+    return rc, msg
+
+
+@pytest.mark.parametrize("field,value", [("k1", -1.0), ("k1", float("nan")), ("k1", float("inf")),
+                                         ("k1", -1e-30), ("k1", float("-inf")),
+                                         ("b", -0.1), ("b", 1.5), ("b", float("nan")), ("b", float("inf"))])
+def test_create_rejects_illegal_bm25_parameters(field, value):
+    """BM25Similarity(k1, b) throws unless k1 is finite and >= 0 and b is in
+    [0, 1]; tfidf_create says so before it asks for a device."""
+    rc, msg = _create(**{field: value})
+    assert rc == L.E_INVALID_ARG
+    assert re.search(r"\b%s\b" % field, msg), msg
+    other = "b" if field == "k1" else "k1"
+    assert not re.search(r"\b%s\b" % other, msg), msg
+
+
+@pytest.mark.parametrize("k1,b", [(0.0, 0.75), (1.2, 0.0), (1.2, 1.0), (0.0, 0.0), (16777216.0, 1.0), (1e9, 0.75),
+                                  (3.4028234663852886e38, 0.75)])
+def test_create_accepts_legal_edge_parameters(k1, b):
+    """The edges of the legal ranges pass the check: the call succeeds on a
+    GPU, and without one fails for the lack of a device, not for the values."""
+    rc, msg = _create(k1, b)
+    assert rc in (L.OK, L.E_NO_DEVICE, L.E_HIP), msg
+
+
 def _raw_key(term):
     """tfidf_common.h key format for terms of <= 16 bytes (exact)."""
     b = term.lower()

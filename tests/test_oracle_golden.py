@@ -111,13 +111,14 @@ def test_tie_break_doc_ascending(ix):
     assert hits[3][1] == hits[4][1] and hits[3][0] == 5 and hits[4][0] == 6
 
 
-def _np_bm25_scores(ix, terms_boosts):
+def _np_bm25_scores(ix, terms_boosts, k1=1.2, b=0.75):
     """Independent float32 NumPy restatement of BM25Similarity 9.8.0."""
     N = ix.doc_count
     avg = np.float32(ix.sum_ttf / float(N))
     L = np.array([O.byte4_to_int(i) for i in range(256)], np.float32)
-    k1, b = np.float32(1.2), np.float32(0.75)
-    cache = np.float32(1) / (k1 * ((np.float32(1) - b) + b * L / avg))
+    k1, b = np.float32(k1), np.float32(b)
+    with np.errstate(divide="ignore"):                 # k1 = 0: the cache is +inf
+        cache = np.float32(1) / (k1 * ((np.float32(1) - b) + b * L / avg))
     acc = {}
     for term, boost in terms_boosts:
         df = ix.df(term)
@@ -140,6 +141,61 @@ def _np_bm25_scores(ix, terms_boosts):
 def test_bm25_numpy_restatement(ix, q):
     want = _np_bm25_scores(ix, O.query_terms(q))
     assert ix.search(q) == want
+
+
+# BM25 parameters beyond the defaults (tests/test_gpu_bm25_params.py holds the
+# GPU paths to the oracle at these): the restatement above is the reference
+# that does not share the oracle's C, in particular where the norm cache is
+# +inf (k1 = 0) and where 1 + tf * cache rounds to 1 (scores of exactly 0.0f).
+BM25_SETS = {
+    "plain": (2.0, 1.0),
+    "nolen": (1.2, 0.0),
+    "idf": (0.0, 0.75),
+    "mixed0": (16777216.0, 0.75),
+    "all0": (1e9, 0.75),
+}
+
+
+@pytest.fixture(scope="module")
+def zipf_texts():
+    from tfidf_amd import synth
+    return synth.corpus(400, V=300, len_min=5, len_max=120)
+
+
+@pytest.mark.parametrize("name", list(BM25_SETS))
+def test_bm25_parameter_sets_numpy_restatement(zipf_texts, name):
+    from tfidf_amd import synth
+    k1, b = BM25_SETS[name]
+    o = O.OracleIndex(k1, b)
+    for i, t in enumerate(zipf_texts):
+        o.add_doc(str(i).encode(), t)
+    o.commit()
+    cache = O.norm_cache(k1, b, O.avgdl(o.sum_ttf, o.doc_count))
+    assert np.isinf(cache).all() == (name == "idf") and not np.isnan(cache).any()
+    terms = [synth.word(r) for r in (1, 2, 3, 5, 8, 13, 21, 34, 55, 89, 144, 233)]
+    bits, n_hits = [], 0
+    for t in terms:
+        got = o.search(t)
+        want = _np_bm25_scores(o, [(t, 1.0)], k1, b)
+        assert len(got) == o.df(t) > 0
+        assert [d for d, _ in got] == [d for d, _ in want]
+        g32 = np.array([s for _, s in got], np.float32).view(np.uint32)
+        assert (g32 == np.array([s for _, s in want], np.float32).view(np.uint32)).all()   # bit for bit, no -0.0
+        bits.append(g32)
+        n_hits += len(got)
+        if name == "idf":                              # every hit scores the term's weight
+            assert set(g32.tolist()) == {np.float32(O.idf(o.df(t), o.doc_count)).view(np.uint32).item()}
+    every = np.concatenate(bits)
+    if name == "mixed0":
+        assert (every == 0).sum() > n_hits // 10 and (every != 0).sum() > n_hits // 10
+    elif name == "all0":
+        assert (every == 0).all()
+    else:
+        assert (every != 0).all()
+    # sums over several terms (double accumulation, one float rounding), boosts included
+    for q in (b"aaaa aaab aaac", b"aaab aaab aaae aaah", b"aaam aaau zzzzzz"):
+        assert o.search(q) == _np_bm25_scores(o, O.query_terms(q), k1, b)
+    o.close()
 
 
 def test_empty_query_is_parse_exception(ix):

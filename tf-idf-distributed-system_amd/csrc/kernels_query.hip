@@ -200,7 +200,7 @@ __device__ __forceinline__ void merge_query_wave(const QueryParams &p, uint32_t 
     lmax = max(lmax, (uint64_t)__shfl_xor((long long)lmax, o, 64));
   }
   const uint32_t M = cnt, kk = M < k ? M : k;
-  uint64_t T = 1, tmask = ~0ull;                            // take (key & tmask) >= T (keys > 0)
+  uint64_t T = 1, tmask = ~0ull;                            // take (key & tmask) >= T (keys > 0: ~doc != 0, score bits may be 0)
   if (M > k) {
     int rb = 64 - __builtin_clzll(lmin ^ lmax);
     uint64_t prefix = rb < 64 ? lmax & (~0ull << rb) : 0ull;
@@ -566,7 +566,10 @@ __global__ void __launch_bounds__(kScoreThreads) k_score_blocks(QueryParams p) {
       mn = min(mn, (uint32_t)__shfl_xor((int)mn, o, 64));
       mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
     }
-    if ((tid & 63) == 0 && mx) { atomicMin(&sm.smin, mn); atomicMax(&sm.smax, mx); }
+    // every wave: one without a hit brings the identities (~0, 0); one whose
+    // hits all score 0.0f (bits 0: tf * norm_inverse <= 2^-24 at a large k1)
+    // must bring its 0, or the select below never counts those hits
+    if ((tid & 63) == 0) { atomicMin(&sm.smin, mn); atomicMax(&sm.smax, mx); }
     __syncthreads();
     // bits [r, 32) are common to all hits / resolved; each pass takes the next
     // (up to) 8 bits below r as the digit, so the first digit is the top 8
@@ -658,7 +661,7 @@ __global__ void __launch_bounds__(1024) k_merge_topk(QueryParams p) {
   if (part) atomicAdd(&sm.total, part);
   auto key_at = [&](uint32_t f) -> uint64_t {
     const uint32_t b = f / k, i = f - b * k;
-    return i < cn[b] ? cand[f] : 0ull;                     // 0 = empty (real keys have score bits > 0)
+    return i < cn[b] ? cand[f] : 0ull;                     // 0 = empty (a real key's low word ~doc is non-zero; its score bits may be 0)
   };
   const bool inreg = nflat <= kMergeRegs * blockDim.x;
   uint64_t kr[kMergeRegs];

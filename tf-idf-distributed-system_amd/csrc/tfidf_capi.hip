@@ -528,6 +528,12 @@ extern "C" int tfidf_create(const tfidf_config *cfg, tfidf_index **out) {
   if (lg < 10 || lg > 26) return fail(TFIDF_E_INVALID_ARG, "vocab_capacity_log2 must be in [10, 26]");
   if (lg > kMaxBlockCapLog2 && cfg->inversion == TFIDF_INVERSION_BLOCK)
     return fail(TFIDF_E_INVALID_ARG, "block-major inversion supports vocab_capacity_log2 <= %u", kMaxBlockCapLog2);
+  // BM25Similarity(k1, b) throws on anything else: a negative or NaN k1 gives
+  // negative or NaN scores, and every select and merge orders hits by the
+  // unsigned bit pattern of the score (negated tests: NaN fails them too)
+  if (!(std::isfinite(cfg->k1) && cfg->k1 >= 0.f))
+    return fail(TFIDF_E_INVALID_ARG, "k1 must be finite and >= 0 (got %g)", (double)cfg->k1);
+  if (!(cfg->b >= 0.f && cfg->b <= 1.f)) return fail(TFIDF_E_INVALID_ARG, "b must be in [0, 1] (got %g)", (double)cfg->b);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(TFIDF_E_NO_DEVICE, "no HIP device");
   if (cfg->device < 0 || cfg->device >= ndev) return fail(TFIDF_E_NO_DEVICE, "device %d out of range", cfg->device);
@@ -848,6 +854,12 @@ extern "C" int tfidf_load(tfidf_index *ix, const char *path) {
     fclose(f);
     return fail(TFIDF_E_INVALID_ARG, "index file has vocab_capacity_log2 %u, this index %u", h.vocab_capacity_log2,
                 ix->cap_log2);
+  }
+  // bit patterns: the saved index's scores are this index's only at the same floats
+  if (memcmp(&h.k1, &ix->cfg.k1, sizeof(float)) != 0 || memcmp(&h.b, &ix->cfg.b, sizeof(float)) != 0) {
+    fclose(f);
+    return fail(TFIDF_E_INVALID_ARG, "index file has (k1, b) = (%.9g, %.9g), this index (%.9g, %.9g)", (double)h.k1,
+                (double)h.b, (double)ix->cfg.k1, (double)ix->cfg.b);
   }
   const uint64_t n = h.n_staged;
   std::vector<uint64_t> offs(n + 1), koff(n + 1);
