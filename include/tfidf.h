@@ -322,6 +322,63 @@ int tfidf_reader_doc_key(const tfidf_reader *rd, uint64_t doc, uint8_t *buf, uin
 int tfidf_reader_doc_text(const tfidf_reader *rd, uint64_t doc, uint8_t *buf, uint64_t cap, uint64_t *n_out);
 /* tfidf_doc_keys of the reader's snapshot (offsets[num_docs + 1] of tfidf_reader_info). */
 int tfidf_reader_doc_keys(const tfidf_reader *rd, uint8_t *buf, uint64_t cap, uint64_t *offsets, uint64_t *n_bytes);
+/* ---- hit highlighting: match offsets and snippets from the device corpus ----
+ * No reference counterpart (Worker.java:216 stores "contents" with Store.NO);
+ * the step past tfidf_doc_text: the device re-scans only the listed documents
+ * of the snapshot's own corpus and returns which words matched and one short
+ * passage per document, instead of the caller downloading whole documents.
+ * Positive terms of a query: parsed as tfidf_search parses it, the analysed
+ *   terms of every clause that is not MUST_NOT, distinct, in order of first
+ *   appearance; a term's position in that list is its ordinal (a function of the
+ *   query alone: a term the index does not hold keeps its ordinal and matches
+ *   nothing).  tfidf_query_positive_terms returns them NUL-terminated, in
+ *   ordinal order (host only; buffer protocol of tfidf_analyze).
+ * Matches of (query, document): the tokens of the document, as the index
+ *   tokenised it, whose term is a positive term: (start, len, ordinal), start and
+ *   len in bytes of the original text relative to the document's first byte (len
+ *   is the raw span: "İstanbul" is 9 bytes for the term "istanbul"), ascending by
+ *   start.  A document that is not valid UTF-8 (indexed empty) has none; a
+ *   document that is not a hit of the query is legal and yields what it holds.
+ * Snippet of (query, document, W = max_bytes, 16 <= W <= 65536): every match
+ *   of at most W bytes is a candidate whose window holds the matches from it on
+ *   that end within W bytes of its start; the best window has the most distinct
+ *   terms (ordinals >= 63 count as one), then the most matches, then the
+ *   earliest start.  The range starts half the unused bytes before the window
+ *   (not before the document), is W bytes long (not past the document's end),
+ *   and both ends move inwards to UTF-8 character boundaries; without a
+ *   candidate it is the head of the document.  The snippet is that byte range;
+ *   its matches are the document's matches wholly inside it, starts relative
+ *   to the snippet.  DESIGN.md section 2 states the rule exactly.
+ * docs may repeat and come in any order; output row i belongs to docs[i]: its
+ *   matches are [match_offsets[i], match_offsets[i + 1]) of starts / lens /
+ *   ordinals, its snippet [text_offsets[i], text_offsets[i + 1]) of text, which
+ *   begins at byte doc_starts[i] of the document.  A doc >= num_docs:
+ *   TFIDF_E_INVALID_ARG, nothing written.  n_docs == 0: OK, offsets {0}.
+ * Query errors as in tfidf_search.  The offsets arrays (n_docs + 1 entries),
+ *   doc_starts and the totals are always written in full; TFIDF_E_BUFFER when a
+ *   total exceeds its cap (nothing is promised about the payload then; cap 0
+ *   with NULL payload pointers asks for the sizes).  Snippet text never exceeds
+ *   n_docs x max_bytes.  *ms_device (may be NULL): HIP events on the call's
+ *   stream, first copy to last.
+ * The calls run on a search context (own stream and scratch) beside other
+ *   readers, tfidf_add_docs and tfidf_commit, and never wait for a commit;
+ *   tfidf_matches / tfidf_snippets use the snapshot published at the call. */
+int tfidf_reader_matches(tfidf_reader *rd, const uint8_t *q, uint64_t q_len, const uint32_t *docs, uint64_t n_docs,
+                         uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t cap,
+                         uint64_t *match_offsets, uint64_t *n_out, float *ms_device);
+int tfidf_reader_snippets(tfidf_reader *rd, const uint8_t *q, uint64_t q_len, const uint32_t *docs, uint64_t n_docs,
+                          uint32_t max_bytes, uint8_t *text, uint64_t text_cap, uint64_t *text_offsets,
+                          uint64_t *doc_starts, uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t m_cap,
+                          uint64_t *match_offsets, uint64_t *n_text, uint64_t *n_matches, float *ms_device);
+int tfidf_matches(tfidf_index *ix, const uint8_t *q, uint64_t q_len, const uint32_t *docs, uint64_t n_docs,
+                  uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t cap, uint64_t *match_offsets,
+                  uint64_t *n_out, float *ms_device);
+int tfidf_snippets(tfidf_index *ix, const uint8_t *q, uint64_t q_len, const uint32_t *docs, uint64_t n_docs,
+                   uint32_t max_bytes, uint8_t *text, uint64_t text_cap, uint64_t *text_offsets, uint64_t *doc_starts,
+                   uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t m_cap, uint64_t *match_offsets,
+                   uint64_t *n_text, uint64_t *n_matches, float *ms_device);
+int tfidf_query_positive_terms(const uint8_t *q, uint64_t q_len, char *out, uint64_t cap, uint64_t *n_terms,
+                               uint64_t *n_bytes);
 /* Per-query device time of the last search call on this index (HIP events on the search's stream). */
 int tfidf_last_search_ms(const tfidf_index *ix, float *ms_scoring, float *ms_total);
 /* Device-time measurement of searches (HIP events around scoring; on by

@@ -260,6 +260,38 @@ inline int parse_query(const uint8_t *q, uint64_t n, QueryPlan *plan) {
   return kQOk;
 }
 
+// Positive terms of a query (hit highlighting): the analysed terms of every
+// clause that is not MUST_NOT, distinct, in order of first appearance in the
+// query; a term's position is its ordinal.  Same return codes as parse_query.
+// In a query that parses, every chunk is an operator word or a clause, and a
+// clause is MUST_NOT exactly when the chunk before it is NOT.
+inline int positive_terms(const uint8_t *q, uint64_t n, std::vector<std::string> *out) {
+  QueryPlan plan;
+  if (const int rc = parse_query(q, n, &plan)) return rc;
+  out->clear();
+  std::unordered_map<std::string, int> seen;
+  bool after_not = false;
+  for (uint64_t i = 0; i < n;) {
+    uint32_t w;
+    while (i < n && (w = qp_ws_len(q, n, i))) i += w;
+    if (i >= n) break;
+    uint64_t j = i;
+    while (j < n && !qp_ws_len(q, n, j)) j++;
+    const uint64_t len = j - i;
+    const bool is_not = len == 3 && !memcmp(q + i, "NOT", 3);
+    const bool is_op = is_not || (len == 3 && !memcmp(q + i, "AND", 3)) || (len == 2 && !memcmp(q + i, "OR", 2));
+    if (!is_op && !after_not) {
+      std::vector<std::string> toks;
+      analyze(q + i, len, &toks);
+      for (auto &t : toks)
+        if (seen.emplace(t, 1).second) out->push_back(t);
+    }
+    after_not = is_not;
+    i = j;
+  }
+  return kQOk;
+}
+
 inline void term_key(const std::string &t, uint64_t *lo, uint64_t *hi, uint64_t seed = 0) {
   KeyBuilder kb;
   for (unsigned char c : t) kb.push(c);

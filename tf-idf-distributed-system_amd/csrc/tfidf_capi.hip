@@ -25,6 +25,7 @@
 #include "../../include/tfidf.h"
 #include "analysis.h"
 #include "compact_plan.h"
+#include "snippet_plan.h"
 #include "tfidf_common.h"
 #include "tfidf_internal.h"
 
@@ -39,6 +40,21 @@ hipError_t gather_df_canon(const uint32_t *dfc, const uint32_t *canon_of_slot, u
                            hipStream_t s);
 hipError_t launch_compact_text(const uint8_t *src, uint8_t *dst, const CompactRun *runs, uint64_t n_runs,
                                uint64_t total, hipStream_t s);
+// hit highlighting (kernels_highlight.hip)
+hipError_t launch_hl_extents(const uint64_t *offsets, const uint32_t *staged, uint64_t n, uint64_t *ext,
+                             hipStream_t s);
+hipError_t launch_hl_scan(bool fill, const uint8_t *text, const uint64_t *ext, const HlItem *items, uint32_t n_items,
+                          const HlKey *keys, uint32_t n_keys, uint64_t seed, uint64_t *counts, uint64_t *starts,
+                          uint32_t *lens, uint32_t *ords, hipStream_t s);
+hipError_t launch_hl_row_offsets(const uint64_t *scanned, const uint64_t *first, uint64_t n, uint64_t *row_off,
+                                 hipStream_t s);
+hipError_t launch_hl_rank(const uint8_t *text, const uint64_t *ext, const uint64_t *row_off, const uint64_t *starts,
+                          const uint32_t *lens, const uint32_t *ords, uint32_t W, uint64_t n, uint64_t *sn_a,
+                          uint64_t *sn_len, uint64_t *in_first, uint64_t *in_cnt, hipStream_t s);
+hipError_t launch_hl_pack(const uint8_t *text, const uint64_t *ext, const uint64_t *sn_a, const uint64_t *text_off,
+                          uint8_t *out, const uint64_t *starts, const uint32_t *lens, const uint32_t *ords,
+                          const uint64_t *in_first, const uint64_t *m_off, uint64_t *o_starts, uint32_t *o_lens,
+                          uint32_t *o_ords, uint64_t n, hipStream_t s);
 }  // namespace tfidf
 
 using namespace tfidf;
@@ -338,6 +354,7 @@ struct SearchCtx {
   bool q_rec_start = true;                  // run_scoring records QEV_0 (false: a later chunk of a batch)
   bool q_timing = true;
   DevMem q_in, q_out, cand, cand_n, out_doc, out_score, hits, hits_n, hits_c, hits_s, hits_P, ovf;
+  DevMem hl_in, hl_cnt, hl_m, hl_s, hl_o;   // hit highlighting: plan, slice counts, matches, per-row ranges, packed output
   PinnedVec<uint32_t> q_host, q_res, q_cand_h;   // q_cand_h: fused single query's block candidates (host merge)
   std::vector<uint64_t> q_merge;
   std::vector<uint32_t> q_units;            // batch scoring units {q, b0, b1, 0} (run_scoring)
@@ -345,7 +362,7 @@ struct SearchCtx {
   float *res_score = nullptr;
   explicit SearchCtx(int d)
       : dev(d), q_in(d), q_out(d), cand(d), cand_n(d), out_doc(d), out_score(d), hits(d), hits_n(d), hits_c(d),
-        hits_s(d), hits_P(d), ovf(d) {}
+        hits_s(d), hits_P(d), ovf(d), hl_in(d), hl_cnt(d), hl_m(d), hl_s(d), hl_o(d) {}
   int init() {
     DeviceGuard g(dev);
     if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess ||
@@ -2503,6 +2520,281 @@ extern "C" int tfidf_reader_doc_text(const tfidf_reader *rd, uint64_t doc, uint8
   if (!rd || !n_out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
   *n_out = 0;
   return doc_text_of(rd->S.get(), doc, buf, cap, n_out);
+}
+
+// ---------------------------------------------------------------------------
+// hit highlighting: match offsets and snippets from the snapshot's own corpus
+// (snippet_plan.h, kernels_highlight.hip)
+
+struct HlOut {
+  uint32_t W = 0;                       // snippet bytes; 0 = the matches of the whole documents
+  uint8_t *text = nullptr;              // snippets only: packed bytes, their offsets, each snippet's
+  uint64_t text_cap = 0;                // start in its document
+  uint64_t *text_offsets = nullptr, *doc_starts = nullptr, *n_text = nullptr;
+  uint64_t *starts = nullptr;           // matches (of the documents / inside the snippets)
+  uint32_t *lens = nullptr, *ordinals = nullptr;
+  uint64_t m_cap = 0;
+  uint64_t *match_offsets = nullptr, *n_matches = nullptr;
+  float *ms_device = nullptr;
+};
+
+static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+static int highlight_on(tfidf_index *ix, Snapshot &S, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
+                        uint64_t n, const HlOut &o) {
+  if (o.ms_device) *o.ms_device = 0.0f;
+  std::vector<std::string> terms;
+  const int prc = positive_terms(q, q_len, &terms);
+  if (prc == kQBadUtf8) return fail(TFIDF_E_UNSUPPORTED_QUERY, "query is not valid UTF-8");
+  if (prc == kQSyntax)
+    return fail(TFIDF_E_QUERY_SYNTAX, "query does not parse (QueryParser ParseException / TooManyClauses)");
+  if (n > (1ull << 26)) return fail(TFIDF_E_INVALID_ARG, "more than 2^26 documents in one call");
+  for (uint64_t i = 0; i < n; i++)
+    if (docs[i] >= S.n_docs) return fail(TFIDF_E_INVALID_ARG, "doc %u out of range", docs[i]);
+  for (uint64_t i = 0; i <= n; i++) {
+    o.match_offsets[i] = 0;
+    if (o.W) o.text_offsets[i] = 0;
+  }
+  *o.n_matches = 0;
+  if (o.W) *o.n_text = 0;
+  if (n == 0) return TFIDF_OK;
+
+  CtxLease lease(ix);
+  if (lease.rc) return lease.rc;
+  SearchCtx &X = *lease.c;
+  const hipStream_t s = lease.stream();
+  DeviceGuard g(ix->cfg.device);
+  const bool timed = o.ms_device != nullptr;
+  // ends the timed span and waits for everything queued
+  auto finish = [&]() -> int {
+    if (timed) HIP_TRY(hipEventRecord(X.ev[QEV_1], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (timed) HIP_TRY(hipEventElapsedTime(o.ms_device, X.ev[QEV_0], X.ev[QEV_1]));
+    return TFIDF_OK;
+  };
+
+  // the positive terms this snapshot holds: dictionary keys (under its hash seed) with their ordinals
+  std::vector<HlKey> keys;
+  for (size_t t = 0; t < terms.size(); t++) {
+    const uint32_t slot = lookup_term(S, terms[t]);
+    if (slot != kInvalidSlot) keys.push_back(HlKey{S.h_dict[slot], S.h_dict[(size_t)S.C + slot], (uint32_t)t, 0});
+  }
+  std::sort(keys.begin(), keys.end(), [](const HlKey &x, const HlKey &y) { return hl_key_less(x, y); });
+
+  // document extents: one gather, one copy back (the plan and the sizes need them)
+  std::vector<uint32_t> h_staged(n);
+  for (uint64_t i = 0; i < n; i++) h_staged[i] = (uint32_t)S.staged_of(docs[i]);
+  std::vector<uint64_t> h_ext(2 * n);
+  HIP_TRY(X.hl_in.reserve(up16(n * 4) + n * 16));
+  uint32_t *d_staged = X.hl_in.as<uint32_t>();
+  uint64_t *d_ext = reinterpret_cast<uint64_t *>(X.hl_in.as<uint8_t>() + up16(n * 4));
+  const uint8_t *d_text = S.text->as<uint8_t>();
+  if (timed) HIP_TRY(hipEventRecord(X.ev[QEV_0], s));
+  HIP_TRY(hipMemcpyAsync(d_staged, h_staged.data(), n * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_hl_extents(S.offsets->as<uint64_t>(), d_staged, n, d_ext, s));
+  HIP_TRY(hipMemcpyAsync(h_ext.data(), d_ext, n * 16, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+
+  // the (row, chunk) work items; nothing to scan for a malformed document
+  // (indexed empty) or when the snapshot holds none of the terms
+  std::vector<uint8_t> skip(n, keys.empty() ? 1 : 0);
+  if (!keys.empty() && !S.malformed.empty())
+    for (uint64_t i = 0; i < n; i++) skip[i] = std::binary_search(S.malformed.begin(), S.malformed.end(), docs[i]);
+  std::vector<HlItem> items;
+  std::vector<uint64_t> first;
+  hl_plan(h_ext.data(), skip.data(), n, &items, &first);
+  if (items.size() > (1ull << 24))
+    return fail(TFIDF_E_INVALID_ARG, "more than 2^24 chunks of %llu bytes in one call",
+                (unsigned long long)kHlChunkBytes);
+  const uint32_t n_items = (uint32_t)items.size(), n_keys = (uint32_t)keys.size();
+  const uint64_t n_cnt = (uint64_t)n_items * kHlLanes;
+  const size_t off_row = (n + 1) * 8, off_keys = 2 * off_row, off_items = off_keys + (size_t)n_keys * sizeof(HlKey),
+               off_counts = up16(off_items + (size_t)n_items * sizeof(HlItem));
+  HIP_TRY(X.hl_cnt.reserve(off_counts + (n_cnt + 1) * 8));
+  uint8_t *cb = X.hl_cnt.as<uint8_t>();
+  uint64_t *d_first = reinterpret_cast<uint64_t *>(cb), *d_row = reinterpret_cast<uint64_t *>(cb + off_row),
+           *d_counts = reinterpret_cast<uint64_t *>(cb + off_counts);
+  HlKey *d_keys = reinterpret_cast<HlKey *>(cb + off_keys);
+  HlItem *d_items = reinterpret_cast<HlItem *>(cb + off_items);
+  std::vector<uint64_t> h_row(n + 1, 0);
+  if (n_items) {
+    HIP_TRY(hipMemcpyAsync(d_first, first.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_keys, keys.data(), (size_t)n_keys * sizeof(HlKey), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_items, items.data(), (size_t)n_items * sizeof(HlItem), hipMemcpyHostToDevice, s));
+    // count per slice, scan, row offsets: the totals are known before any match is stored
+    HIP_TRY(launch_hl_scan(false, d_text, d_ext, d_items, n_items, d_keys, n_keys, S.hash_seed, d_counts, nullptr,
+                           nullptr, nullptr, s));
+    HIP_TRY(exclusive_scan_u64(d_counts, d_counts, n_cnt, s));
+    HIP_TRY(launch_hl_row_offsets(d_counts, d_first, n, d_row, s));
+    HIP_TRY(hipMemcpyAsync(h_row.data(), d_row, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+  } else {
+    HIP_TRY(hipMemsetAsync(d_row, 0, (n + 1) * 8, s));
+  }
+  const uint64_t T = h_row[n];
+
+  if (!o.W) {
+    memcpy(o.match_offsets, h_row.data(), (n + 1) * 8);
+    *o.n_matches = T;
+    if (T > o.m_cap || (T && (!o.starts || !o.lens || !o.ordinals))) {
+      if (int rc = finish()) return rc;
+      return fail(TFIDF_E_BUFFER, "need %llu match slots", (unsigned long long)T);
+    }
+    if (T) {
+      HIP_TRY(X.hl_m.reserve(T * 16));
+      uint64_t *m_st = X.hl_m.as<uint64_t>();
+      uint32_t *m_ln = reinterpret_cast<uint32_t *>(m_st + T), *m_od = m_ln + T;
+      HIP_TRY(launch_hl_scan(true, d_text, d_ext, d_items, n_items, d_keys, n_keys, S.hash_seed, d_counts, m_st, m_ln,
+                             m_od, s));
+      HIP_TRY(hipMemcpyAsync(o.starts, m_st, T * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(o.lens, m_ln, T * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(o.ordinals, m_od, T * 4, hipMemcpyDeviceToHost, s));
+    }
+    return finish();
+  }
+
+  // snippets: all matches of the documents stay on the device; only the
+  // packed snippets, their offsets and the matches inside them come back
+  uint64_t text_bound = 0;
+  for (uint64_t i = 0; i < n; i++) text_bound += std::min<uint64_t>(h_ext[2 * i + 1] - h_ext[2 * i], o.W);
+  HIP_TRY(X.hl_m.reserve(std::max<uint64_t>(T, 1) * 16));
+  HIP_TRY(X.hl_s.reserve((4 * n + 2) * 8));
+  HIP_TRY(X.hl_o.reserve(std::max<uint64_t>(T, 1) * 16 + text_bound + 16));
+  uint64_t *m_st = X.hl_m.as<uint64_t>();
+  uint32_t *m_ln = reinterpret_cast<uint32_t *>(m_st + std::max<uint64_t>(T, 1)), *m_od = m_ln + std::max<uint64_t>(T, 1);
+  uint64_t *sn_a = X.hl_s.as<uint64_t>(), *sn_len = sn_a + n, *in_first = sn_len + n + 1, *in_cnt = in_first + n;
+  uint64_t *o_st = X.hl_o.as<uint64_t>();
+  uint32_t *o_ln = reinterpret_cast<uint32_t *>(o_st + std::max<uint64_t>(T, 1)), *o_od = o_ln + std::max<uint64_t>(T, 1);
+  uint8_t *o_text = reinterpret_cast<uint8_t *>(o_od + std::max<uint64_t>(T, 1));
+  if (T)
+    HIP_TRY(launch_hl_scan(true, d_text, d_ext, d_items, n_items, d_keys, n_keys, S.hash_seed, d_counts, m_st, m_ln,
+                           m_od, s));
+  HIP_TRY(launch_hl_rank(d_text, d_ext, d_row, m_st, m_ln, m_od, o.W, n, sn_a, sn_len, in_first, in_cnt, s));
+  HIP_TRY(exclusive_scan_u64(sn_len, sn_len, n, s));
+  HIP_TRY(exclusive_scan_u64(in_cnt, in_cnt, n, s));
+  HIP_TRY(launch_hl_pack(d_text, d_ext, sn_a, sn_len, o_text, m_st, m_ln, m_od, in_first, in_cnt, o_st, o_ln, o_od, n,
+                         s));
+  HIP_TRY(hipMemcpyAsync(o.text_offsets, sn_len, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(o.match_offsets, in_cnt, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(o.doc_starts, sn_a, n * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const uint64_t nt = o.text_offsets[n], nm = o.match_offsets[n];
+  *o.n_text = nt;
+  *o.n_matches = nm;
+  if (nt > o.text_cap || nm > o.m_cap || (nt && !o.text) || (nm && (!o.starts || !o.lens || !o.ordinals))) {
+    if (int rc = finish()) return rc;
+    return fail(TFIDF_E_BUFFER, "need %llu text bytes and %llu match slots", (unsigned long long)nt,
+                (unsigned long long)nm);
+  }
+  if (nt) HIP_TRY(hipMemcpyAsync(o.text, o_text, nt, hipMemcpyDeviceToHost, s));
+  if (nm) {
+    HIP_TRY(hipMemcpyAsync(o.starts, o_st, nm * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(o.lens, o_ln, nm * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(o.ordinals, o_od, nm * 4, hipMemcpyDeviceToHost, s));
+  }
+  return finish();
+}
+
+static int matches_on(tfidf_index *ix, Snapshot &S, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
+                      uint64_t n_docs, uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t cap,
+                      uint64_t *match_offsets, uint64_t *n_out, float *ms_device) {
+  if ((!q && q_len) || (!docs && n_docs) || !match_offsets || !n_out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  HlOut o;
+  o.starts = starts;
+  o.lens = lens;
+  o.ordinals = ordinals;
+  o.m_cap = cap;
+  o.match_offsets = match_offsets;
+  o.n_matches = n_out;
+  o.ms_device = ms_device;
+  return highlight_on(ix, S, q, q_len, docs, n_docs, o);
+}
+
+static int snippets_on(tfidf_index *ix, Snapshot &S, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
+                       uint64_t n_docs, uint32_t max_bytes, uint8_t *text, uint64_t text_cap, uint64_t *text_offsets,
+                       uint64_t *doc_starts, uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t m_cap,
+                       uint64_t *match_offsets, uint64_t *n_text, uint64_t *n_matches, float *ms_device) {
+  if ((!q && q_len) || (!docs && n_docs) || !text_offsets || (!doc_starts && n_docs) || !match_offsets || !n_text ||
+      !n_matches)
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (max_bytes < kHlMinBytes || max_bytes > kHlMaxBytes)
+    return fail(TFIDF_E_INVALID_ARG, "max_bytes %u outside %u..%u", max_bytes, kHlMinBytes, kHlMaxBytes);
+  HlOut o;
+  o.W = max_bytes;
+  o.text = text;
+  o.text_cap = text_cap;
+  o.text_offsets = text_offsets;
+  o.doc_starts = doc_starts;
+  o.n_text = n_text;
+  o.starts = starts;
+  o.lens = lens;
+  o.ordinals = ordinals;
+  o.m_cap = m_cap;
+  o.match_offsets = match_offsets;
+  o.n_matches = n_matches;
+  o.ms_device = ms_device;
+  return highlight_on(ix, S, q, q_len, docs, n_docs, o);
+}
+
+extern "C" int tfidf_reader_matches(tfidf_reader *rd, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
+                                    uint64_t n_docs, uint64_t *starts, uint32_t *lens, uint32_t *ordinals,
+                                    uint64_t cap, uint64_t *match_offsets, uint64_t *n_out, float *ms_device) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  return matches_on(rd->ix, *rd->S, q, q_len, docs, n_docs, starts, lens, ordinals, cap, match_offsets, n_out,
+                    ms_device);
+}
+
+extern "C" int tfidf_matches(tfidf_index *ix, const uint8_t *q, uint64_t q_len, const uint32_t *docs, uint64_t n_docs,
+                             uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t cap,
+                             uint64_t *match_offsets, uint64_t *n_out, float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "matches before commit");
+  return matches_on(ix, *snap, q, q_len, docs, n_docs, starts, lens, ordinals, cap, match_offsets, n_out, ms_device);
+}
+
+extern "C" int tfidf_reader_snippets(tfidf_reader *rd, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
+                                     uint64_t n_docs, uint32_t max_bytes, uint8_t *text, uint64_t text_cap,
+                                     uint64_t *text_offsets, uint64_t *doc_starts, uint64_t *starts, uint32_t *lens,
+                                     uint32_t *ordinals, uint64_t m_cap, uint64_t *match_offsets, uint64_t *n_text,
+                                     uint64_t *n_matches, float *ms_device) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  return snippets_on(rd->ix, *rd->S, q, q_len, docs, n_docs, max_bytes, text, text_cap, text_offsets, doc_starts,
+                     starts, lens, ordinals, m_cap, match_offsets, n_text, n_matches, ms_device);
+}
+
+extern "C" int tfidf_snippets(tfidf_index *ix, const uint8_t *q, uint64_t q_len, const uint32_t *docs, uint64_t n_docs,
+                              uint32_t max_bytes, uint8_t *text, uint64_t text_cap, uint64_t *text_offsets,
+                              uint64_t *doc_starts, uint64_t *starts, uint32_t *lens, uint32_t *ordinals,
+                              uint64_t m_cap, uint64_t *match_offsets, uint64_t *n_text, uint64_t *n_matches,
+                              float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "snippets before commit");
+  return snippets_on(ix, *snap, q, q_len, docs, n_docs, max_bytes, text, text_cap, text_offsets, doc_starts, starts,
+                     lens, ordinals, m_cap, match_offsets, n_text, n_matches, ms_device);
+}
+
+extern "C" int tfidf_query_positive_terms(const uint8_t *q, uint64_t q_len, char *out, uint64_t cap, uint64_t *n_terms,
+                                          uint64_t *n_bytes) {
+  if ((!q && q_len) || !n_terms || !n_bytes || (!out && cap)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::vector<std::string> terms;
+  const int prc = positive_terms(q, q_len, &terms);
+  if (prc == kQBadUtf8) return fail(TFIDF_E_UNSUPPORTED_QUERY, "query is not valid UTF-8");
+  if (prc == kQSyntax)
+    return fail(TFIDF_E_QUERY_SYNTAX, "query does not parse (QueryParser ParseException / TooManyClauses)");
+  uint64_t need = 0;
+  for (auto &t : terms) need += t.size() + 1;
+  *n_terms = terms.size();
+  *n_bytes = need;
+  if (need > cap) return fail(TFIDF_E_BUFFER, "buffer too small");
+  uint64_t p = 0;
+  for (auto &t : terms) {
+    memcpy(out + p, t.data(), t.size());
+    out[p + t.size()] = 0;
+    p += t.size() + 1;
+  }
+  return TFIDF_OK;
 }
 
 extern "C" int tfidf_search_batch(tfidf_index *ix, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,

@@ -95,6 +95,15 @@ SIGNATURES = {
     "tfidf_set_compact_threshold": (C.c_int, [VP, C.c_uint32]),
     "tfidf_doc_text": (C.c_int, [VP, C.c_uint64, VP, C.c_uint64, U64P]),
     "tfidf_reader_doc_text": (C.c_int, [VP, C.c_uint64, VP, C.c_uint64, U64P]),
+    "tfidf_reader_matches": (C.c_int, [VP, C.c_char_p, C.c_uint64, U32P, C.c_uint64, U64P, U32P, U32P, C.c_uint64,
+                                       U64P, U64P, F32P]),
+    "tfidf_matches": (C.c_int, [VP, C.c_char_p, C.c_uint64, U32P, C.c_uint64, U64P, U32P, U32P, C.c_uint64, U64P,
+                                U64P, F32P]),
+    "tfidf_reader_snippets": (C.c_int, [VP, C.c_char_p, C.c_uint64, U32P, C.c_uint64, C.c_uint32, VP, C.c_uint64,
+                                        U64P, U64P, U64P, U32P, U32P, C.c_uint64, U64P, U64P, U64P, F32P]),
+    "tfidf_snippets": (C.c_int, [VP, C.c_char_p, C.c_uint64, U32P, C.c_uint64, C.c_uint32, VP, C.c_uint64, U64P,
+                                 U64P, U64P, U32P, U32P, C.c_uint64, U64P, U64P, U64P, F32P]),
+    "tfidf_query_positive_terms": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, U64P, U64P]),
     "tfidf_set_hash_attempt": (C.c_int, [VP, C.c_uint32]),
     "tfidf_get_commit_timing": (C.c_int, [VP, C.POINTER(CommitTiming)]),
     "tfidf_stats": (C.c_int, [VP, C.POINTER(IndexStats)]),

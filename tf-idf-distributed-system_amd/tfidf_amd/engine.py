@@ -68,6 +68,85 @@ def _doc_text(fn, handle, doc):
     return buf.raw[:n.value]
 
 
+def query_positive_terms(q: bytes):
+    """Positive terms of a query in ordinal order (tfidf_query_positive_terms):
+    the analysed terms of every clause that is not MUST_NOT, distinct, by first
+    appearance.  The ordinals of matches index this list."""
+    cap = 2 * len(q) + 64
+    buf = C.create_string_buffer(cap)
+    nt, nb = C.c_uint64(), C.c_uint64()
+    L.check(L.load().tfidf_query_positive_terms(q, len(q), buf, cap, C.byref(nt), C.byref(nb)))
+    return buf.raw[:nb.value].split(b"\0")[:nt.value]
+
+
+def _doc_array(docs):
+    return np.ascontiguousarray(docs, dtype=np.uint32).reshape(-1)
+
+
+def _match_lists(starts, lens, ords, offs):
+    s, l, o, f = starts.tolist(), lens.tolist(), ords.tolist(), offs.tolist()
+    return [list(zip(s[f[i]:f[i + 1]], l[f[i]:f[i + 1]], o[f[i]:f[i + 1]])) for i in range(len(f) - 1)]
+
+
+def _matches_arrays(fn, handle, query, docs, cap=None):
+    """tfidf_matches / tfidf_reader_matches: one call with ``cap`` match slots,
+    and once more with the size the library reports when that was too small.
+    -> (starts uint64[], lens uint32[], ordinals uint32[], offsets uint64[n + 1], ms_device)."""
+    d = _doc_array(docs)
+    n = len(d)
+    offs = np.zeros(n + 1, np.uint64)
+    total, ms = C.c_uint64(), C.c_float()
+    cap = 64 * max(n, 1) if cap is None else cap
+    for _ in range(2):
+        st = np.empty(max(cap, 1), np.uint64)
+        ln = np.empty(max(cap, 1), np.uint32)
+        od = np.empty(max(cap, 1), np.uint32)
+        rc = fn(handle, query, len(query), L.ptr(d, C.c_uint32), n, L.ptr(st, C.c_uint64), L.ptr(ln, C.c_uint32),
+                L.ptr(od, C.c_uint32), cap, L.ptr(offs, C.c_uint64), C.byref(total), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        cap = total.value
+    L.check(rc)
+    m = total.value
+    return st[:m], ln[:m], od[:m], offs, ms.value
+
+
+def _snippets_arrays(fn, handle, query, docs, max_bytes, m_cap=None):
+    """tfidf_snippets / tfidf_reader_snippets: the text buffer is sized in
+    advance (n x max_bytes), the match buffers once more when too small.
+    -> (text bytes, text offsets, doc_starts, starts, lens, ordinals, match offsets, ms_device)."""
+    d = _doc_array(docs)
+    n = len(d)
+    t_cap = n * min(max(int(max_bytes), 0), 65536)
+    text = np.empty(max(t_cap, 1), np.uint8)
+    t_offs = np.zeros(n + 1, np.uint64)
+    m_offs = np.zeros(n + 1, np.uint64)
+    d_starts = np.zeros(max(n, 1), np.uint64)
+    nt, nm, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+    m_cap = 16 * max(n, 1) if m_cap is None else m_cap
+    for _ in range(2):
+        st = np.empty(max(m_cap, 1), np.uint64)
+        ln = np.empty(max(m_cap, 1), np.uint32)
+        od = np.empty(max(m_cap, 1), np.uint32)
+        rc = fn(handle, query, len(query), L.ptr(d, C.c_uint32), n, max_bytes, text.ctypes.data_as(C.c_void_p), t_cap,
+                L.ptr(t_offs, C.c_uint64), L.ptr(d_starts, C.c_uint64), L.ptr(st, C.c_uint64),
+                L.ptr(ln, C.c_uint32), L.ptr(od, C.c_uint32), m_cap, L.ptr(m_offs, C.c_uint64), C.byref(nt),
+                C.byref(nm), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        m_cap = nm.value
+    L.check(rc)
+    return (text[:nt.value].tobytes(), t_offs, d_starts[:n], st[:nm.value], ln[:nm.value], od[:nm.value], m_offs,
+            ms.value)
+
+
+def _snippet_lists(arrays):
+    text, t_offs, d_starts, st, ln, od, m_offs, _ = arrays
+    t = t_offs.tolist()
+    ms = _match_lists(st, ln, od, m_offs)
+    return [(int(d_starts[i]), text[t[i]:t[i + 1]], ms[i]) for i in range(len(t) - 1)]
+
+
 def _hit_lists(docs, scores, offs):
     d, s, o = docs.tolist(), scores.tolist(), offs.tolist()
     return [list(zip(d[o[i]:o[i + 1]], s[o[i]:o[i + 1]])) for i in range(len(o) - 1)]
@@ -174,6 +253,18 @@ class ShardIndex:
     def doc_text(self, doc):
         """The committed document's bytes as they were added."""
         return _doc_text(L.load().tfidf_doc_text, self._h, doc)
+
+    def matches(self, query: bytes, docs):
+        """Per document of ``docs``: [(start, len, ordinal)] of the tokens that
+        are positive terms of ``query``, in document bytes, on the snapshot
+        published now (tfidf_matches)."""
+        return _match_lists(*_matches_arrays(L.load().tfidf_matches, self._h, query, docs)[:4])
+
+    def snippets(self, query: bytes, docs, max_bytes=160):
+        """Per document of ``docs``: (doc_start, snippet bytes, [(start, len,
+        ordinal)] in snippet bytes) — the passage of at most ``max_bytes``
+        bytes with the most distinct query terms (tfidf_snippets)."""
+        return _snippet_lists(_snippets_arrays(L.load().tfidf_snippets, self._h, query, docs, max_bytes))
 
     def set_hash_attempt(self, attempt):
         """Seed attempt (0..3) the following commits start from (tfidf_set_hash_attempt)."""
@@ -492,6 +583,20 @@ class Reader:
     def doc_text(self, doc):
         """The document's bytes in this reader's snapshot."""
         return _doc_text(L.load().tfidf_reader_doc_text, self._h, doc)
+
+    def matches_arrays(self, query: bytes, docs, cap=None):
+        return _matches_arrays(L.load().tfidf_reader_matches, self._h, query, docs, cap)
+
+    def matches(self, query: bytes, docs):
+        """ShardIndex.matches on this reader's snapshot."""
+        return _match_lists(*self.matches_arrays(query, docs)[:4])
+
+    def snippets_arrays(self, query: bytes, docs, max_bytes=160, m_cap=None):
+        return _snippets_arrays(L.load().tfidf_reader_snippets, self._h, query, docs, max_bytes, m_cap)
+
+    def snippets(self, query: bytes, docs, max_bytes=160):
+        """ShardIndex.snippets on this reader's snapshot."""
+        return _snippet_lists(self.snippets_arrays(query, docs, max_bytes))
 
     def doc_keys(self):
         lib = L.load()

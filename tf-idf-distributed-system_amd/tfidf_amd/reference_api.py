@@ -146,6 +146,24 @@ class Worker:
             hits = rd.search(query.encode(), 0)
             return [document_score_info(rd.doc_key(d).decode(), s) for d, s in hits]
 
+    # No reference counterpart ("contents" is stored with Store.NO,
+    # Worker.java:216): the top-k hits with the passage that shows why each
+    # matched, search and snippets on one reader.  DocumentScoreInfo JSON
+    # extended with "snippet" (str) and "matches" ([[start, len], ...] in
+    # snippet bytes).
+    def search_snippets(self, query: str, k=10, max_bytes=160):
+        q = query.encode()
+        with self.index.reader() as rd:
+            hits = rd.search(q, k)
+            snips = rd.snippets(q, [d for d, _ in hits], max_bytes)
+            out = []
+            for (d, s), (_, text, ms) in zip(hits, snips):
+                info = document_score_info(rd.doc_key(d).decode(), s)
+                info["snippet"] = text.decode("utf-8", errors="replace")
+                info["matches"] = [[st, ln] for st, ln, _ in ms]
+                out.append(info)
+            return out
+
     # Worker.java:175-186 /worker/process: any exception -> empty list
     def process_documents(self, search_query: str):
         try:
