@@ -379,6 +379,56 @@ int tfidf_snippets(tfidf_index *ix, const uint8_t *q, uint64_t q_len, const uint
                    uint64_t *n_text, uint64_t *n_matches, float *ms_device);
 int tfidf_query_positive_terms(const uint8_t *q, uint64_t q_len, char *out, uint64_t cap, uint64_t *n_terms,
                                uint64_t *n_bytes);
+/* ---- batched hit highlighting: the rows of many queries in one call ----
+ * A row is one (query, document) pair.  The n_q queries come as in
+ * tfidf_search_batch_all (q_utf8, q_offsets[n_q + 1]); their documents in CSR
+ * form: query i owns rows [doc_offsets[i], doc_offsets[i + 1]) of docs, R =
+ * doc_offsets[n_q].  This is the layout tfidf_search_batch_all writes
+ * (hit_offsets, doc_ids), so its output, or any per-query prefix of it, can be
+ * passed on.  Rows may repeat documents within and across queries; a query may
+ * own no row; n_q == 0 or R == 0: OK, offsets {0}.
+ * Row r's matches and snippet are exactly what tfidf_matches / tfidf_snippets
+ *   return for (its query, docs[r]) on the same snapshot: the positive terms
+ *   and ordinals of that query, the match triples, the passage rule, the UTF-8
+ *   snapping and the in-snippet matches.  All output offset arrays have R + 1
+ *   entries; doc_starts has R.
+ * A query that does not parse, or is not valid UTF-8, does not fail the batch
+ *   (the convention of tfidf_search_batch[_all]: it has no hits): its rows have
+ *   no matches and get head-of-document snippets, as a query with no positive
+ *   term present does.
+ * TFIDF_E_INVALID_ARG, nothing written: doc_offsets not non-decreasing from 0,
+ *   a doc >= num_docs, R > 2^26, max_bytes outside 16..65536.
+ * Buffer protocol of the single form: offsets, doc_starts and totals are
+ *   always written in full, also when a payload cap is too small
+ *   (TFIDF_E_BUFFER); cap 0 with NULL payload pointers asks for the sizes.
+ * One call costs one chain of launches and synchronisations, not one per
+ *   query.  Scratch is bounded: the rows are processed in consecutive chunks
+ *   under a budget of 2^16 planned (row, 16 KiB) items and 2^22 matches (one
+ *   row at least), each chunk appending its payload at the running totals.
+ * The calls run on a search context beside readers, tfidf_add_docs and
+ *   tfidf_commit; tfidf_matches_batch / tfidf_snippets_batch use the snapshot
+ *   published at the call.  *ms_device as in the single form. */
+int tfidf_reader_matches_batch(tfidf_reader *rd, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                               const uint32_t *docs, const uint64_t *doc_offsets, uint64_t *starts, uint32_t *lens,
+                               uint32_t *ordinals, uint64_t cap, uint64_t *match_offsets, uint64_t *n_out,
+                               float *ms_device);
+int tfidf_reader_snippets_batch(tfidf_reader *rd, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                                const uint32_t *docs, const uint64_t *doc_offsets, uint32_t max_bytes, uint8_t *text,
+                                uint64_t text_cap, uint64_t *text_offsets, uint64_t *doc_starts, uint64_t *starts,
+                                uint32_t *lens, uint32_t *ordinals, uint64_t m_cap, uint64_t *match_offsets,
+                                uint64_t *n_text, uint64_t *n_matches, float *ms_device);
+int tfidf_matches_batch(tfidf_index *ix, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                        const uint32_t *docs, const uint64_t *doc_offsets, uint64_t *starts, uint32_t *lens,
+                        uint32_t *ordinals, uint64_t cap, uint64_t *match_offsets, uint64_t *n_out, float *ms_device);
+int tfidf_snippets_batch(tfidf_index *ix, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                         const uint32_t *docs, const uint64_t *doc_offsets, uint32_t max_bytes, uint8_t *text,
+                         uint64_t text_cap, uint64_t *text_offsets, uint64_t *doc_starts, uint64_t *starts,
+                         uint32_t *lens, uint32_t *ordinals, uint64_t m_cap, uint64_t *match_offsets,
+                         uint64_t *n_text, uint64_t *n_matches, float *ms_device);
+/* Row chunks of the last batched highlighting call that ran on this index
+ * (any form): the chunks the item budget cut, and the final chunks after the
+ * match budget cut those further (1, 1 when everything fitted). */
+int tfidf_last_highlight_chunks(const tfidf_index *ix, uint64_t *item_chunks, uint64_t *row_chunks);
 /* Per-query device time of the last search call on this index (HIP events on the search's stream). */
 int tfidf_last_search_ms(const tfidf_index *ix, float *ms_scoring, float *ms_total);
 /* Device-time measurement of searches (HIP events around scoring; on by
@@ -718,6 +768,25 @@ int tfidf_node_last_names_batch(const tfidf_node *n, uint8_t *buf, uint64_t cap,
 int tfidf_node_last_failed(const tfidf_node *n, uint64_t *shard_mask);
 /* Global doc id -> its document key (Worker.java:235-236, across shards). */
 int tfidf_node_doc_key(tfidf_node *n, uint64_t doc, uint8_t *buf, uint64_t cap, uint64_t *n_out);
+/* tfidf_matches_batch / tfidf_snippets_batch over the node: docs are global
+ * doc ids (what the node's searches return).  After tfidf_node_commit, in
+ * either statistics mode.  Each row is routed to its shard as
+ * tfidf_node_doc_key routes it; every shard runs one batch of its own rows
+ * (query grouping and order kept) at once, and the results come back in the
+ * caller's row order with the offsets recomputed.  A global id >= the node's
+ * num_docs: TFIDF_E_INVALID_ARG, nothing written.  A shard's failure fails the
+ * call with that shard's code (no partial answer).  Everything else (results,
+ * queries that do not parse, buffer protocol) as in the single-index batch
+ * form; *ms_device is the largest of the shards' device times. */
+int tfidf_node_matches_batch(tfidf_node *n, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                             const uint64_t *docs, const uint64_t *doc_offsets, uint64_t *starts, uint32_t *lens,
+                             uint32_t *ordinals, uint64_t cap, uint64_t *match_offsets, uint64_t *n_out,
+                             float *ms_device);
+int tfidf_node_snippets_batch(tfidf_node *n, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                              const uint64_t *docs, const uint64_t *doc_offsets, uint32_t max_bytes, uint8_t *text,
+                              uint64_t text_cap, uint64_t *text_offsets, uint64_t *doc_starts, uint64_t *starts,
+                              uint32_t *lens, uint32_t *ordinals, uint64_t m_cap, uint64_t *match_offsets,
+                              uint64_t *n_text, uint64_t *n_matches, float *ms_device);
 typedef struct tfidf_node_stats {
   uint64_t n_shards;
   uint64_t num_docs;      /* all shards */

@@ -221,4 +221,39 @@ inline uint64_t hl_plan(const uint64_t *ext, const uint8_t *skip, uint64_t n, st
   return bytes;
 }
 
+// --- batches: many queries, each with its own rows ---
+// The present positive terms of all queries are one HlKey array: query q's
+// keys are the segment [key_off[q], key_off[q + 1]), sorted by hl_key_less on
+// its own (two queries may give one term different ordinals), and row r is
+// scanned against the segment of its query row_q[r].
+TFIDF_HD void hl_segment(const HlKey *keys, const uint32_t *key_off, uint32_t q, const HlKey **seg, uint32_t *n) {
+  *seg = keys + key_off[q];
+  *n = key_off[q + 1] - key_off[q];
+}
+
+// Row chunks of a batch.  Scratch is bounded by two budgets: the (row, chunk)
+// items of a chunk (known from the extents: they size the slice counts) and
+// its matches (known after the count pass: they size the match arrays).
+// Rows [r0, r1) are cut greedily into consecutive ranges: a range takes the
+// next row while both sums stay within their budgets, and always takes one
+// row, so a single row above a budget is a range of its own.  items / matches
+// are per row, indexed from 0 (either may be null: not counted).  Appends the
+// cut points to *cuts: r0, ..., r1 (only r0 when r0 == r1), ascending; range k
+// is [cuts[k], cuts[k + 1]).
+inline void hl_plan_chunks(const uint64_t *items, const uint64_t *matches, uint64_t r0, uint64_t r1,
+                           uint64_t budget_items, uint64_t budget_matches, std::vector<uint64_t> *cuts) {
+  cuts->push_back(r0);
+  uint64_t si = 0, sm = 0;
+  for (uint64_t r = r0; r < r1; r++) {
+    const uint64_t ni = items ? items[r] : 0, nm = matches ? matches[r] : 0;
+    if (r > cuts->back() && (si + ni > budget_items || sm + nm > budget_matches)) {
+      cuts->push_back(r);
+      si = sm = 0;
+    }
+    si += ni;     // a first row above a budget leaves its sum above it: the next row starts a range
+    sm += nm;
+  }
+  if (r1 > r0) cuts->push_back(r1);
+}
+
 }  // namespace tfidf

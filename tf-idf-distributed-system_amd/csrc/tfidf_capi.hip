@@ -46,6 +46,12 @@ hipError_t launch_hl_extents(const uint64_t *offsets, const uint32_t *staged, ui
 hipError_t launch_hl_scan(bool fill, const uint8_t *text, const uint64_t *ext, const HlItem *items, uint32_t n_items,
                           const HlKey *keys, uint32_t n_keys, uint64_t seed, uint64_t *counts, uint64_t *starts,
                           uint32_t *lens, uint32_t *ords, hipStream_t s);
+hipError_t launch_hl_scan_batch(bool fill, const uint8_t *text, const uint64_t *ext, const HlItem *items,
+                                uint32_t n_items, const HlKey *keys, const uint32_t *key_off, const uint32_t *row_q,
+                                uint64_t seed, uint64_t *counts, uint64_t m_base, uint64_t *starts, uint32_t *lens,
+                                uint32_t *ords, hipStream_t s);
+hipError_t launch_hl_row_offsets_rel(const uint64_t *scanned, const uint64_t *first, uint64_t n, uint64_t base,
+                                     uint64_t *row_off, hipStream_t s);
 hipError_t launch_hl_row_offsets(const uint64_t *scanned, const uint64_t *first, uint64_t n, uint64_t *row_off,
                                  hipStream_t s);
 hipError_t launch_hl_rank(const uint8_t *text, const uint64_t *ext, const uint64_t *row_off, const uint64_t *starts,
@@ -408,6 +414,7 @@ struct tfidf_index {
   std::atomic<bool> q_timing{true};  // record HIP events around each search (tfidf_set_query_timing)
   std::mutex ms_mu;
   float last_ms_scoring = 0, last_ms_total = 0;
+  uint64_t last_hl_item_chunks = 0, last_hl_row_chunks = 0;   // of the last batched highlighting call (ms_mu)
 
   // staged corpus (builder)
   std::shared_ptr<DevMem> text, offsets;   // offsets: u64[n_staged + 1]
@@ -2773,6 +2780,346 @@ extern "C" int tfidf_snippets(tfidf_index *ix, const uint8_t *q, uint64_t q_len,
   if (!snap) return fail(TFIDF_E_STATE, "snippets before commit");
   return snippets_on(ix, *snap, q, q_len, docs, n_docs, max_bytes, text, text_cap, text_offsets, doc_starts, starts,
                      lens, ordinals, m_cap, match_offsets, n_text, n_matches, ms_device);
+}
+
+// ---------------------------------------------------------------------------
+// batched hit highlighting: the rows (query, document) of many queries in one
+// call.  Row r's result is highlight_on's for (its query, docs[r]); the chain
+// of launches, copies and synchronisations is paid per call (per row chunk
+// when the scratch budgets cut the rows), never per query.
+
+static uint64_t hl_budget(const char *name, uint64_t dflt) {
+  if (const char *e = knob(name)) return (uint64_t)std::max<long long>(1, atoll(e));   // tests: chunk edges anywhere
+  return dflt;
+}
+
+constexpr uint64_t kHlChunkItems = 1ull << 16;     // (row, chunk) items per row chunk: 32 MiB of slice counts
+constexpr uint64_t kHlChunkMatches = 1ull << 22;   // matches per row chunk: 128 MiB over hl_m + hl_o
+
+static int highlight_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf8, const uint64_t *q_offsets,
+                              uint32_t n_q, const uint32_t *docs, const uint64_t *doc_offsets, const HlOut &o) {
+  if (o.ms_device) *o.ms_device = 0.0f;
+  if (doc_offsets[0] != 0) return fail(TFIDF_E_INVALID_ARG, "doc_offsets[0] is not 0");
+  for (uint32_t i = 0; i < n_q; i++) {
+    if (doc_offsets[i + 1] < doc_offsets[i]) return fail(TFIDF_E_INVALID_ARG, "doc_offsets decrease at query %u", i);
+    if (q_offsets[i + 1] < q_offsets[i]) return fail(TFIDF_E_INVALID_ARG, "q_offsets decrease at query %u", i);
+  }
+  const uint64_t R = doc_offsets[n_q];
+  if (R > (1ull << 26)) return fail(TFIDF_E_INVALID_ARG, "more than 2^26 rows in one call");
+  for (uint64_t r = 0; r < R; r++)
+    if (docs[r] >= S.n_docs) return fail(TFIDF_E_INVALID_ARG, "doc %u out of range", docs[r]);
+
+  // every query's present positive terms: one segment of keys each, sorted on
+  // its own; a query that does not parse has an empty segment (no matches)
+  std::vector<HlKey> keys;
+  std::vector<uint32_t> key_off((size_t)n_q + 1, 0), row_q(R);
+  std::vector<std::string> terms;
+  for (uint32_t i = 0; i < n_q; i++) {
+    key_off[i] = (uint32_t)keys.size();
+    for (uint64_t r = doc_offsets[i]; r < doc_offsets[i + 1]; r++) row_q[r] = i;
+    if (doc_offsets[i + 1] == doc_offsets[i]) continue;
+    terms.clear();
+    if (positive_terms(q_utf8 + q_offsets[i], q_offsets[i + 1] - q_offsets[i], &terms) != 0) continue;
+    for (size_t t = 0; t < terms.size(); t++) {
+      const uint32_t slot = lookup_term(S, terms[t]);
+      if (slot != kInvalidSlot) keys.push_back(HlKey{S.h_dict[slot], S.h_dict[(size_t)S.C + slot], (uint32_t)t, 0});
+    }
+    std::sort(keys.begin() + key_off[i], keys.end(), [](const HlKey &x, const HlKey &y) { return hl_key_less(x, y); });
+    if (keys.size() > (1ull << 31)) return fail(TFIDF_E_INVALID_ARG, "more than 2^31 query terms in one call");
+  }
+  key_off[n_q] = (uint32_t)keys.size();
+  const size_t n_keys = keys.size();
+  for (uint64_t r = 0; r <= R; r++) {
+    o.match_offsets[r] = 0;
+    if (o.W) o.text_offsets[r] = 0;
+  }
+  *o.n_matches = 0;
+  if (o.W) *o.n_text = 0;
+  if (R == 0) return TFIDF_OK;
+
+  CtxLease lease(ix);
+  if (lease.rc) return lease.rc;
+  SearchCtx &X = *lease.c;
+  const hipStream_t s = lease.stream();
+  DeviceGuard g(ix->cfg.device);
+  const bool timed = o.ms_device != nullptr;
+  auto finish = [&]() -> int {
+    if (timed) HIP_TRY(hipEventRecord(X.ev[QEV_1], s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (timed) HIP_TRY(hipEventElapsedTime(o.ms_device, X.ev[QEV_0], X.ev[QEV_1]));
+    return TFIDF_OK;
+  };
+
+  // the call's inputs on the device: staged ids, extents, row -> query, keys, key segments
+  std::vector<uint32_t> h_staged(R);
+  for (uint64_t r = 0; r < R; r++) h_staged[r] = (uint32_t)S.staged_of(docs[r]);
+  std::vector<uint64_t> h_ext(2 * R);
+  const size_t in_ext = up16(R * 4), in_rowq = in_ext + R * 16, in_koff = up16(in_rowq + R * 4),
+               in_keys = up16(in_koff + ((size_t)n_q + 1) * 4);
+  HIP_TRY(X.hl_in.reserve(in_keys + n_keys * sizeof(HlKey)));
+  uint8_t *ib = X.hl_in.as<uint8_t>();
+  uint32_t *d_staged = reinterpret_cast<uint32_t *>(ib), *d_rowq = reinterpret_cast<uint32_t *>(ib + in_rowq),
+           *d_koff = reinterpret_cast<uint32_t *>(ib + in_koff);
+  uint64_t *d_ext = reinterpret_cast<uint64_t *>(ib + in_ext);
+  HlKey *d_keys = reinterpret_cast<HlKey *>(ib + in_keys);
+  const uint8_t *d_text = S.text->as<uint8_t>();
+  if (timed) HIP_TRY(hipEventRecord(X.ev[QEV_0], s));
+  HIP_TRY(hipMemcpyAsync(d_staged, h_staged.data(), R * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(launch_hl_extents(S.offsets->as<uint64_t>(), d_staged, R, d_ext, s));
+  HIP_TRY(hipMemcpyAsync(h_ext.data(), d_ext, R * 16, hipMemcpyDeviceToHost, s));
+  if (n_keys) {
+    HIP_TRY(hipMemcpyAsync(d_rowq, row_q.data(), R * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_koff, key_off.data(), ((size_t)n_q + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_keys, keys.data(), n_keys * sizeof(HlKey), hipMemcpyHostToDevice, s));
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+
+  // rows without work: an empty key segment, a malformed document (indexed empty)
+  std::vector<uint8_t> skip(R);
+  std::vector<uint64_t> row_items(R);
+  for (uint64_t r = 0; r < R; r++) {
+    skip[r] = key_off[row_q[r]] == key_off[row_q[r] + 1] ||
+              (!S.malformed.empty() && std::binary_search(S.malformed.begin(), S.malformed.end(), docs[r]));
+    row_items[r] = skip[r] ? 0 : hl_num_chunks(h_ext[2 * r + 1] - h_ext[2 * r]);
+  }
+  std::vector<uint64_t> cuts;
+  hl_plan_chunks(row_items.data(), nullptr, 0, R, hl_budget("TFIDF_HL_CHUNK_ITEMS", kHlChunkItems), ~0ull, &cuts);
+  const uint64_t budget_m = hl_budget("TFIDF_HL_CHUNK_MATCHES", kHlChunkMatches);
+
+  uint64_t run_m = 0, run_t = 0;          // running totals: where the next chunk's payload goes
+  uint64_t n_row_chunks = 0;
+  bool fits = true;
+  std::vector<HlItem> items;
+  std::vector<uint64_t> first, h_row, row_m, sub, h_to, h_mo;
+  for (size_t ci = 0; ci + 1 < cuts.size(); ci++) {
+    const uint64_t r0 = cuts[ci], nr = cuts[ci + 1] - r0;
+    hl_plan(h_ext.data() + 2 * r0, skip.data() + r0, nr, &items, &first);
+    if (items.size() > (1ull << 24))
+      return fail(TFIDF_E_INVALID_ARG, "a document of more than 2^24 chunks of %llu bytes",
+                  (unsigned long long)kHlChunkBytes);
+    const uint32_t n_items = (uint32_t)items.size();
+    const uint64_t n_cnt = (uint64_t)n_items * kHlLanes;
+    const size_t off_row = (nr + 1) * 8, off_items = 3 * off_row,
+                 off_counts = up16(off_items + (size_t)n_items * sizeof(HlItem));
+    HIP_TRY(X.hl_cnt.reserve(off_counts + (n_cnt + 1) * 8));
+    uint8_t *cb = X.hl_cnt.as<uint8_t>();
+    uint64_t *d_first = reinterpret_cast<uint64_t *>(cb), *d_row = reinterpret_cast<uint64_t *>(cb + off_row),
+             *d_row_sub = reinterpret_cast<uint64_t *>(cb + 2 * off_row),
+             *d_counts = reinterpret_cast<uint64_t *>(cb + off_counts);
+    HlItem *d_items = reinterpret_cast<HlItem *>(cb + off_items);
+    h_row.assign(nr + 1, 0);
+    if (n_items) {
+      // count per slice, scan, row offsets: the chunk's totals before any match is stored
+      HIP_TRY(hipMemcpyAsync(d_first, first.data(), (nr + 1) * 8, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipMemcpyAsync(d_items, items.data(), (size_t)n_items * sizeof(HlItem), hipMemcpyHostToDevice, s));
+      HIP_TRY(launch_hl_scan_batch(false, d_text, d_ext + 2 * r0, d_items, n_items, d_keys, d_koff, d_rowq + r0,
+                                   S.hash_seed, d_counts, 0, nullptr, nullptr, nullptr, s));
+      HIP_TRY(exclusive_scan_u64(d_counts, d_counts, n_cnt, s));
+      HIP_TRY(launch_hl_row_offsets(d_counts, d_first, nr, d_row, s));
+      HIP_TRY(hipMemcpyAsync(h_row.data(), d_row, (nr + 1) * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+    } else {
+      HIP_TRY(hipMemsetAsync(d_row, 0, (nr + 1) * 8, s));
+    }
+    if (!o.W) {
+      for (uint64_t i = 1; i <= nr; i++) o.match_offsets[r0 + i] = run_m + h_row[i];
+      fits = fits && run_m + h_row[nr] <= o.m_cap && (!h_row[nr] || (o.starts && o.lens && o.ordinals));
+      if (!fits) {                          // the sizes alone from here on
+        run_m += h_row[nr];
+        n_row_chunks++;
+        continue;
+      }
+    }
+    // the rows of the item chunk by the match budget
+    row_m.resize(nr);
+    for (uint64_t i = 0; i < nr; i++) row_m[i] = h_row[i + 1] - h_row[i];
+    sub.clear();
+    hl_plan_chunks(nullptr, row_m.data(), 0, nr, ~0ull, budget_m, &sub);
+    for (size_t si = 0; si + 1 < sub.size(); si++) {
+      const uint64_t s0 = sub[si], ns = sub[si + 1] - s0, m_base = h_row[s0], T = h_row[s0 + ns] - m_base;
+      const uint64_t Tc = std::max<uint64_t>(T, 1);
+      n_row_chunks++;
+      const uint32_t i0 = (uint32_t)first[s0], ni = (uint32_t)first[s0 + ns] - i0;
+      HIP_TRY(X.hl_m.reserve(Tc * 16));
+      uint64_t *m_st = X.hl_m.as<uint64_t>();
+      uint32_t *m_ln = reinterpret_cast<uint32_t *>(m_st + Tc), *m_od = m_ln + Tc;
+      if (T)
+        HIP_TRY(launch_hl_scan_batch(true, d_text, d_ext + 2 * r0, d_items + i0, ni, d_keys, d_koff, d_rowq + r0,
+                                     S.hash_seed, d_counts + (uint64_t)i0 * kHlLanes, m_base, m_st, m_ln, m_od, s));
+      if (!o.W) {
+        if (T) {
+          HIP_TRY(hipMemcpyAsync(o.starts + run_m, m_st, T * 8, hipMemcpyDeviceToHost, s));
+          HIP_TRY(hipMemcpyAsync(o.lens + run_m, m_ln, T * 4, hipMemcpyDeviceToHost, s));
+          HIP_TRY(hipMemcpyAsync(o.ordinals + run_m, m_od, T * 4, hipMemcpyDeviceToHost, s));
+        }
+        run_m += T;
+        continue;
+      }
+      // snippets: the chunk's matches stay on the device; its packed snippets,
+      // offsets and in-snippet matches come back at the running totals
+      const uint64_t *d_ext_s = d_ext + 2 * (r0 + s0);
+      const uint64_t *d_row_s = d_row + s0;
+      if (m_base) {
+        HIP_TRY(launch_hl_row_offsets_rel(d_counts, d_first + s0, ns, m_base, d_row_sub, s));
+        d_row_s = d_row_sub;
+      }
+      uint64_t text_bound = 0;
+      for (uint64_t i = 0; i < ns; i++) {
+        const uint64_t r = r0 + s0 + i;
+        text_bound += std::min<uint64_t>(h_ext[2 * r + 1] - h_ext[2 * r], o.W);
+      }
+      HIP_TRY(X.hl_s.reserve((4 * ns + 2) * 8));
+      HIP_TRY(X.hl_o.reserve(Tc * 16 + text_bound + 16));
+      uint64_t *sn_a = X.hl_s.as<uint64_t>(), *sn_len = sn_a + ns, *in_first = sn_len + ns + 1, *in_cnt = in_first + ns;
+      uint64_t *o_st = X.hl_o.as<uint64_t>();
+      uint32_t *o_ln = reinterpret_cast<uint32_t *>(o_st + Tc), *o_od = o_ln + Tc;
+      uint8_t *o_text = reinterpret_cast<uint8_t *>(o_od + Tc);
+      HIP_TRY(launch_hl_rank(d_text, d_ext_s, d_row_s, m_st, m_ln, m_od, o.W, ns, sn_a, sn_len, in_first, in_cnt, s));
+      HIP_TRY(exclusive_scan_u64(sn_len, sn_len, ns, s));
+      HIP_TRY(exclusive_scan_u64(in_cnt, in_cnt, ns, s));
+      if (fits)
+        HIP_TRY(launch_hl_pack(d_text, d_ext_s, sn_a, sn_len, o_text, m_st, m_ln, m_od, in_first, in_cnt, o_st, o_ln,
+                               o_od, ns, s));
+      h_to.resize(ns + 1);
+      h_mo.resize(ns + 1);
+      HIP_TRY(hipMemcpyAsync(h_to.data(), sn_len, (ns + 1) * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(h_mo.data(), in_cnt, (ns + 1) * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(o.doc_starts + r0 + s0, sn_a, ns * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      for (uint64_t i = 1; i <= ns; i++) {
+        o.text_offsets[r0 + s0 + i] = run_t + h_to[i];
+        o.match_offsets[r0 + s0 + i] = run_m + h_mo[i];
+      }
+      const uint64_t nt = h_to[ns], nm = h_mo[ns];
+      fits = fits && run_t + nt <= o.text_cap && run_m + nm <= o.m_cap && (!nt || o.text) &&
+             (!nm || (o.starts && o.lens && o.ordinals));
+      if (fits) {
+        if (nt) HIP_TRY(hipMemcpyAsync(o.text + run_t, o_text, nt, hipMemcpyDeviceToHost, s));
+        if (nm) {
+          HIP_TRY(hipMemcpyAsync(o.starts + run_m, o_st, nm * 8, hipMemcpyDeviceToHost, s));
+          HIP_TRY(hipMemcpyAsync(o.lens + run_m, o_ln, nm * 4, hipMemcpyDeviceToHost, s));
+          HIP_TRY(hipMemcpyAsync(o.ordinals + run_m, o_od, nm * 4, hipMemcpyDeviceToHost, s));
+        }
+      }
+      run_t += nt;
+      run_m += nm;
+    }
+  }
+  *o.n_matches = run_m;
+  if (o.W) *o.n_text = run_t;
+  if (int rc = finish()) return rc;
+  {
+    std::lock_guard<std::mutex> lk(ix->ms_mu);
+    ix->last_hl_item_chunks = cuts.size() - 1;
+    ix->last_hl_row_chunks = n_row_chunks;
+  }
+  if (!fits) {
+    if (o.W)
+      return fail(TFIDF_E_BUFFER, "need %llu text bytes and %llu match slots", (unsigned long long)run_t,
+                  (unsigned long long)run_m);
+    return fail(TFIDF_E_BUFFER, "need %llu match slots", (unsigned long long)run_m);
+  }
+  return TFIDF_OK;
+}
+
+static int matches_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf8, const uint64_t *q_offsets,
+                            uint32_t n_q, const uint32_t *docs, const uint64_t *doc_offsets, uint64_t *starts,
+                            uint32_t *lens, uint32_t *ordinals, uint64_t cap, uint64_t *match_offsets, uint64_t *n_out,
+                            float *ms_device) {
+  if ((n_q && (!q_offsets || (!q_utf8 && q_offsets[n_q]))) || !doc_offsets || (!docs && doc_offsets[n_q]) ||
+      !match_offsets || !n_out)
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  HlOut o;
+  o.starts = starts;
+  o.lens = lens;
+  o.ordinals = ordinals;
+  o.m_cap = cap;
+  o.match_offsets = match_offsets;
+  o.n_matches = n_out;
+  o.ms_device = ms_device;
+  return highlight_batch_on(ix, S, q_utf8, q_offsets, n_q, docs, doc_offsets, o);
+}
+
+static int snippets_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf8, const uint64_t *q_offsets,
+                             uint32_t n_q, const uint32_t *docs, const uint64_t *doc_offsets, uint32_t max_bytes,
+                             uint8_t *text, uint64_t text_cap, uint64_t *text_offsets, uint64_t *doc_starts,
+                             uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t m_cap,
+                             uint64_t *match_offsets, uint64_t *n_text, uint64_t *n_matches, float *ms_device) {
+  if ((n_q && (!q_offsets || (!q_utf8 && q_offsets[n_q]))) || !doc_offsets || (!docs && doc_offsets[n_q]) ||
+      !text_offsets || (!doc_starts && doc_offsets[n_q]) || !match_offsets || !n_text || !n_matches)
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (max_bytes < kHlMinBytes || max_bytes > kHlMaxBytes)
+    return fail(TFIDF_E_INVALID_ARG, "max_bytes %u outside %u..%u", max_bytes, kHlMinBytes, kHlMaxBytes);
+  HlOut o;
+  o.W = max_bytes;
+  o.text = text;
+  o.text_cap = text_cap;
+  o.text_offsets = text_offsets;
+  o.doc_starts = doc_starts;
+  o.n_text = n_text;
+  o.starts = starts;
+  o.lens = lens;
+  o.ordinals = ordinals;
+  o.m_cap = m_cap;
+  o.match_offsets = match_offsets;
+  o.n_matches = n_matches;
+  o.ms_device = ms_device;
+  return highlight_batch_on(ix, S, q_utf8, q_offsets, n_q, docs, doc_offsets, o);
+}
+
+extern "C" int tfidf_reader_matches_batch(tfidf_reader *rd, const uint8_t *q_utf8, const uint64_t *q_offsets,
+                                          uint32_t n_q, const uint32_t *docs, const uint64_t *doc_offsets,
+                                          uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t cap,
+                                          uint64_t *match_offsets, uint64_t *n_out, float *ms_device) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  return matches_batch_on(rd->ix, *rd->S, q_utf8, q_offsets, n_q, docs, doc_offsets, starts, lens, ordinals, cap,
+                          match_offsets, n_out, ms_device);
+}
+
+extern "C" int tfidf_matches_batch(tfidf_index *ix, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                                   const uint32_t *docs, const uint64_t *doc_offsets, uint64_t *starts, uint32_t *lens,
+                                   uint32_t *ordinals, uint64_t cap, uint64_t *match_offsets, uint64_t *n_out,
+                                   float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "matches before commit");
+  return matches_batch_on(ix, *snap, q_utf8, q_offsets, n_q, docs, doc_offsets, starts, lens, ordinals, cap,
+                          match_offsets, n_out, ms_device);
+}
+
+extern "C" int tfidf_reader_snippets_batch(tfidf_reader *rd, const uint8_t *q_utf8, const uint64_t *q_offsets,
+                                           uint32_t n_q, const uint32_t *docs, const uint64_t *doc_offsets,
+                                           uint32_t max_bytes, uint8_t *text, uint64_t text_cap,
+                                           uint64_t *text_offsets, uint64_t *doc_starts, uint64_t *starts,
+                                           uint32_t *lens, uint32_t *ordinals, uint64_t m_cap,
+                                           uint64_t *match_offsets, uint64_t *n_text, uint64_t *n_matches,
+                                           float *ms_device) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  return snippets_batch_on(rd->ix, *rd->S, q_utf8, q_offsets, n_q, docs, doc_offsets, max_bytes, text, text_cap,
+                           text_offsets, doc_starts, starts, lens, ordinals, m_cap, match_offsets, n_text, n_matches,
+                           ms_device);
+}
+
+extern "C" int tfidf_snippets_batch(tfidf_index *ix, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                                    const uint32_t *docs, const uint64_t *doc_offsets, uint32_t max_bytes,
+                                    uint8_t *text, uint64_t text_cap, uint64_t *text_offsets, uint64_t *doc_starts,
+                                    uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t m_cap,
+                                    uint64_t *match_offsets, uint64_t *n_text, uint64_t *n_matches,
+                                    float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "snippets before commit");
+  return snippets_batch_on(ix, *snap, q_utf8, q_offsets, n_q, docs, doc_offsets, max_bytes, text, text_cap,
+                           text_offsets, doc_starts, starts, lens, ordinals, m_cap, match_offsets, n_text, n_matches,
+                           ms_device);
+}
+
+extern "C" int tfidf_last_highlight_chunks(const tfidf_index *ix, uint64_t *item_chunks, uint64_t *row_chunks) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->ms_mu);
+  if (item_chunks) *item_chunks = ix->last_hl_item_chunks;
+  if (row_chunks) *row_chunks = ix->last_hl_row_chunks;
+  return TFIDF_OK;
 }
 
 extern "C" int tfidf_query_positive_terms(const uint8_t *q, uint64_t q_len, char *out, uint64_t cap, uint64_t *n_terms,

@@ -2034,6 +2034,177 @@ extern "C" int tfidf_node_doc_key(tfidf_node *n, uint64_t doc, uint8_t *buf, uin
   return tfidf_doc_key(n->shards[g], doc - n->doc_base[g], buf, cap, n_out);
 }
 
+// ---------------------------------------------------------------------------
+// batched hit highlighting over the node: rows by global doc id
+
+namespace {
+
+struct NodeHlOut {                     // the caller's arrays (HlOut of tfidf_capi.hip, global rows)
+  uint32_t W = 0;                      // 0 = matches
+  uint8_t *text = nullptr;
+  uint64_t text_cap = 0;
+  uint64_t *text_offsets = nullptr, *doc_starts = nullptr, *n_text = nullptr;
+  uint64_t *starts = nullptr;
+  uint32_t *lens = nullptr, *ordinals = nullptr;
+  uint64_t m_cap = 0;
+  uint64_t *match_offsets = nullptr, *n_matches = nullptr;
+  float *ms_device = nullptr;
+};
+
+struct ShardRows {                     // one shard's batch: its rows in the caller's order
+  std::vector<uint64_t> row;           // caller row of local row j
+  std::vector<uint32_t> docs;          // shard-local doc ids
+  std::vector<uint64_t> doc_offsets;   // n_q + 1
+  std::vector<uint8_t> text;
+  std::vector<uint64_t> text_offsets, doc_starts, starts, match_offsets;
+  std::vector<uint32_t> lens, ordinals;
+  float ms = 0.0f;
+};
+
+// one shard's batch: once with guessed payload sizes, once more with the sizes it reports
+int shard_highlight(tfidf_index *ix, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q, uint32_t W,
+                    ShardRows &b) {
+  const uint64_t R = b.docs.size();
+  b.match_offsets.assign(R + 1, 0);
+  b.text_offsets.assign(R + 1, 0);
+  b.doc_starts.assign(R, 0);
+  uint64_t t_cap = W ? std::min<uint64_t>(R * W, 64ull << 20) : 0, m_cap = 64 * R, nt = 0, nm = 0;
+  int rc = TFIDF_OK;
+  for (int attempt = 0; attempt < 2; attempt++) {
+    b.text.resize(t_cap);
+    b.starts.resize(m_cap);
+    b.lens.resize(m_cap);
+    b.ordinals.resize(m_cap);
+    rc = W ? tfidf_snippets_batch(ix, q_utf8, q_offsets, n_q, b.docs.data(), b.doc_offsets.data(), W, b.text.data(),
+                                  t_cap, b.text_offsets.data(), b.doc_starts.data(), b.starts.data(), b.lens.data(),
+                                  b.ordinals.data(), m_cap, b.match_offsets.data(), &nt, &nm, &b.ms)
+           : tfidf_matches_batch(ix, q_utf8, q_offsets, n_q, b.docs.data(), b.doc_offsets.data(), b.starts.data(),
+                                 b.lens.data(), b.ordinals.data(), m_cap, b.match_offsets.data(), &nm, &b.ms);
+    if (rc != TFIDF_E_BUFFER) break;
+    t_cap = nt;
+    m_cap = nm;
+  }
+  return rc;
+}
+
+int node_highlight(tfidf_node *n, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q, const uint64_t *docs,
+                   const uint64_t *doc_offsets, const NodeHlOut &o) {
+  std::lock_guard<std::mutex> lk(n->mu);
+  if (o.ms_device) *o.ms_device = 0.0f;
+  if (!n->committed) return errf(TFIDF_E_STATE, "highlighting before tfidf_node_commit");
+  if (doc_offsets[0] != 0) return errf(TFIDF_E_INVALID_ARG, "doc_offsets[0] is not 0");
+  for (uint32_t i = 0; i < n_q; i++)
+    if (doc_offsets[i + 1] < doc_offsets[i]) return errf(TFIDF_E_INVALID_ARG, "doc_offsets decrease at query %u", i);
+  const uint64_t R = doc_offsets[n_q];
+  if (R > (1ull << 26)) return errf(TFIDF_E_INVALID_ARG, "more than 2^26 rows in one call");
+  for (uint64_t r = 0; r < R; r++)
+    if (docs[r] >= n->num_docs)
+      return errf(TFIDF_E_INVALID_ARG, "doc %llu out of range", (unsigned long long)docs[r]);
+  // rows to their shards (tfidf_node_doc_key's rule), query grouping and order kept
+  const size_t G = n->shards.size();
+  std::vector<ShardRows> sh(G);
+  std::vector<uint32_t> row_shard(R);
+  std::vector<uint64_t> row_local(R);
+  for (size_t g = 0; g < G; g++) sh[g].doc_offsets.assign((size_t)n_q + 1, 0);
+  for (uint32_t i = 0; i < n_q; i++) {
+    for (uint64_t r = doc_offsets[i]; r < doc_offsets[i + 1]; r++) {
+      size_t g = G - 1;
+      while (n->doc_base[g] > docs[r]) g--;
+      row_shard[r] = (uint32_t)g;
+      row_local[r] = sh[g].docs.size();
+      sh[g].row.push_back(r);
+      sh[g].docs.push_back((uint32_t)(docs[r] - n->doc_base[g]));
+    }
+    for (size_t g = 0; g < G; g++) sh[g].doc_offsets[i + 1] = sh[g].docs.size();
+  }
+  // every shard with rows runs its own batch at once
+  if (int rc = n->pool->run([&](uint32_t g) {
+        return sh[g].docs.empty() ? TFIDF_OK : shard_highlight(n->shards[g], q_utf8, q_offsets, n_q, o.W, sh[g]);
+      }))
+    return rc;
+  // back into the caller's row order: offsets first (always in full), then the payload when it fits
+  uint64_t nt = 0, nm = 0;
+  o.match_offsets[0] = 0;
+  if (o.W) o.text_offsets[0] = 0;
+  for (uint64_t r = 0; r < R; r++) {
+    const ShardRows &b = sh[row_shard[r]];
+    const uint64_t j = row_local[r];
+    nm += b.match_offsets[j + 1] - b.match_offsets[j];
+    o.match_offsets[r + 1] = nm;
+    if (o.W) {
+      nt += b.text_offsets[j + 1] - b.text_offsets[j];
+      o.text_offsets[r + 1] = nt;
+      o.doc_starts[r] = b.doc_starts[j];
+    }
+  }
+  *o.n_matches = nm;
+  if (o.W) *o.n_text = nt;
+  if (o.ms_device)
+    for (const ShardRows &b : sh) *o.ms_device = std::max(*o.ms_device, b.ms);
+  if (nm > o.m_cap || (nm && (!o.starts || !o.lens || !o.ordinals)) || (o.W && (nt > o.text_cap || (nt && !o.text))))
+    return errf(TFIDF_E_BUFFER, "need %llu text bytes and %llu match slots", (unsigned long long)nt,
+                (unsigned long long)nm);
+  for (uint64_t r = 0; r < R; r++) {
+    const ShardRows &b = sh[row_shard[r]];
+    const uint64_t j = row_local[r], m0 = b.match_offsets[j], mc = b.match_offsets[j + 1] - m0;
+    if (mc) {
+      memcpy(o.starts + o.match_offsets[r], b.starts.data() + m0, mc * 8);
+      memcpy(o.lens + o.match_offsets[r], b.lens.data() + m0, mc * 4);
+      memcpy(o.ordinals + o.match_offsets[r], b.ordinals.data() + m0, mc * 4);
+    }
+    if (o.W && b.text_offsets[j + 1] > b.text_offsets[j])
+      memcpy(o.text + o.text_offsets[r], b.text.data() + b.text_offsets[j], b.text_offsets[j + 1] - b.text_offsets[j]);
+  }
+  return TFIDF_OK;
+}
+
+}  // namespace
+
+extern "C" int tfidf_node_matches_batch(tfidf_node *n, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                                        const uint64_t *docs, const uint64_t *doc_offsets, uint64_t *starts,
+                                        uint32_t *lens, uint32_t *ordinals, uint64_t cap, uint64_t *match_offsets,
+                                        uint64_t *n_out, float *ms_device) {
+  if (!n || (n_q && !q_offsets) || !doc_offsets || (!docs && doc_offsets[n_q]) || !match_offsets || !n_out)
+    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  NodeHlOut o;
+  o.starts = starts;
+  o.lens = lens;
+  o.ordinals = ordinals;
+  o.m_cap = cap;
+  o.match_offsets = match_offsets;
+  o.n_matches = n_out;
+  o.ms_device = ms_device;
+  return node_highlight(n, q_utf8, q_offsets, n_q, docs, doc_offsets, o);
+}
+
+extern "C" int tfidf_node_snippets_batch(tfidf_node *n, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
+                                         const uint64_t *docs, const uint64_t *doc_offsets, uint32_t max_bytes,
+                                         uint8_t *text, uint64_t text_cap, uint64_t *text_offsets,
+                                         uint64_t *doc_starts, uint64_t *starts, uint32_t *lens, uint32_t *ordinals,
+                                         uint64_t m_cap, uint64_t *match_offsets, uint64_t *n_text,
+                                         uint64_t *n_matches, float *ms_device) {
+  if (!n || (n_q && !q_offsets) || !doc_offsets || (!docs && doc_offsets[n_q]) || !text_offsets ||
+      (!doc_starts && doc_offsets[n_q]) || !match_offsets || !n_text || !n_matches)
+    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (max_bytes < 16 || max_bytes > 65536)
+    return errf(TFIDF_E_INVALID_ARG, "max_bytes %u outside 16..65536", max_bytes);
+  NodeHlOut o;
+  o.W = max_bytes;
+  o.text = text;
+  o.text_cap = text_cap;
+  o.text_offsets = text_offsets;
+  o.doc_starts = doc_starts;
+  o.n_text = n_text;
+  o.starts = starts;
+  o.lens = lens;
+  o.ordinals = ordinals;
+  o.m_cap = m_cap;
+  o.match_offsets = match_offsets;
+  o.n_matches = n_matches;
+  o.ms_device = ms_device;
+  return node_highlight(n, q_utf8, q_offsets, n_q, docs, doc_offsets, o);
+}
+
 extern "C" int tfidf_node_stats_get(const tfidf_node *n, tfidf_node_stats *out) {
   if (!n || !out) return errf(TFIDF_E_INVALID_ARG, "NULL argument");
   out->n_shards = n->shards.size();

@@ -103,6 +103,16 @@ SIGNATURES = {
                                         U64P, U64P, U64P, U32P, U32P, C.c_uint64, U64P, U64P, U64P, F32P]),
     "tfidf_snippets": (C.c_int, [VP, C.c_char_p, C.c_uint64, U32P, C.c_uint64, C.c_uint32, VP, C.c_uint64, U64P,
                                  U64P, U64P, U32P, U32P, C.c_uint64, U64P, U64P, U64P, F32P]),
+    "tfidf_reader_matches_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U32P, U64P, U64P, U32P, U32P,
+                                             C.c_uint64, U64P, U64P, F32P]),
+    "tfidf_matches_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U32P, U64P, U64P, U32P, U32P, C.c_uint64,
+                                      U64P, U64P, F32P]),
+    "tfidf_reader_snippets_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U32P, U64P, C.c_uint32, VP,
+                                              C.c_uint64, U64P, U64P, U64P, U32P, U32P, C.c_uint64, U64P, U64P,
+                                              U64P, F32P]),
+    "tfidf_snippets_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U32P, U64P, C.c_uint32, VP, C.c_uint64,
+                                       U64P, U64P, U64P, U32P, U32P, C.c_uint64, U64P, U64P, U64P, F32P]),
+    "tfidf_last_highlight_chunks": (C.c_int, [VP, U64P, U64P]),
     "tfidf_query_positive_terms": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, U64P, U64P]),
     "tfidf_set_hash_attempt": (C.c_int, [VP, C.c_uint32]),
     "tfidf_get_commit_timing": (C.c_int, [VP, C.POINTER(CommitTiming)]),
@@ -185,6 +195,10 @@ SIGNATURES = {
     "tfidf_node_search_names_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U64P, U64P]),
     "tfidf_node_last_names_batch": (C.c_int, [VP, C.c_char_p, C.c_uint64, U64P, F64P, C.c_uint64, U64P, U64P, U64P]),
     "tfidf_node_doc_key": (C.c_int, [VP, C.c_uint64, C.c_char_p, C.c_uint64, U64P]),
+    "tfidf_node_matches_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U64P, U64P, U64P, U32P, U32P,
+                                           C.c_uint64, U64P, U64P, F32P]),
+    "tfidf_node_snippets_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U64P, U64P, C.c_uint32, VP, C.c_uint64,
+                                            U64P, U64P, U64P, U32P, U32P, C.c_uint64, U64P, U64P, U64P, F32P]),
     "tfidf_node_last_failed": (C.c_int, [VP, U64P]),
     "tfidf_node_stats_get": (C.c_int, [VP, VP]),
     "tfidf_device_free": (C.c_int, [C.c_int, VP]),

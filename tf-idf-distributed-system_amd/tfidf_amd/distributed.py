@@ -461,6 +461,21 @@ class Node:
         L.check(L.load().tfidf_node_doc_key(self._h, doc, buf, 4096, C.byref(n)))
         return buf.raw[:n.value]
 
+    def matches_batch(self, queries, docs_per_query):
+        """ShardIndex.matches_batch over the node: documents by global id, each
+        row served by its shard (tfidf_node_matches_batch)."""
+        from . import engine as E
+        a = E._matches_batch_arrays(L.load().tfidf_node_matches_batch, self._h, queries, docs_per_query,
+                                    dtype=np.uint64)
+        return E._per_query(E._match_lists(*a[:4]), a[4])
+
+    def snippets_batch(self, queries, docs_per_query, max_bytes=160):
+        """ShardIndex.snippets_batch over the node: documents by global id (tfidf_node_snippets_batch)."""
+        from . import engine as E
+        a = E._snippets_batch_arrays(L.load().tfidf_node_snippets_batch, self._h, queries, docs_per_query, max_bytes,
+                                     dtype=np.uint64)
+        return E._per_query(E._snippet_lists(a[:8]), a[8])
+
 
 class NodeStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("n_shards", "num_docs", "doc_count", "sum_ttf", "num_terms", "transport")]

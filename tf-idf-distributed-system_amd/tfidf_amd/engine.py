@@ -147,6 +147,81 @@ def _snippet_lists(arrays):
     return [(int(d_starts[i]), text[t[i]:t[i + 1]], ms[i]) for i in range(len(t) - 1)]
 
 
+def _batch_rows(queries, docs_per_query, dtype):
+    """(query blob, q offsets, docs array, doc offsets) of a highlighting batch:
+    query i owns rows doc_offsets[i] .. doc_offsets[i + 1] of docs."""
+    queries = list(queries)
+    per = [np.asarray(d, dtype=dtype).reshape(-1) for d in docs_per_query]
+    if len(per) != len(queries):
+        raise ValueError("one list of documents per query")
+    blob, q_offs = _key_arrays(queries)
+    d_offs = np.zeros(len(per) + 1, np.uint64)
+    if per:
+        d_offs[1:] = np.cumsum([len(d) for d in per], dtype=np.uint64)
+    docs = np.ascontiguousarray(np.concatenate(per) if per else np.zeros(0, dtype), dtype=dtype)
+    return blob, q_offs, docs, d_offs
+
+
+def _matches_batch_arrays(fn, handle, queries, docs_per_query, cap=None, dtype=np.uint32):
+    """tfidf_[reader_|node_]matches_batch: one call with ``cap`` match slots,
+    once more with the reported size when that was too small.
+    -> (starts, lens, ordinals, match offsets uint64[R + 1], doc offsets uint64[n_q + 1], ms_device)."""
+    blob, q_offs, d, d_offs = _batch_rows(queries, docs_per_query, dtype)
+    R = len(d)
+    offs = np.zeros(R + 1, np.uint64)
+    total, ms = C.c_uint64(), C.c_float()
+    cap = 64 * max(R, 1) if cap is None else cap
+    for _ in range(2):
+        st = np.empty(max(cap, 1), np.uint64)
+        ln = np.empty(max(cap, 1), np.uint32)
+        od = np.empty(max(cap, 1), np.uint32)
+        rc = fn(handle, blob, L.ptr(q_offs, C.c_uint64), len(q_offs) - 1, L.ptr(d, np.ctypeslib.as_ctypes_type(dtype)),
+                L.ptr(d_offs, C.c_uint64), L.ptr(st, C.c_uint64), L.ptr(ln, C.c_uint32), L.ptr(od, C.c_uint32), cap,
+                L.ptr(offs, C.c_uint64), C.byref(total), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        cap = total.value
+    L.check(rc)
+    m = total.value
+    return st[:m], ln[:m], od[:m], offs, d_offs, ms.value
+
+
+def _snippets_batch_arrays(fn, handle, queries, docs_per_query, max_bytes, m_cap=None, dtype=np.uint32):
+    """tfidf_[reader_|node_]snippets_batch: the text buffer is sized in advance
+    (R x max_bytes), the match buffers once more when too small.  -> (text
+    bytes, text offsets, doc_starts, starts, lens, ordinals, match offsets,
+    ms_device, doc offsets uint64[n_q + 1]); the first eight as snippets_arrays."""
+    blob, q_offs, d, d_offs = _batch_rows(queries, docs_per_query, dtype)
+    R = len(d)
+    t_cap = R * min(max(int(max_bytes), 0), 65536)
+    text = np.empty(max(t_cap, 1), np.uint8)
+    t_offs = np.zeros(R + 1, np.uint64)
+    m_offs = np.zeros(R + 1, np.uint64)
+    d_starts = np.zeros(max(R, 1), np.uint64)
+    nt, nm, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+    m_cap = 16 * max(R, 1) if m_cap is None else m_cap
+    for _ in range(2):
+        st = np.empty(max(m_cap, 1), np.uint64)
+        ln = np.empty(max(m_cap, 1), np.uint32)
+        od = np.empty(max(m_cap, 1), np.uint32)
+        rc = fn(handle, blob, L.ptr(q_offs, C.c_uint64), len(q_offs) - 1, L.ptr(d, np.ctypeslib.as_ctypes_type(dtype)),
+                L.ptr(d_offs, C.c_uint64), max_bytes, text.ctypes.data_as(C.c_void_p), t_cap,
+                L.ptr(t_offs, C.c_uint64), L.ptr(d_starts, C.c_uint64), L.ptr(st, C.c_uint64),
+                L.ptr(ln, C.c_uint32), L.ptr(od, C.c_uint32), m_cap, L.ptr(m_offs, C.c_uint64), C.byref(nt),
+                C.byref(nm), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        m_cap = nm.value
+    L.check(rc)
+    return (text[:nt.value].tobytes(), t_offs, d_starts[:R], st[:nm.value], ln[:nm.value], od[:nm.value], m_offs,
+            ms.value, d_offs)
+
+
+def _per_query(rows, d_offs):
+    f = d_offs.tolist()
+    return [rows[f[i]:f[i + 1]] for i in range(len(f) - 1)]
+
+
 def _hit_lists(docs, scores, offs):
     d, s, o = docs.tolist(), scores.tolist(), offs.tolist()
     return [list(zip(d[o[i]:o[i + 1]], s[o[i]:o[i + 1]])) for i in range(len(o) - 1)]
@@ -265,6 +340,27 @@ class ShardIndex:
         ordinal)] in snippet bytes) — the passage of at most ``max_bytes``
         bytes with the most distinct query terms (tfidf_snippets)."""
         return _snippet_lists(_snippets_arrays(L.load().tfidf_snippets, self._h, query, docs, max_bytes))
+
+    def matches_batch(self, queries, docs_per_query):
+        """[matches(q, docs) for q, docs in zip(queries, docs_per_query)] in
+        one pass (tfidf_matches_batch); a query that does not parse has no
+        matches."""
+        a = _matches_batch_arrays(L.load().tfidf_matches_batch, self._h, queries, docs_per_query)
+        return _per_query(_match_lists(*a[:4]), a[4])
+
+    def snippets_batch(self, queries, docs_per_query, max_bytes=160):
+        """[snippets(q, docs, max_bytes) for q, docs in zip(queries,
+        docs_per_query)] in one pass (tfidf_snippets_batch); the rows of a
+        query that does not parse get head-of-document snippets."""
+        a = _snippets_batch_arrays(L.load().tfidf_snippets_batch, self._h, queries, docs_per_query, max_bytes)
+        return _per_query(_snippet_lists(a[:8]), a[8])
+
+    def last_highlight_chunks(self):
+        """(item chunks, row chunks) of the last batched highlighting call on
+        this index or one of its readers (tfidf_last_highlight_chunks)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        L.check(L.load().tfidf_last_highlight_chunks(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def set_hash_attempt(self, attempt):
         """Seed attempt (0..3) the following commits start from (tfidf_set_hash_attempt)."""
@@ -597,6 +693,25 @@ class Reader:
     def snippets(self, query: bytes, docs, max_bytes=160):
         """ShardIndex.snippets on this reader's snapshot."""
         return _snippet_lists(self.snippets_arrays(query, docs, max_bytes))
+
+    def matches_batch_arrays(self, queries, docs_per_query, cap=None):
+        """(starts, lens, ordinals, match offsets[R + 1], doc offsets[n_q + 1], ms_device) of tfidf_reader_matches_batch."""
+        return _matches_batch_arrays(L.load().tfidf_reader_matches_batch, self._h, queries, docs_per_query, cap)
+
+    def matches_batch(self, queries, docs_per_query):
+        """ShardIndex.matches_batch on this reader's snapshot."""
+        a = self.matches_batch_arrays(queries, docs_per_query)
+        return _per_query(_match_lists(*a[:4]), a[4])
+
+    def snippets_batch_arrays(self, queries, docs_per_query, max_bytes=160, m_cap=None):
+        """snippets_arrays' eight results over all rows, then doc offsets[n_q + 1] (tfidf_reader_snippets_batch)."""
+        return _snippets_batch_arrays(L.load().tfidf_reader_snippets_batch, self._h, queries, docs_per_query, max_bytes,
+                                      m_cap)
+
+    def snippets_batch(self, queries, docs_per_query, max_bytes=160):
+        """ShardIndex.snippets_batch on this reader's snapshot."""
+        a = self.snippets_batch_arrays(queries, docs_per_query, max_bytes)
+        return _per_query(_snippet_lists(a[:8]), a[8])
 
     def doc_keys(self):
         lib = L.load()

@@ -164,6 +164,33 @@ class Worker:
                 out.append(info)
             return out
 
+    # search_snippets for the requests of concurrent threads in one pass: one
+    # reader, one batched all-hits search, the first k hits of each query, one
+    # batched snippets call for all of them.  A request whose query fails
+    # yields [] (as in process_documents_batch).
+    def search_snippets_batch(self, queries, k=10, max_bytes=160):
+        out = [[] for _ in queries]
+        enc, at = [], []
+        for i, q in enumerate(queries):
+            try:
+                enc.append(q.encode())
+                at.append(i)
+            except Exception:
+                pass
+        with self.index.reader() as rd:
+            top = [hits[:k] if k else hits for hits in rd.search_batch_all(enc)]
+            snips = rd.snippets_batch(enc, [[d for d, _ in hits] for hits in top], max_bytes)
+            names = {}
+            for i, hits, sn in zip(at, top, snips):
+                for (d, s), (_, text, ms) in zip(hits, sn):
+                    if d not in names:
+                        names[d] = rd.doc_key(d).decode()
+                    info = document_score_info(names[d], s)
+                    info["snippet"] = text.decode("utf-8", errors="replace")
+                    info["matches"] = [[st, ln] for st, ln, _ in ms]
+                    out[i].append(info)
+        return out
+
     # Worker.java:175-186 /worker/process: any exception -> empty list
     def process_documents(self, search_query: str):
         try:

@@ -16,6 +16,18 @@ Per shape, median and [min, max] over --runs timed calls after --warmup:
 plus the bytes of the documents, bytes returned, bytes scanned per device
 second, and the commit's tokenizer time over the same corpus for comparison.
 One JSON file per shape under --out-dir, and one line per shape on stdout.
+
+Batch shapes (tfidf_reader_snippets_batch against the only route without it,
+one tfidf_reader_snippets call per query on the same reader; a round alternates
+the two, buffers allocated once):
+  cfg2-batch-Q        Q in {1, 64, 1024} three-term queries (fixed seed), top-10 rows each
+  cfg2-batch-1024x100 1024 queries, top-100 rows each
+  node2-batch-1024    tfidf_node_snippets_batch on two shards of one device
+                      (--node-docs documents) against one tfidf_snippets call
+                      per (query, shard), routed by hand
+Per shape: device and wall median [min, max] of both routes, bytes scanned per
+device second of both, the row chunks of the batched call, and whether the
+batch's slowest round beat the loop's fastest.
 """
 import argparse
 import ctypes as C
@@ -79,6 +91,168 @@ def measure(name, rd, q, docs, runs, warmup, extra):
     return res
 
 
+class RawSnippets:
+    """tfidf_*_snippets[_batch] through ctypes into buffers allocated once, so
+    neither route of measure_batch pays for Python-side allocation."""
+
+    def __init__(self, n_rows, W, docs_dtype=np.uint32):
+        self.W = W
+        self.t_cap, self.m_cap = n_rows * W, n_rows * (W // 2 + 1)     # a match and its separator: >= 2 bytes
+        self.text = np.empty(max(self.t_cap, 1), np.uint8)
+        self.t_offs = np.zeros(n_rows + 1, np.uint64)
+        self.m_offs = np.zeros(n_rows + 1, np.uint64)
+        self.d_starts = np.zeros(max(n_rows, 1), np.uint64)
+        self.st = np.empty(max(self.m_cap, 1), np.uint64)
+        self.ln = np.empty(max(self.m_cap, 1), np.uint32)
+        self.od = np.empty(max(self.m_cap, 1), np.uint32)
+        self.nt, self.nm, self.ms = C.c_uint64(), C.c_uint64(), C.c_float()
+        self.dt = np.ctypeslib.as_ctypes_type(docs_dtype)
+
+    def tail(self):
+        return (self.W, self.text.ctypes.data_as(C.c_void_p), self.t_cap, L.ptr(self.t_offs, C.c_uint64),
+                L.ptr(self.d_starts, C.c_uint64), L.ptr(self.st, C.c_uint64), L.ptr(self.ln, C.c_uint32),
+                L.ptr(self.od, C.c_uint32), self.m_cap, L.ptr(self.m_offs, C.c_uint64), C.byref(self.nt),
+                C.byref(self.nm), C.byref(self.ms))
+
+    def batch(self, fn, handle, blob, q_offs, n_q, docs, d_offs):
+        L.check(fn(handle, blob, L.ptr(q_offs, C.c_uint64), n_q, L.ptr(docs, self.dt), L.ptr(d_offs, C.c_uint64),
+                   *self.tail()))
+        return self.ms.value
+
+    def single(self, fn, handle, q, docs):
+        L.check(fn(handle, q, len(q), L.ptr(docs, C.c_uint32), len(docs), *self.tail()))
+        return self.ms.value
+
+
+def measure_batch(name, batch_call, loop_call, chunks, n_q, rows, nbytes, runs, warmup, extra):
+    """A round alternates the two routes: one batched call, and the only route
+    without it, one single-query call per query (per query and shard on a
+    node).  Each returns (device ms, snippet bytes, in-snippet matches)."""
+    dev, wall, ldev, lwall = [], [], [], []
+    out = lout = None
+    for r in range(warmup + runs):
+        t0 = time.perf_counter()
+        out = batch_call()
+        t1 = time.perf_counter()
+        lout = loop_call()
+        t2 = time.perf_counter()
+        if r >= warmup:
+            dev.append(out[0])
+            wall.append((t1 - t0) * 1e3)
+            ldev.append(lout[0])
+            lwall.append((t2 - t1) * 1e3)
+    assert out[1:] == lout[1:], (out, lout)                # the same snippets and matches in total
+    res = {"shape": name, "queries": n_q, "rows": rows, "runs": runs, "warmup": warmup, "document_bytes": nbytes,
+           "snippet_bytes": out[1], "snippet_matches": out[2],
+           "batch": {"device_ms": spread(dev), "wall_ms": spread(wall)},
+           "loop_of_single_calls": {"device_ms": spread(ldev), "wall_ms": spread(lwall)},
+           "item_chunks": chunks()[0], "row_chunks": chunks()[1]}
+    res["scan_GBs_device"] = nbytes / (res["batch"]["device_ms"]["median"] * 1e-3) / 1e9
+    res["loop_scan_GBs_device"] = nbytes / (res["loop_of_single_calls"]["device_ms"]["median"] * 1e-3) / 1e9
+    res["wall_speedup_over_loop"] = res["loop_of_single_calls"]["wall_ms"]["median"] / res["batch"]["wall_ms"]["median"]
+    res["batch_max_below_loop_min"] = res["batch"]["wall_ms"]["max"] < res["loop_of_single_calls"]["wall_ms"]["min"]
+    res.update(extra)
+    return res
+
+
+def top_rows(docs, offs, k):
+    """The first k hits of every query of a search_batch_all result, CSR."""
+    o = offs.astype(np.int64)
+    per = [docs[o[i]:min(o[i + 1], o[i] + k)] for i in range(len(o) - 1)]
+    d_offs = np.zeros(len(per) + 1, np.uint64)
+    d_offs[1:] = np.cumsum([len(p) for p in per], dtype=np.uint64)
+    return per, np.ascontiguousarray(np.concatenate(per)), d_offs
+
+
+def doc_lengths(dc):
+    """Byte length of every document of a DeviceCorpus (its offsets alone come to the host)."""
+    offs = np.zeros(dc.n_docs + 1, np.uint64)
+    synth._d2h(offs, dc.d_offsets, (dc.n_docs + 1) * 8, dc.device)
+    return np.diff(offs.astype(np.int64))
+
+
+def batch_shape(name, g, rd, queries, k, lens, runs, warmup, extra):
+    lib = L.load()
+    docs, _, offs = rd.search_batch_all_arrays(queries)
+    per, flat, d_offs = top_rows(docs.astype(np.uint32), offs, k)
+    per = [np.ascontiguousarray(p) for p in per]
+    blob = b"".join(queries)
+    q_offs = np.zeros(len(queries) + 1, np.uint64)
+    q_offs[1:] = np.cumsum([len(q) for q in queries], dtype=np.uint64)
+    raw = RawSnippets(len(flat), 160)
+    nbytes = int(lens[flat.astype(np.int64)].sum())
+
+    def batch_call():
+        ms = raw.batch(lib.tfidf_reader_snippets_batch, rd._h, blob, q_offs, len(queries), flat, d_offs)
+        return ms, raw.nt.value, raw.nm.value
+
+    def loop_call():
+        ms = nt = nm = 0
+        for q, p in zip(queries, per):
+            ms += raw.single(lib.tfidf_reader_snippets, rd._h, q, p)
+            nt += raw.nt.value
+            nm += raw.nm.value
+        return ms, nt, nm
+    return measure_batch(name, batch_call, loop_call, g.last_highlight_chunks, len(queries), int(len(flat)), nbytes,
+                         runs, warmup, extra)
+
+
+def node_shape(name, n_docs, n_q, k, runs, warmup):
+    """Two shards on device 0, in-process, GLOBAL statistics; the loop is one
+    tfidf_snippets call per (query, shard with rows), routed by hand."""
+    from tfidf_amd import distributed as D
+    lib = L.load()
+    dc = synth.DeviceCorpus(n_docs, V=100_000, len_min=400, len_max=600)
+    text, offsets = dc.to_host()
+    dc.free()
+    node = D.Node(devices=[0, 0], stats_mode=L.STATS_GLOBAL)
+    half = n_docs // 2
+    for g, (a, z) in enumerate(((0, half), (half, n_docs))):
+        offs = np.ascontiguousarray(offsets[a:z + 1] - offsets[a])
+        L.check(lib.tfidf_node_add_docs(node._h, g, C.cast(text[int(offsets[a]):].ctypes.data, C.c_char_p),
+                                        L.ptr(offs, C.c_uint64), z - a, None, None))
+    node.commit()
+    queries = synth.queries(n_q, n_terms=3)
+    docs, _, offs = node.search_batch_all_arrays(queries)
+    per, flat, d_offs = top_rows(docs.astype(np.uint64), offs, k)
+    blob = b"".join(queries)
+    q_offs = np.zeros(n_q + 1, np.uint64)
+    q_offs[1:] = np.cumsum([len(q) for q in queries], dtype=np.uint64)
+    raw = RawSnippets(len(flat), 160, np.uint64)
+    lens = np.diff(offsets.astype(np.int64))
+    nbytes = int(lens[flat.astype(np.int64)].sum())
+    shards = [node.shard(0), node.shard(1)]
+    routed = [[np.ascontiguousarray(p[p < half], dtype=np.uint32),
+               np.ascontiguousarray(p[p >= half] - half, dtype=np.uint32)] for p in per]
+
+    def batch_call():
+        ms = raw.batch(lib.tfidf_node_snippets_batch, node._h, blob, q_offs, n_q, flat, d_offs)
+        return ms, raw.nt.value, raw.nm.value
+
+    def loop_call():
+        ms = nt = nm = 0
+        for q, parts in zip(queries, routed):
+            for h, p in zip(shards, parts):
+                if len(p):
+                    ms += raw.single(lib.tfidf_snippets, h, q, p)
+                    nt += raw.nt.value
+                    nm += raw.nm.value
+        return ms, nt, nm
+
+    def chunks():
+        a, b = C.c_uint64(), C.c_uint64()
+        tot = [0, 0]
+        for h in shards:
+            L.check(lib.tfidf_last_highlight_chunks(h, C.byref(a), C.byref(b)))
+            tot = [tot[0] + a.value, tot[1] + b.value]
+        return tot
+    res = measure_batch(name, batch_call, loop_call, chunks, n_q, int(len(flat)), nbytes, runs, warmup,
+                        {"corpus": "node of 2 shards on one device: %d docs x U[400,600] tokens, V=100000" % n_docs,
+                         "note": "batch device_ms is the larger of the two shards' device times; chunks summed over shards"})
+    node.close()
+    return res
+
+
 def commit_rates(g):
     t = g.commit_timing()
     return {"commit_ms_tokenize": t["ms_tokenize"], "commit_ms_long": t["ms_long"],
@@ -94,7 +268,8 @@ def main():
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out-dir", default=os.path.join(REPO, "profiles", "highlight"))
-    ap.add_argument("--skip", default="", help="comma-separated shapes to leave out (cfg2, book)")
+    ap.add_argument("--node-docs", type=int, default=200_000, help="documents of the two-shard node (host staged)")
+    ap.add_argument("--skip", default="", help="comma-separated shapes to leave out (cfg2, book, batch, node)")
     args = ap.parse_args()
     from tfidf_amd.engine import ShardIndex
     os.makedirs(args.out_dir, exist_ok=True)
@@ -125,8 +300,18 @@ def main():
             extra["search_top10_wall_ms_p50"] = float(np.median(lat[args.warmup:]))
             emit(measure("cfg2-top10", rd, q, top[:10], args.runs, args.warmup, extra))
             emit(measure("cfg2-top1024", rd, q, top, args.runs, args.warmup, extra))
+            if "batch" not in skip:
+                lens = doc_lengths(dc)
+                bx = {"corpus": extra["corpus"]}
+                for nq in (1, 64, 1024):
+                    emit(batch_shape("cfg2-batch-%d" % nq, g, rd, synth.queries(nq, n_terms=3), 10, lens, args.runs,
+                                     args.warmup, bx))
+                emit(batch_shape("cfg2-batch-1024x100", g, rd, synth.queries(1024, n_terms=3), 100, lens, args.runs,
+                                 args.warmup, bx))
         g.close()
         dc.free()
+    if "node" not in skip:
+        emit(node_shape("node2-batch-1024", args.node_docs, 1024, 10, args.runs, args.warmup))
     if "book" not in skip:
         nb, T = args.books, args.book_tokens
         dc = synth.DeviceCorpus(nb, V=100_000, len_min=T, len_max=T, seed=synth.SEED + 29)
