@@ -2506,59 +2506,91 @@ __device__ __forceinline__ void doc_segment(const PostingParams &p, uint64_t d, 
   *hi = p.rsplit[d * p.n_ranges + r];
 }
 
-// Documents per wave in flight in the inversion kernels: each wave walks
-// kInvDocs documents' segments together so their loads overlap, and issues
-// the next group's segment loads before the current group's LDS atomics and
-// stores (gfx9 counts stores in vmcnt: waiting for loads issued after a
-// store would also wait for the store).
-#ifndef TFIDF_INV_DOCS
-#define TFIDF_INV_DOCS 8
+// Segment loads of the inversion kernels, in quads: sixteen lanes serve one
+// document, lane l reading entries [4 (l & 15), + 4) of the segment of
+// document l >> 4 of the quad, so one 16-byte load instruction covers four
+// documents x 64 entries (a cfg-2 segment averages 42).  A wave walks Q quads
+// (4 Q consecutive documents) together and issues the next group's loads
+// before the current group's LDS atomics and stores (gfx9 counts stores in
+// vmcnt: waiting for loads issued after a store would also wait for the
+// store).  Quads per group, per kernel (DESIGN.md §6 "Inversion: 16-byte
+// segment loads" has the measurements):
+#ifndef TFIDF_DF_QUADS
+#define TFIDF_DF_QUADS 4
 #endif
-constexpr int kInvDocs = TFIDF_INV_DOCS;   // A/B: -DTFIDF_INV_DOCS=16
+#ifndef TFIDF_PART_QUADS
+#define TFIDF_PART_QUADS 3
+#endif
+constexpr int kDfQuads = TFIDF_DF_QUADS;      // k_df_partial
+constexpr int kPartQuads = TFIDF_PART_QUADS;  // k_scatter_part (its LDS stage holds 16 waves x 4 Q x 64 entries)
+static_assert(kDfQuads >= 1 && kDfQuads <= 4 && kPartQuads >= 1 && kPartQuads <= 4, "quads per group");
 
-struct InvGroup {               // wave-uniform
-  uint64_t base[kInvDocs];
-  uint32_t lo[kInvDocs], hi[kInvDocs], nrm[kInvDocs];
-  uint32_t maxn;
+// A segment starts on a 4-byte boundary only: the vector type is declared
+// with that alignment, so the load is one global_load_dwordx4 without an
+// over-aligned pointer.
+typedef uint32_t csr_quad_t __attribute__((ext_vector_type(4), aligned(4)));
+
+template <int Q>
+struct InvQuads {               // per lane: its document of each quad
+  uint64_t at[Q];               // CSR index of the segment's first entry
+  uint32_t n[Q];                // entries in the segment (0: no such document)
 };
 
-// Group metadata, loaded lane-parallel (lane j < kInvDocs fetches document j:
-// one round trip for the whole group instead of a dependent scalar chain per
-// document) and broadcast with readlane.
-__device__ __forceinline__ InvGroup inv_group(const PostingParams &p, uint64_t dd, uint64_t d1, uint32_t stride,
-                                              uint32_t r, bool with_norm) {
+// Group metadata: lane j < 4 Q fetches document dd + j (one round trip for
+// the group) and the sixteen lanes of a document take its two values from
+// that lane by a wave shuffle.  (Each lane loading its own document's words,
+// sixteen lanes the same ones, costs four times the address arithmetic:
+// k_df_partial 0.36 -> 0.49 ms at cfg 2; both kernels are issue-bound.)
+template <int Q>
+__device__ __forceinline__ InvQuads<Q> inv_quads(const PostingParams &p, uint64_t dd, uint64_t d1, uint32_t r) {
   const uint32_t lane = threadIdx.x & 63;
-  const uint64_t d = dd + (uint64_t)stride * (lane & (kInvDocs - 1));
-  const bool ok = lane < (uint32_t)kInvDocs && d < d1;
-  uint64_t base = 0;
-  uint32_t lo = 0, hi = 0, nrm = 0;
-  if (ok) {
+  const uint64_t d = dd + lane;
+  uint64_t at = 0;
+  uint32_t n = 0;
+  if (lane < (uint32_t)(4 * Q) && d < d1) {
     const uint64_t src = p.live_map ? p.live_map[d] : d;
-    base = csr_row_base(p.offsets, src);
-    lo = r ? p.rsplit[d * p.n_ranges + r - 1] : 0;
-    hi = p.rsplit[d * p.n_ranges + r];
-    if (with_norm) nrm = p.doc_norm[d];
+    const uint32_t lo = r ? p.rsplit[d * p.n_ranges + r - 1] : 0;
+    at = csr_row_base(p.offsets, src) + lo;
+    n = p.rsplit[d * p.n_ranges + r] - lo;
   }
-  InvGroup g;
-  g.maxn = 0;
+  InvQuads<Q> g;
 #pragma unroll
-  for (int j = 0; j < kInvDocs; j++) {
-    g.base[j] = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(base >> 32), j) << 32) |
-                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)base, j);
-    g.lo[j] = (uint32_t)__builtin_amdgcn_readlane((int)lo, j);
-    g.hi[j] = (uint32_t)__builtin_amdgcn_readlane((int)hi, j);
-    g.nrm[j] = (uint32_t)__builtin_amdgcn_readlane((int)nrm, j);
-    g.maxn = max(g.maxn, g.hi[j] - g.lo[j]);
+  for (int q = 0; q < Q; q++) {
+    const int from = 4 * q + (int)(lane >> 4);
+    g.at[q] = ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(at >> 32), from, 64) << 32) |
+              (uint32_t)__shfl((int)(uint32_t)at, from, 64);
+    g.n[q] = (uint32_t)__shfl((int)n, from, 64);
   }
   return g;
 }
 
-// packed CSR words off of the group's documents' segments (0 past a segment)
-__device__ __forceinline__ void inv_load(const PostingParams &p, const InvGroup &g, uint32_t off, uint32_t *c) {
+// the longest segment among the lane's documents (the follow-up loops run
+// while any lane of the wave has entries at or past `off`)
+template <int Q>
+__device__ __forceinline__ uint32_t inv_maxn(const InvQuads<Q> &g) {
+  uint32_t m = 0;
 #pragma unroll
-  for (int j = 0; j < kInvDocs; j++) {
-    const bool in = g.lo[j] + off < g.hi[j];
-    c[j] = in ? p.csr[g.base[j] + g.lo[j] + off] : 0u;
+  for (int q = 0; q < Q; q++) m = max(m, g.n[q]);
+  return m;
+}
+
+// c[4 q + k] = entry off + 4 (lane & 15) + k of the lane's document of quad q
+// (0 at or past the segment's end; a CSR word is never 0).  A lane whose
+// first entry is inside the segment loads 16 bytes, so the last lane of a
+// segment reads up to 12 bytes past it: the next row's words, or the slack
+// tfidf_commit reserves behind the CSR buffer.
+template <int Q>
+__device__ __forceinline__ void inv_load(const PostingParams &p, const InvQuads<Q> &g, uint32_t off, uint32_t *c) {
+  const uint32_t e0 = off + 4 * (threadIdx.x & 15);
+#pragma unroll
+  for (int q = 0; q < Q; q++) {
+    const uint32_t n = g.n[q];
+    csr_quad_t v = {0u, 0u, 0u, 0u};
+    if (e0 < n) v = *reinterpret_cast<const csr_quad_t *>(p.csr + g.at[q] + e0);
+    c[4 * q] = v.x;
+    c[4 * q + 1] = e0 + 1 < n ? v.y : 0u;
+    c[4 * q + 2] = e0 + 2 < n ? v.z : 0u;
+    c[4 * q + 3] = e0 + 3 < n ? v.w : 0u;
   }
 }
 
@@ -2578,7 +2610,8 @@ static uint32_t tiles_grid(uint32_t n_blocks, uint32_t R) { return (n_blocks + 7
 // one workgroup (1024 threads) per (block, range) tile (tile_of): LDS
 // histogram of the range's 65536 slots in 16-bit counters (two per word; a
 // block's count of one slot is at most kBlockDocs = 8192), 128 KiB.  Wave w
-// handles documents d0 + w + 16 (kInvDocs i + j), j < kInvDocs.  The counts
+// handles the 4 kDfQuads consecutive documents from d0 + 4 kDfQuads (16 i + w)
+// in its group i (inv_load).  The counts
 // of the range's occupied slots are written at their columns (col_rank), so
 // the count table follows the vocabulary, not the dictionary's probe table.
 __global__ void __launch_bounds__(1024) k_df_partial(PostingParams p) {
@@ -2590,35 +2623,37 @@ __global__ void __launch_bounds__(1024) k_df_partial(PostingParams p) {
   __syncthreads();
   const uint64_t d0 = (uint64_t)b * kBlockDocs;
   const uint64_t d1 = d0 + kBlockDocs < p.n_docs ? d0 + kBlockDocs : p.n_docs;
-  const uint32_t lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+  const uint32_t nw = blockDim.x >> 6;
   const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint32_t rmask = RS - 1;
-  const uint64_t step = (uint64_t)nw * kInvDocs;
-  uint64_t dd = d0 + wid;
-  InvGroup cur = inv_group(p, dd, d1, nw, r, false);
-  uint32_t c[kInvDocs];
-  if (dd < d1) inv_load(p, cur, lane, c);
+  constexpr int Q = kDfQuads, E = 4 * Q;
+  const uint64_t step = (uint64_t)nw * E;
+  uint64_t dd = d0 + (uint64_t)wid * E;
+  InvQuads<Q> cur = inv_quads<Q>(p, dd, d1, r);
+  uint32_t c[E];
+  inv_load<Q>(p, cur, 0, c);
   auto count = [&](uint32_t e) __attribute__((always_inline)) {
     const uint32_t sl = e & rmask;
     atomicAdd(&hist[sl >> 1], 1u << ((sl & 1u) << 4));
   };
   while (dd < d1) {
     const uint64_t dn = dd + step;
-    const InvGroup nxt = inv_group(p, dn, d1, nw, r, false);
-    uint32_t cn[kInvDocs];
-    if (dn < d1) inv_load(p, nxt, lane, cn);                       // next group in flight
+    const InvQuads<Q> nxt = inv_quads<Q>(p, dn, d1, r);
+    uint32_t cn[E];
+    inv_load<Q>(p, nxt, 0, cn);                                    // next group in flight
 #pragma unroll
-    for (int j = 0; j < kInvDocs; j++)
+    for (int j = 0; j < E; j++)
       if (c[j]) count(c[j]);
-    for (uint32_t off = lane + 64; off < cur.maxn; off += 64) {     // segments longer than 64
-      inv_load(p, cur, off, c);
+    const uint32_t maxn = inv_maxn<Q>(cur);
+    for (uint32_t off = 64; __any(off < maxn); off += 64) {        // segments longer than 64
+      inv_load<Q>(p, cur, off, c);
 #pragma unroll
-      for (int j = 0; j < kInvDocs; j++)
+      for (int j = 0; j < E; j++)
         if (c[j]) count(c[j]);
     }
     cur = nxt;
 #pragma unroll
-    for (int j = 0; j < kInvDocs; j++) c[j] = cn[j];
+    for (int j = 0; j < E; j++) c[j] = cn[j];
     dd = dn;
   }
   __syncthreads();
@@ -2731,34 +2766,43 @@ constexpr uint32_t kTmpTfEsc = (1u << (32 - kTmpTfShift)) - 1; // tf field value
 constexpr uint32_t kPartStreams = kRangeSlots / kSubSlots;  // 64
 static_assert(kTmpTfShift <= 23 && kPartStreams == 64, "temp word layout");
 
+// temp word of CSR entry e of the block's document dl
+__device__ __forceinline__ uint32_t part_word(const PostingParams &p, uint32_t e, uint32_t rmask, uint32_t dl) {
+  const uint32_t sl = e & rmask;
+  const uint32_t tf = csr_tf_field(e, p.range_shift);
+  return dl | ((sl & (kSubSlots - 1)) << 13) | (min(tf, kTmpTfEsc) << kTmpTfShift);
+}
+
+// entries past a segment's first 64 (c from inv_load; dl0 = the block-local
+// document of the lane in quad 0): appended to their streams straight from
+// the wave
+template <int Q>
 __device__ __forceinline__ void part_entries(const PostingParams &p, uint32_t *bcur, uint32_t rmask, uint64_t bb,
-                                             const InvGroup &g, uint64_t dd, uint32_t d0l, uint32_t stride,
-                                             const uint32_t *c) {
+                                             uint32_t dl0, const uint32_t *c) {
   const uint32_t lane = threadIdx.x & 63;
   constexpr uint32_t kNoop = kPartStreams;                    // idle lanes bump a spare cursor
 #pragma unroll
-  for (int j = 0; j < kInvDocs; j++) {
+  for (int j = 0; j < 4 * Q; j++) {
     const bool in = c[j] != 0;
     if (!__any(in)) continue;                                 // wave-uniform
     const uint32_t sl = c[j] & rmask;
-    const uint32_t dl = (uint32_t)(dd + (uint64_t)stride * j) - d0l;
-    const uint32_t tf = csr_tf_field(c[j], p.range_shift);
-    const uint32_t val = dl | ((sl & (kSubSlots - 1)) << 13) | (min(tf, kTmpTfEsc) << kTmpTfShift);
+    const uint32_t val = part_word(p, c[j], rmask, dl0 + (uint32_t)(j & ~3));
     const uint32_t pos = cursor_bump<kRangeBits - kSubBits + 1>(bcur, in ? sl >> kSubBits : kNoop, lane);
     if (in) p.post_tmp[bb + pos] = val;
   }
 }
 
 // Workgroup-wide staging (round 5).  All the workgroup's waves take their next
-// document group together (a round: nw * kInvDocs documents, up to 8 192
-// entries); the round's entries are counting-sorted by sub-range stream in LDS
-// and stored stream run by stream run, ~16x longer runs than wave-local
-// staging (one to two lines per store instruction instead of ~13).
+// document group together (a round: nw * 4 kPartQuads documents, up to
+// kPartStage entries); the round's entries are counting-sorted by sub-range
+// stream in LDS and stored stream run by stream run, ~16x longer runs than
+// wave-local staging (one to two lines per store instruction instead of ~13).
+constexpr uint32_t kPartStage = 16 * 4 * kPartQuads * 64;   // 12 288 entries at 3 quads: 60 KiB, two workgroups per CU
 __global__ void __launch_bounds__(1024) k_scatter_part(PostingParams p) {
   __shared__ uint32_t bcur[kPartStreams + 1];
   __shared__ uint32_t cnt[kPartStreams], soff[kPartStreams], gb[kPartStreams], tot_sh;
-  __shared__ uint32_t stage[16 * kInvDocs * 64];
-  __shared__ uint8_t sid[16 * kInvDocs * 64];
+  __shared__ uint32_t stage[kPartStage];
+  __shared__ uint8_t sid[kPartStage];
   const uint32_t lane = threadIdx.x & 63, nw = blockDim.x >> 6;
   const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   uint32_t b, r;
@@ -2777,32 +2821,23 @@ __global__ void __launch_bounds__(1024) k_scatter_part(PostingParams p) {
   const uint64_t bb = p.bbase[b];
   const uint64_t d0 = (uint64_t)b * kBlockDocs;
   const uint64_t d1 = d0 + kBlockDocs < p.n_docs ? d0 + kBlockDocs : p.n_docs;
-  const uint64_t step = (uint64_t)nw * kInvDocs;
+  constexpr int Q = kPartQuads, E = 4 * Q;
+  const uint64_t step = (uint64_t)nw * E;
   const uint32_t rounds = (uint32_t)((d1 - d0 + step - 1) / step);   // workgroup-uniform
-  uint64_t dd = d0 + wid;
-  InvGroup g = inv_group(p, dd, d1, nw, r, false);
-  uint32_t c[kInvDocs];
-  if (dd < d1) inv_load(p, g, lane, c);
-  else
-#pragma unroll
-    for (int j = 0; j < kInvDocs; j++) c[j] = 0;
+  uint64_t dd = d0 + (uint64_t)wid * E;                              // the wave's 4 Q consecutive documents
+  InvQuads<Q> g = inv_quads<Q>(p, dd, d1, r);
+  uint32_t c[E];
+  inv_load<Q>(p, g, 0, c);
   for (uint32_t k = 0; k < rounds; k++) {
     const uint64_t dn = dd + step;
-    const InvGroup gn = inv_group(p, dn, d1, nw, r, false);
-    uint32_t cn[kInvDocs];
+    const InvQuads<Q> gn = inv_quads<Q>(p, dn, d1, r);
+    uint32_t cn[E];
+    inv_load<Q>(p, gn, 0, cn);                                    // next group in flight
+    const uint32_t dl0 = (uint32_t)(dd - d0) + (lane >> 4);       // block-local document of the lane in quad 0
+    uint32_t rank[E];
 #pragma unroll
-    for (int j = 0; j < kInvDocs; j++) cn[j] = 0;
-    if (dn < d1) inv_load(p, gn, lane, cn);                       // next group in flight
-    uint32_t val[kInvDocs], rank[kInvDocs], sj[kInvDocs];
-#pragma unroll
-    for (int j = 0; j < kInvDocs; j++) {
-      const uint32_t sl = c[j] & rmask;
-      sj[j] = sl >> kSubBits;
-      const uint32_t dl = (uint32_t)(dd + (uint64_t)nw * j - d0);
-      const uint32_t tf = csr_tf_field(c[j], p.range_shift);
-      val[j] = dl | ((sl & (kSubSlots - 1)) << 13) | (min(tf, kTmpTfEsc) << kTmpTfShift);
-      rank[j] = c[j] != 0 ? atomicAdd(&cnt[sj[j]], 1u) : 0u;
-    }
+    for (int j = 0; j < E; j++)
+      rank[j] = c[j] != 0 ? atomicAdd(&cnt[(c[j] & rmask) >> kSubBits], 1u) : 0u;
     __syncthreads();                                              // the round's counts are complete
     if (wid == 0) {
       const uint32_t n = cnt[lane];
@@ -2814,11 +2849,12 @@ __global__ void __launch_bounds__(1024) k_scatter_part(PostingParams p) {
     }
     __syncthreads();                                              // offsets known
 #pragma unroll
-    for (int j = 0; j < kInvDocs; j++)
+    for (int j = 0; j < E; j++)
       if (c[j] != 0) {
-        const uint32_t at = soff[sj[j]] + rank[j];
-        stage[at] = val[j];
-        sid[at] = (uint8_t)sj[j];
+        const uint32_t sj = (c[j] & rmask) >> kSubBits;
+        const uint32_t at = soff[sj] + rank[j];
+        stage[at] = part_word(p, c[j], rmask, dl0 + (uint32_t)(j & ~3));
+        sid[at] = (uint8_t)sj;
       }
     __syncthreads();                                              // the round's entries are staged
     const uint32_t T = tot_sh;
@@ -2826,13 +2862,14 @@ __global__ void __launch_bounds__(1024) k_scatter_part(PostingParams p) {
       const uint32_t st = sid[ti];
       p.post_tmp[bb + gb[st] + (ti - soff[st])] = stage[ti];
     }
-    for (uint32_t off = lane + 64; off < g.maxn; off += 64) {    // segments longer than 64
-      inv_load(p, g, off, c);
-      part_entries(p, bcur, rmask, bb, g, dd, (uint32_t)d0, nw, c);
+    const uint32_t maxn = inv_maxn<Q>(g);
+    for (uint32_t off = 64; __any(off < maxn); off += 64) {      // segments longer than 64
+      inv_load<Q>(p, g, off, c);
+      part_entries<Q>(p, bcur, rmask, bb, dl0, c);
     }
     g = gn;
 #pragma unroll
-    for (int j = 0; j < kInvDocs; j++) c[j] = cn[j];
+    for (int j = 0; j < E; j++) c[j] = cn[j];
     dd = dn;
     // the next round's counts go to cnt (reset above); its stage / soff / gb
     // writes come after its first barrier, when every thread has left this

@@ -1258,7 +1258,9 @@ static int commit_once(tfidf_index *ix, Snapshot &S) {
 
   HIP_TRY(S.dict.reserve((size_t)3 * C * 8));          // lo, hi, reference occurrence (dict_device.h)
   HIP_TRY(ix->verify_defer.reserve((size_t)kVerifyCap * 16));
-  HIP_TRY(S.csr.reserve(row_cap * 4));
+  // + 16: the inversion reads row segments in 16-byte pieces, and the piece
+  // that holds the last row's last entry may end up to 12 bytes past it
+  HIP_TRY(S.csr.reserve(row_cap * 4 + 16));
   // escapes: each needs tf >= the field's escape value, and a row holds at
   // most row_cap tokens in all, so this bounds their number
   const uint64_t esc_cap = row_cap / csr_esc_value(S.range_shift) + 64;
