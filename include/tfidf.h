@@ -429,6 +429,69 @@ int tfidf_snippets_batch(tfidf_index *ix, const uint8_t *q_utf8, const uint64_t 
  * (any form): the chunks the item budget cut, and the final chunks after the
  * match budget cut those further (1, 1 when everything fitted). */
 int tfidf_last_highlight_chunks(const tfidf_index *ix, uint64_t *item_chunks, uint64_t *row_chunks);
+/* ---- fuzzy term lookup: the vocabulary terms within max_edits of a term ----
+ * (Lucene's FuzzyQuery term enumeration / DirectSpellChecker; the reference
+ * has no counterpart: QueryParser.escape neutralises '~'.)
+ * Vocabulary of a snapshot: every term of its dictionary with local df >= 1,
+ *   as lower-cased UTF-8 bytes.
+ * Input: n_terms byte strings (t_utf8, t_offsets[n_terms + 1], the layout of
+ *   q_utf8 / q_offsets).  A term is not tokenised; it is lower-cased per code
+ *   point as LowerCaseFilter does.  An empty term, one that is not strict
+ *   UTF-8, or one longer than 255 UTF-16 units has no candidates and n_within
+ *   0, without failing the call.
+ * Distance: optimal string alignment over Unicode code points: insert,
+ *   delete, substitute and transpose two adjacent code points cost 1 each, no
+ *   substring is edited twice (ca -> abc is 3).  max_edits is 0, 1 or 2.
+ * Prefix: with p = min(prefix_len, code points of the term), a candidate has
+ *   at least p code points and its first p equal the term's; the distance is
+ *   still taken over the whole strings.
+ * Candidates of a term: the vocabulary terms passing the prefix rule with
+ *   distance <= max_edits (the term itself at distance 0 when present), in
+ *   (distance ascending, df descending, term bytes ascending) order; the first
+ *   max_out (1..1024) are returned, n_within[i] counts them before truncation.
+ *   df is the shard's own document frequency in that snapshot, whatever
+ *   tfidf_set_global_* installed.
+ * Output, CSR: term i's candidates are [cand_offsets[i], cand_offsets[i + 1]);
+ *   candidate j's bytes are terms[term_offsets[j] .. term_offsets[j + 1]),
+ *   with df[j] and dist[j].  cand_offsets[n_terms + 1], n_within[n_terms],
+ *   *n_cands and *n_term_bytes are always written; term_offsets (cand_cap + 1
+ *   entries), terms, df and dist when n_cands <= cand_cap and n_term_bytes <=
+ *   terms_cap, else TFIDF_E_BUFFER.  Caps 0 with NULL payload pointers ask for
+ *   the sizes.  n_terms == 0 is legal.
+ * TFIDF_E_INVALID_ARG, nothing written: max_edits > 2, max_out outside
+ *   1..1024, n_terms > 65536, decreasing t_offsets.  TFIDF_E_STATE before the
+ *   first commit.
+ * Runs on a search context beside readers, tfidf_add_docs and tfidf_commit;
+ *   the reader forms see their own snapshot's vocabulary.  Scratch is bounded:
+ *   the input terms are scanned in chunks that fit the kernels' staging, and a
+ *   chunk whose counted candidates exceed 2^22 is filled by ranges of its
+ *   terms (one term at least).  *ms_device (may be NULL): HIP-event time of
+ *   the call's device work.
+ * tfidf_fuzzy_terms / tfidf_reader_fuzzy_terms: the batch of one, without the
+ *   two offsets arrays that one term does not need. */
+int tfidf_fuzzy_terms_batch(tfidf_index *ix, const uint8_t *t_utf8, const uint64_t *t_offsets, uint32_t n_terms,
+                            uint32_t max_edits, uint32_t prefix_len, uint32_t max_out, uint64_t *cand_offsets,
+                            uint64_t *n_within, uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap,
+                            uint32_t *df, uint8_t *dist, uint64_t cand_cap, uint64_t *n_cands,
+                            uint64_t *n_term_bytes, float *ms_device);
+int tfidf_reader_fuzzy_terms_batch(tfidf_reader *rd, const uint8_t *t_utf8, const uint64_t *t_offsets,
+                                   uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len, uint32_t max_out,
+                                   uint64_t *cand_offsets, uint64_t *n_within, uint64_t *term_offsets, uint8_t *terms,
+                                   uint64_t terms_cap, uint32_t *df, uint8_t *dist, uint64_t cand_cap,
+                                   uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device);
+int tfidf_fuzzy_terms(tfidf_index *ix, const uint8_t *term, uint64_t len, uint32_t max_edits, uint32_t prefix_len,
+                      uint32_t max_out, uint64_t *n_within, uint64_t *term_offsets, uint8_t *terms,
+                      uint64_t terms_cap, uint32_t *df, uint8_t *dist, uint64_t cand_cap, uint64_t *n_cands,
+                      uint64_t *n_term_bytes, float *ms_device);
+int tfidf_reader_fuzzy_terms(tfidf_reader *rd, const uint8_t *term, uint64_t len, uint32_t max_edits,
+                             uint32_t prefix_len, uint32_t max_out, uint64_t *n_within, uint64_t *term_offsets,
+                             uint8_t *terms, uint64_t terms_cap, uint32_t *df, uint8_t *dist, uint64_t cand_cap,
+                             uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device);
+/* Chunks of the last fuzzy lookup that ran on this index (any form): the scans
+ * of the dictionary (one per staged chunk of input terms) and the candidate
+ * chunks filled and sorted (1, 1 when everything fitted; 0, 0 when no input
+ * term could have candidates). */
+int tfidf_last_fuzzy_chunks(const tfidf_index *ix, uint64_t *scan_chunks, uint64_t *cand_chunks);
 /* Per-query device time of the last search call on this index (HIP events on the search's stream). */
 int tfidf_last_search_ms(const tfidf_index *ix, float *ms_scoring, float *ms_total);
 /* Device-time measurement of searches (HIP events around scoring; on by
@@ -787,6 +850,17 @@ int tfidf_node_snippets_batch(tfidf_node *n, const uint8_t *q_utf8, const uint64
                               uint64_t text_cap, uint64_t *text_offsets, uint64_t *doc_starts, uint64_t *starts,
                               uint32_t *lens, uint32_t *ordinals, uint64_t m_cap, uint64_t *match_offsets,
                               uint64_t *n_text, uint64_t *n_matches, float *ms_device);
+/* tfidf_fuzzy_terms_batch over the node, after tfidf_node_commit: every shard
+ * runs the batch at once on its own device, untruncated, and the host merges
+ * the shards' candidates by term bytes: df is the sum over the shards (u64
+ * here), n_within counts the distinct terms, the order and max_out apply to
+ * the merged lists.  A shard's failure fails the call with that shard's code.
+ * *ms_device is the largest of the shards' device times. */
+int tfidf_node_fuzzy_terms_batch(tfidf_node *n, const uint8_t *t_utf8, const uint64_t *t_offsets, uint32_t n_terms,
+                                 uint32_t max_edits, uint32_t prefix_len, uint32_t max_out, uint64_t *cand_offsets,
+                                 uint64_t *n_within, uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap,
+                                 uint64_t *df, uint8_t *dist, uint64_t cand_cap, uint64_t *n_cands,
+                                 uint64_t *n_term_bytes, float *ms_device);
 typedef struct tfidf_node_stats {
   uint64_t n_shards;
   uint64_t num_docs;      /* all shards */

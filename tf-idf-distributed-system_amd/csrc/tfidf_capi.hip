@@ -25,6 +25,7 @@
 #include "../../include/tfidf.h"
 #include "analysis.h"
 #include "compact_plan.h"
+#include "fuzzy_plan.h"
 #include "snippet_plan.h"
 #include "tfidf_common.h"
 #include "tfidf_internal.h"
@@ -361,6 +362,7 @@ struct SearchCtx {
   bool q_timing = true;
   DevMem q_in, q_out, cand, cand_n, out_doc, out_score, hits, hits_n, hits_c, hits_s, hits_P, ovf;
   DevMem hl_in, hl_cnt, hl_m, hl_s, hl_o;   // hit highlighting: plan, slice counts, matches, per-row ranges, packed output
+  DevMem fz_in, fz_hs, fz_c, fz_tmp;        // fuzzy lookup: staged terms + counters, hashed slots, candidates, sort scratch
   PinnedVec<uint32_t> q_host, q_res, q_cand_h;   // q_cand_h: fused single query's block candidates (host merge)
   std::vector<uint64_t> q_merge;
   std::vector<uint32_t> q_units;            // batch scoring units {q, b0, b1, 0} (run_scoring)
@@ -368,7 +370,8 @@ struct SearchCtx {
   float *res_score = nullptr;
   explicit SearchCtx(int d)
       : dev(d), q_in(d), q_out(d), cand(d), cand_n(d), out_doc(d), out_score(d), hits(d), hits_n(d), hits_c(d),
-        hits_s(d), hits_P(d), ovf(d), hl_in(d), hl_cnt(d), hl_m(d), hl_s(d), hl_o(d) {}
+        hits_s(d), hits_P(d), ovf(d), hl_in(d), hl_cnt(d), hl_m(d), hl_s(d), hl_o(d), fz_in(d), fz_hs(d), fz_c(d),
+        fz_tmp(d) {}
   int init() {
     DeviceGuard g(dev);
     if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess ||
@@ -415,6 +418,7 @@ struct tfidf_index {
   std::mutex ms_mu;
   float last_ms_scoring = 0, last_ms_total = 0;
   uint64_t last_hl_item_chunks = 0, last_hl_row_chunks = 0;   // of the last batched highlighting call (ms_mu)
+  uint64_t last_fz_scan_chunks = 0, last_fz_cand_chunks = 0;  // of the last fuzzy term lookup (ms_mu)
 
   // staged corpus (builder)
   std::shared_ptr<DevMem> text, offsets;   // offsets: u64[n_staged + 1]
@@ -3121,6 +3125,336 @@ extern "C" int tfidf_last_highlight_chunks(const tfidf_index *ix, uint64_t *item
   std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->ms_mu);
   if (item_chunks) *item_chunks = ix->last_hl_item_chunks;
   if (row_chunks) *row_chunks = ix->last_hl_row_chunks;
+  return TFIDF_OK;
+}
+
+// ---------------------------------------------------------------------------
+// fuzzy term lookup: the vocabulary terms within max_edits of each input term
+// (fuzzy_plan.h, kernels_fuzzy.hip).  Per scan chunk of input terms: one
+// counting pass over the dictionary (n_within and the scratch sizes), then per
+// candidate chunk a filling pass, the (term, dist, df) sort and the selection
+// of what the host orders: the first max_out candidates of a term and the tie
+// group of the max_out-th.  Only those candidates' strings are materialised
+// (exact keys from the host mirror, hashed ones from their reference
+// occurrence), where the byte order breaks the ties.
+
+constexpr uint64_t kFzCandBudget = 1ull << 22;   // candidates per fill: 96 MiB of keys and slots, both sort buffers
+constexpr uint32_t kFzHashedInit = 1u << 16;     // hashed slots listed before the list is grown and the scan redone
+
+static int fuzzy_on(tfidf_index *ix, Snapshot &S, const uint8_t *t_utf8, const uint64_t *t_offsets, uint32_t n_terms,
+                    uint32_t max_edits, uint32_t prefix_len, uint32_t max_out, FuzzyLists *out) {
+  out->ms_device = 0.0f;
+  out->cands.assign(n_terms, {});
+  out->n_within.assign(n_terms, 0);
+  // input terms -> lower-cased code points (none: a term without candidates)
+  std::vector<std::vector<uint32_t>> cps(n_terms);
+  std::vector<uint32_t> n_cps(n_terms, 0);
+  uint32_t buf[kMaxTokenLen];
+  bool any = false;
+  for (uint32_t i = 0; i < n_terms; i++) {
+    const uint64_t len = t_offsets[i + 1] - t_offsets[i];
+    if (len == 0 || len > 4ull * kMaxTokenLen) continue;
+    n_cps[i] = fz_decode_term(t_utf8 + t_offsets[i], len, buf);
+    cps[i].assign(buf, buf + n_cps[i]);
+    any = any || n_cps[i];
+  }
+  uint64_t n_scan = 0, n_fill = 0;
+  auto publish = [&]() {
+    std::lock_guard<std::mutex> lk(ix->ms_mu);
+    ix->last_fz_scan_chunks = n_scan;
+    ix->last_fz_cand_chunks = n_fill;
+  };
+  if (!any) { publish(); return TFIDF_OK; }
+  std::vector<uint64_t> cuts;
+  fz_plan_scan_chunks(n_cps.data(), n_terms, kFzChunkTerms, kFzChunkCps, &cuts);
+  const uint64_t budget = std::min<uint64_t>(hl_budget("TFIDF_FUZZY_CAND_BUDGET", kFzCandBudget), 1ull << 30);
+
+  CtxLease lease(ix);
+  if (lease.rc) return lease.rc;
+  SearchCtx &X = *lease.c;
+  const hipStream_t s = lease.stream();
+  DeviceGuard g(ix->cfg.device);
+  const int max_grid = ix->num_cus * 8;
+  HIP_TRY(hipEventRecord(X.ev[QEV_0], s));
+
+  // staged terms and counters: off[kFzChunkTerms + 1], cps[kFzChunkCps], counts[kFzChunkTerms], seg and
+  // out_off [kFzChunkTerms + 1] each, take[kFzChunkTerms], the fill cursor and the hashed-slot count
+  const size_t in_cps = (kFzChunkTerms + 1) * 4, in_cnt = in_cps + kFzChunkCps * 4, in_seg = in_cnt + kFzChunkTerms * 4,
+               in_oo = in_seg + (kFzChunkTerms + 1) * 4, in_take = in_oo + (kFzChunkTerms + 1) * 4,
+               in_cur = in_take + kFzChunkTerms * 4, in_end = in_cur + 8;
+  HIP_TRY(X.fz_in.reserve(in_end));
+  uint8_t *ib = X.fz_in.as<uint8_t>();
+  uint32_t *d_off = reinterpret_cast<uint32_t *>(ib), *d_cps = reinterpret_cast<uint32_t *>(ib + in_cps),
+           *d_cnt = reinterpret_cast<uint32_t *>(ib + in_cnt), *d_seg = reinterpret_cast<uint32_t *>(ib + in_seg),
+           *d_oo = reinterpret_cast<uint32_t *>(ib + in_oo), *d_take = reinterpret_cast<uint32_t *>(ib + in_take),
+           *d_cur = reinterpret_cast<uint32_t *>(ib + in_cur), *d_hsn = d_cur + 1;
+
+  FzScan a{};
+  a.dict = S.dict.as<uint64_t>();
+  a.df = S.df_dev();
+  a.C = S.C;
+  a.t_off = d_off;
+  a.t_cps = d_cps;
+  a.max_edits = max_edits;
+  a.prefix_len = prefix_len;
+  a.counts = d_cnt;
+  a.cursor = d_cur;
+  const uint8_t *d_text = S.text->as<uint8_t>();
+  bool listed = false;                     // the hashed slots are listed by the first counting scan
+  uint32_t hs_n = 0;
+
+  FzStage st;
+  std::vector<uint32_t> counts, seg, take, oo, h_slots;
+  std::vector<uint64_t> sub, h_keys;
+  std::string ts;
+  for (size_t ci = 0; ci + 1 < cuts.size(); ci++) {
+    const uint64_t t0 = cuts[ci], nt = cuts[ci + 1] - t0;
+    fz_stage_terms(cps, t0, t0 + nt, &st);
+    if (st.cps.empty()) continue;                                   // only terms without candidates
+    if (nt > kFzChunkTerms || st.cps.size() > kFzChunkCps) return fail(TFIDF_E_STATE, "fuzzy scan chunk over its limits");
+    n_scan++;
+    HIP_TRY(hipMemcpyAsync(d_off, st.off.data(), (nt + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_cps, st.cps.data(), st.cps.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, nt * 4, s));
+    a.n_terms = (uint32_t)nt;
+    a.t_off = d_off;
+    a.keys = nullptr;
+    a.slots = nullptr;
+    a.cap = 0;
+    a.hs_list = nullptr;
+    a.hs_cap = 0;
+    if (!listed) {
+      HIP_TRY(X.fz_hs.reserve((size_t)kFzHashedInit * 4));
+      HIP_TRY(hipMemsetAsync(d_hsn, 0, 4, s));
+      a.hs_list = X.fz_hs.as<uint32_t>();
+      a.hs_count = d_hsn;
+      a.hs_cap = (uint32_t)(X.fz_hs.bytes / 4);
+    }
+    HIP_TRY(launch_fz_scan(false, a, max_grid, s));
+    if (!listed) {
+      HIP_TRY(hipMemcpyAsync(&hs_n, d_hsn, 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      if (hs_n > a.hs_cap) {                                        // more hashed slots than the list held: list them again
+        HIP_TRY(X.fz_hs.reserve((size_t)hs_n * 4));
+        HIP_TRY(hipMemsetAsync(d_hsn, 0, 4, s));
+        FzScan l = a;
+        l.n_terms = 0;
+        l.hs_list = X.fz_hs.as<uint32_t>();
+        l.hs_cap = hs_n;
+        HIP_TRY(launch_fz_scan(false, l, max_grid, s));
+      }
+      listed = true;
+    }
+    a.hs_list = X.fz_hs.as<uint32_t>();
+    a.hs_count = nullptr;
+    a.hs_n = hs_n;
+    HIP_TRY(launch_fz_hashed(false, a, d_text, S.text_bytes, max_grid, s));
+    counts.resize(nt);
+    HIP_TRY(hipMemcpyAsync(counts.data(), d_cnt, nt * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint64_t t = 0; t < nt; t++) out->n_within[t0 + t] = counts[t];
+
+    sub.clear();
+    fz_plan_cand_chunks(counts.data(), 0, nt, budget, &sub);
+    for (size_t si = 0; si + 1 < sub.size(); si++) {
+      const uint64_t a0 = sub[si], na = sub[si + 1] - a0;
+      seg.assign(na + 1, 0);
+      uint64_t T = 0;
+      for (uint64_t t = 0; t < na; t++) {
+        T += counts[a0 + t];
+        if (T >= (1ull << 31)) return fail(TFIDF_E_INVALID_ARG, "more than 2^31 candidates for one term range");
+        seg[t + 1] = (uint32_t)T;
+      }
+      if (T == 0) continue;
+      n_fill++;
+      // candidates: keys [T] x 2 (sort in / out), slots [T] x 2
+      const size_t Tp = (T + 1) & ~(size_t)1;
+      HIP_TRY(X.fz_c.reserve(Tp * 24));
+      uint64_t *k_in = X.fz_c.as<uint64_t>(), *k_out = k_in + Tp;
+      uint32_t *s_in = reinterpret_cast<uint32_t *>(k_out + Tp), *s_out = s_in + Tp;
+      HIP_TRY(hipMemsetAsync(d_cur, 0, 4, s));
+      FzScan f = a;
+      f.t_off = d_off + a0;                 // the range's terms: offsets into the chunk's code points
+      f.n_terms = (uint32_t)na;
+      f.keys = k_in;
+      f.slots = s_in;
+      f.cap = (uint32_t)T;
+      HIP_TRY(launch_fz_scan(true, f, max_grid, s));
+      HIP_TRY(launch_fz_hashed(true, f, d_text, S.text_bytes, max_grid, s));
+      size_t tmp_bytes = 0;
+      HIP_TRY(fz_sort(nullptr, &tmp_bytes, k_in, k_out, s_in, s_out, (uint32_t)T, s));
+      HIP_TRY(X.fz_tmp.reserve(tmp_bytes));
+      tmp_bytes = X.fz_tmp.bytes;
+      HIP_TRY(fz_sort(X.fz_tmp.p, &tmp_bytes, k_in, k_out, s_in, s_out, (uint32_t)T, s));
+      // what the host orders: everything (max_out == 0), or the selection packed into the sort's input buffers
+      uint64_t n_take = T;
+      oo = seg;
+      const uint64_t *src_k = k_out;
+      const uint32_t *src_s = s_out;
+      if (max_out) {
+        take.resize(na);
+        HIP_TRY(hipMemcpyAsync(d_seg, seg.data(), (na + 1) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(launch_fz_select(k_out, d_seg, (uint32_t)na, max_out, d_take, s));
+        HIP_TRY(hipMemcpyAsync(take.data(), d_take, na * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        n_take = 0;
+        for (uint64_t t = 0; t < na; t++) {
+          if (take[t] > seg[t + 1] - seg[t]) return fail(TFIDF_E_STATE, "fuzzy selection past its segment");
+          oo[t] = (uint32_t)n_take;
+          n_take += take[t];
+        }
+        oo[na] = (uint32_t)n_take;
+        HIP_TRY(hipMemcpyAsync(d_oo, oo.data(), (na + 1) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(launch_fz_gather(k_out, s_out, d_seg, d_oo, (uint32_t)na, k_in, s_in, s));
+        src_k = k_in;
+        src_s = s_in;
+      }
+      h_keys.resize(n_take);
+      h_slots.resize(n_take);
+      HIP_TRY(hipMemcpyAsync(h_keys.data(), src_k, n_take * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(h_slots.data(), src_s, n_take * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      for (uint64_t t = 0; t < na; t++) {
+        std::vector<FuzzyCand> &L = out->cands[t0 + a0 + t];
+        L.reserve(oo[t + 1] - oo[t]);
+        for (uint32_t i = oo[t]; i < oo[t + 1]; i++) {
+          if (fz_key_term(h_keys[i]) != t || h_slots[i] >= S.C)
+            return fail(TFIDF_E_STATE, "fuzzy candidate %u of term %llu is out of place", i, (unsigned long long)t);
+          if (int rc = slot_term(S, h_slots[i], &ts)) return rc;
+          L.push_back(FuzzyCand{ts, fz_key_df(h_keys[i]), fz_key_dist(h_keys[i])});
+        }
+        std::sort(L.begin(), L.end(), [](const FuzzyCand &x, const FuzzyCand &y) {
+          if (x.dist != y.dist) return x.dist < y.dist;
+          if (x.df != y.df) return x.df > y.df;
+          return x.term < y.term;
+        });
+        if (max_out && L.size() > max_out) L.resize(max_out);
+      }
+    }
+  }
+  HIP_TRY(hipEventRecord(X.ev[QEV_1], s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipEventElapsedTime(&out->ms_device, X.ev[QEV_0], X.ev[QEV_1]));
+  publish();
+  return TFIDF_OK;
+}
+
+static int fuzzy_check_args(const uint8_t *t_utf8, const uint64_t *t_offsets, uint32_t n_terms, uint32_t max_edits,
+                            uint32_t max_out, bool all) {
+  if (n_terms > kFzMaxTerms) return fail(TFIDF_E_INVALID_ARG, "more than %u terms in one call", kFzMaxTerms);
+  if (max_edits > kFzMaxEdits) return fail(TFIDF_E_INVALID_ARG, "max_edits %u above %u", max_edits, kFzMaxEdits);
+  if (!all && (max_out < 1 || max_out > kFzMaxOut))
+    return fail(TFIDF_E_INVALID_ARG, "max_out %u outside 1..%u", max_out, kFzMaxOut);
+  if (n_terms && (!t_offsets || (!t_utf8 && t_offsets[n_terms] != t_offsets[0])))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  for (uint32_t i = 0; i < n_terms; i++)
+    if (t_offsets[i + 1] < t_offsets[i]) return fail(TFIDF_E_INVALID_ARG, "t_offsets decrease at term %u", i);
+  return TFIDF_OK;
+}
+
+int tfidf::index_fuzzy_terms(tfidf_index *ix, const uint8_t *t_utf8, const uint64_t *t_offsets, uint32_t n_terms,
+                             uint32_t max_edits, uint32_t prefix_len, uint32_t max_out, FuzzyLists *out) {
+  if (!ix || !out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (int rc = fuzzy_check_args(t_utf8, t_offsets, n_terms, max_edits, max_out, max_out == 0)) return rc;
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "fuzzy lookup before commit");
+  return fuzzy_on(ix, *snap, t_utf8, t_offsets, n_terms, max_edits, prefix_len, max_out, out);
+}
+
+// the CSR output of the fuzzy calls: offsets, n_within and the totals always, the payload when it fits
+static int fuzzy_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *t_utf8, const uint64_t *t_offsets,
+                          uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len, uint32_t max_out,
+                          uint64_t *cand_offsets, uint64_t *n_within, uint64_t *term_offsets, uint8_t *terms,
+                          uint64_t terms_cap, uint32_t *df, uint8_t *dist, uint64_t cand_cap, uint64_t *n_cands,
+                          uint64_t *n_term_bytes, float *ms_device) {
+  if (int rc = fuzzy_check_args(t_utf8, t_offsets, n_terms, max_edits, max_out, false)) return rc;
+  if (!cand_offsets || (n_terms && !n_within) || !n_cands || !n_term_bytes)
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (ms_device) *ms_device = 0.0f;
+  FuzzyLists fl;
+  if (int rc = fuzzy_on(ix, S, t_utf8, t_offsets, n_terms, max_edits, prefix_len, max_out, &fl)) return rc;
+  if (ms_device) *ms_device = fl.ms_device;
+  uint64_t nc = 0, nb = 0;
+  cand_offsets[0] = 0;
+  for (uint32_t i = 0; i < n_terms; i++) {
+    n_within[i] = fl.n_within[i];
+    nc += fl.cands[i].size();
+    for (const FuzzyCand &c : fl.cands[i]) nb += c.term.size();
+    cand_offsets[i + 1] = nc;
+  }
+  *n_cands = nc;
+  *n_term_bytes = nb;
+  if (nc > cand_cap || nb > terms_cap || (nc && (!term_offsets || !df || !dist)) || (nb && !terms))
+    return fail(TFIDF_E_BUFFER, "need %llu candidate slots and %llu term bytes", (unsigned long long)nc,
+                (unsigned long long)nb);
+  uint64_t at = 0, b = 0;
+  if (term_offsets) term_offsets[0] = 0;
+  for (uint32_t i = 0; i < n_terms; i++)
+    for (const FuzzyCand &c : fl.cands[i]) {
+      memcpy(terms + b, c.term.data(), c.term.size());
+      b += c.term.size();
+      df[at] = (uint32_t)c.df;
+      dist[at] = (uint8_t)c.dist;
+      term_offsets[++at] = b;
+    }
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_reader_fuzzy_terms_batch(tfidf_reader *rd, const uint8_t *t_utf8, const uint64_t *t_offsets,
+                                              uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len,
+                                              uint32_t max_out, uint64_t *cand_offsets, uint64_t *n_within,
+                                              uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *df,
+                                              uint8_t *dist, uint64_t cand_cap, uint64_t *n_cands,
+                                              uint64_t *n_term_bytes, float *ms_device) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  return fuzzy_batch_on(rd->ix, *rd->S, t_utf8, t_offsets, n_terms, max_edits, prefix_len, max_out, cand_offsets,
+                        n_within, term_offsets, terms, terms_cap, df, dist, cand_cap, n_cands, n_term_bytes, ms_device);
+}
+
+extern "C" int tfidf_fuzzy_terms_batch(tfidf_index *ix, const uint8_t *t_utf8, const uint64_t *t_offsets,
+                                       uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len, uint32_t max_out,
+                                       uint64_t *cand_offsets, uint64_t *n_within, uint64_t *term_offsets,
+                                       uint8_t *terms, uint64_t terms_cap, uint32_t *df, uint8_t *dist,
+                                       uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes,
+                                       float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  if (int rc = fuzzy_check_args(t_utf8, t_offsets, n_terms, max_edits, max_out, false)) return rc;
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "fuzzy lookup before commit");
+  return fuzzy_batch_on(ix, *snap, t_utf8, t_offsets, n_terms, max_edits, prefix_len, max_out, cand_offsets, n_within,
+                        term_offsets, terms, terms_cap, df, dist, cand_cap, n_cands, n_term_bytes, ms_device);
+}
+
+// the batch of one, without the offsets arrays of the input and of the terms' candidates
+extern "C" int tfidf_reader_fuzzy_terms(tfidf_reader *rd, const uint8_t *term, uint64_t len, uint32_t max_edits,
+                                        uint32_t prefix_len, uint32_t max_out, uint64_t *n_within,
+                                        uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *df,
+                                        uint8_t *dist, uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes,
+                                        float *ms_device) {
+  if (!n_within || (!term && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t t_off[2] = {0, len};
+  uint64_t c_off[2];
+  return tfidf_reader_fuzzy_terms_batch(rd, term, t_off, 1, max_edits, prefix_len, max_out, c_off, n_within,
+                                        term_offsets, terms, terms_cap, df, dist, cand_cap, n_cands, n_term_bytes,
+                                        ms_device);
+}
+
+extern "C" int tfidf_fuzzy_terms(tfidf_index *ix, const uint8_t *term, uint64_t len, uint32_t max_edits,
+                                 uint32_t prefix_len, uint32_t max_out, uint64_t *n_within, uint64_t *term_offsets,
+                                 uint8_t *terms, uint64_t terms_cap, uint32_t *df, uint8_t *dist, uint64_t cand_cap,
+                                 uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device) {
+  if (!n_within || (!term && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t t_off[2] = {0, len};
+  uint64_t c_off[2];
+  return tfidf_fuzzy_terms_batch(ix, term, t_off, 1, max_edits, prefix_len, max_out, c_off, n_within, term_offsets,
+                                 terms, terms_cap, df, dist, cand_cap, n_cands, n_term_bytes, ms_device);
+}
+
+extern "C" int tfidf_last_fuzzy_chunks(const tfidf_index *ix, uint64_t *scan_chunks, uint64_t *cand_chunks) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->ms_mu);
+  if (scan_chunks) *scan_chunks = ix->last_fz_scan_chunks;
+  if (cand_chunks) *cand_chunks = ix->last_fz_cand_chunks;
   return TFIDF_OK;
 }
 

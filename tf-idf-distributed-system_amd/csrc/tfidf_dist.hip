@@ -28,6 +28,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <functional>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -2203,6 +2204,74 @@ extern "C" int tfidf_node_snippets_batch(tfidf_node *n, const uint8_t *q_utf8, c
   o.n_matches = n_matches;
   o.ms_device = ms_device;
   return node_highlight(n, q_utf8, q_offsets, n_q, docs, doc_offsets, o);
+}
+
+// ---------------------------------------------------------------------------
+// fuzzy term lookup over the node: every shard's untruncated candidates, merged by term bytes
+
+extern "C" int tfidf_node_fuzzy_terms_batch(tfidf_node *n, const uint8_t *t_utf8, const uint64_t *t_offsets,
+                                            uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len,
+                                            uint32_t max_out, uint64_t *cand_offsets, uint64_t *n_within,
+                                            uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint64_t *df,
+                                            uint8_t *dist, uint64_t cand_cap, uint64_t *n_cands,
+                                            uint64_t *n_term_bytes, float *ms_device) {
+  if (!n || !cand_offsets || (n_terms && (!n_within || !t_offsets)) || !n_cands || !n_term_bytes)
+    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (max_out < 1 || max_out > 1024) return errf(TFIDF_E_INVALID_ARG, "max_out %u outside 1..1024", max_out);
+  if (max_edits > 2) return errf(TFIDF_E_INVALID_ARG, "max_edits %u above 2", max_edits);
+  if (n_terms > 65536) return errf(TFIDF_E_INVALID_ARG, "more than 65536 terms in one call");
+  std::lock_guard<std::mutex> lk(n->mu);
+  if (ms_device) *ms_device = 0.0f;
+  if (!n->committed) return errf(TFIDF_E_STATE, "fuzzy lookup before tfidf_node_commit");
+  const size_t G = n->shards.size();
+  std::vector<FuzzyLists> sh(G);
+  if (int rc = n->pool->run([&](uint32_t g) {
+        return index_fuzzy_terms(n->shards[g], t_utf8, t_offsets, n_terms, max_edits, prefix_len, 0, &sh[g]);
+      }))
+    return rc;
+  // per input term: the shards' candidates by term bytes (df summed), then the order of the single index
+  std::vector<std::vector<FuzzyCand>> merged(n_terms);
+  uint64_t nc = 0, nb = 0;
+  cand_offsets[0] = 0;
+  for (uint32_t i = 0; i < n_terms; i++) {
+    std::map<std::string, FuzzyCand> by;
+    for (size_t g = 0; g < G; g++)
+      for (const FuzzyCand &c : sh[g].cands[i]) {
+        auto it = by.find(c.term);
+        if (it == by.end()) by.emplace(c.term, c);
+        else it->second.df += c.df;
+      }
+    std::vector<FuzzyCand> &L = merged[i];
+    for (auto &kv : by) L.push_back(kv.second);
+    std::sort(L.begin(), L.end(), [](const FuzzyCand &x, const FuzzyCand &y) {
+      if (x.dist != y.dist) return x.dist < y.dist;
+      if (x.df != y.df) return x.df > y.df;
+      return x.term < y.term;
+    });
+    n_within[i] = L.size();
+    if (L.size() > max_out) L.resize(max_out);
+    nc += L.size();
+    for (const FuzzyCand &c : L) nb += c.term.size();
+    cand_offsets[i + 1] = nc;
+  }
+  *n_cands = nc;
+  *n_term_bytes = nb;
+  if (ms_device)
+    for (const FuzzyLists &f : sh) *ms_device = std::max(*ms_device, f.ms_device);
+  if (nc > cand_cap || nb > terms_cap || (nc && (!term_offsets || !df || !dist)) || (nb && !terms))
+    return errf(TFIDF_E_BUFFER, "need %llu candidate slots and %llu term bytes", (unsigned long long)nc,
+                (unsigned long long)nb);
+  uint64_t at = 0, b = 0;
+  if (term_offsets) term_offsets[0] = 0;
+  for (uint32_t i = 0; i < n_terms; i++)
+    for (const FuzzyCand &c : merged[i]) {
+      memcpy(terms + b, c.term.data(), c.term.size());
+      b += c.term.size();
+      df[at] = c.df;
+      dist[at] = (uint8_t)c.dist;
+      term_offsets[++at] = b;
+    }
+  return TFIDF_OK;
 }
 
 extern "C" int tfidf_node_stats_get(const tfidf_node *n, tfidf_node_stats *out) {

@@ -6,6 +6,8 @@
 #include <stdlib.h>
 
 #include <atomic>
+#include <string>
+#include <vector>
 
 #include "tfidf_common.h"
 
@@ -425,6 +427,35 @@ hipError_t vocab_reduce(const uint64_t *records, uint64_t n, uint64_t *table, ui
                         uint32_t *rslot, uint32_t *out, unsigned long long *n_unique, hipStream_t s);
 hipError_t vocab_import(const uint32_t *sent_slot, const uint32_t *gdf_in, uint64_t n, uint32_t *gdf, hipStream_t s);
 
+// --- fuzzy term lookup (kernels_fuzzy.hip; rules in fuzzy_plan.h) ---
+// One pass of a chunk of staged input terms over the dictionary.  t_off[i] ..
+// t_off[i + 1] index t_cps (lower-cased code points; an empty range = a term
+// without candidates); n_terms <= kFzChunkTerms, t_off[n_terms] <= kFzChunkCps.
+struct FzScan {
+  const uint64_t *dict;       // lo[C], hi[C], ref[C]
+  const uint32_t *df;         // per slot (Snapshot::df_dev)
+  uint32_t C;
+  const uint32_t *t_off, *t_cps;
+  uint32_t n_terms, max_edits, prefix_len;
+  uint32_t *counts;           // count pass: survivors per staged term (zeroed before)
+  uint64_t *keys;             // fill pass: fz_sort_key per survivor, its slot, the append cursor (zeroed
+  uint32_t *slots;            // before) and the capacity the counts gave
+  uint32_t *cursor;
+  uint32_t cap;
+  uint32_t *hs_list;          // hashed slots: compacted by the count scan (hs_count zeroed before; entries
+  uint32_t *hs_count;         // past hs_cap are counted, not stored), read by k_fz_hashed (hs_n of them)
+  uint32_t hs_cap, hs_n;
+};
+hipError_t launch_fz_scan(bool fill, const FzScan &a, int max_grid, hipStream_t s);
+hipError_t launch_fz_hashed(bool fill, const FzScan &a, const uint8_t *text, uint64_t text_bytes, int max_grid,
+                            hipStream_t s);
+hipError_t fz_sort(void *tmp, size_t *tmp_bytes, const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *slots_in,
+                   uint32_t *slots_out, uint32_t n, hipStream_t s);
+hipError_t launch_fz_select(const uint64_t *keys, const uint32_t *seg, uint32_t n_terms, uint32_t max_out,
+                            uint32_t *take, hipStream_t s);
+hipError_t launch_fz_gather(const uint64_t *keys, const uint32_t *slots, const uint32_t *seg, const uint32_t *out_off,
+                            uint32_t n_terms, uint64_t *o_keys, uint32_t *o_slots, hipStream_t s);
+
 // --- index internals the node-level orchestration reads (tfidf_capi.hip) ---
 }  // namespace tfidf
 struct tfidf_index;
@@ -436,6 +467,20 @@ bool index_committed(const tfidf_index *ix);
 uint64_t index_num_docs(const tfidf_index *ix);
 uint64_t index_generation(const tfidf_index *ix);   // successful commits so far
 int set_error(int code, const char *msg);       // sets tfidf_last_error() of the calling thread
+// fuzzy term lookup on the snapshot published now: per input term its ordered
+// candidates (at most max_out; 0 = all of them) and their count before truncation
+struct FuzzyCand {
+  std::string term;
+  uint64_t df;
+  uint32_t dist;
+};
+struct FuzzyLists {
+  std::vector<std::vector<FuzzyCand>> cands;
+  std::vector<uint64_t> n_within;
+  float ms_device = 0.0f;
+};
+int index_fuzzy_terms(tfidf_index *ix, const uint8_t *t_utf8, const uint64_t *t_offsets, uint32_t n_terms,
+                      uint32_t max_edits, uint32_t prefix_len, uint32_t max_out, FuzzyLists *out);
 // device-key searches on a reader's pinned snapshot (tfidf_reader_open)
 int reader_batch_keys_device(tfidf_reader *rd, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
                              uint32_t k, uint64_t doc_base, void *d_keys);

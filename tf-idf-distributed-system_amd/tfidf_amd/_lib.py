@@ -78,6 +78,16 @@ U64P = C.POINTER(C.c_uint64)
 F32P = C.POINTER(C.c_float)
 F64P = C.POINTER(C.c_double)
 
+
+def _fuzzy_batch_sig(df):
+    """tfidf_[reader_|node_]fuzzy_terms_batch; df is u32 per shard, u64 over a node."""
+    return (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, U64P, U64P, U64P, VP,
+                      C.c_uint64, df, U8P, C.c_uint64, U64P, U64P, F32P])
+
+
+_FUZZY_SINGLE_SIG = (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, U64P, U64P, VP,
+                               C.c_uint64, U32P, U8P, C.c_uint64, U64P, U64P, F32P])
+
 SIGNATURES = {
     "tfidf_version": (C.c_char_p, []),
     "tfidf_last_error": (C.c_char_p, []),
@@ -113,6 +123,11 @@ SIGNATURES = {
     "tfidf_snippets_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U32P, U64P, C.c_uint32, VP, C.c_uint64,
                                        U64P, U64P, U64P, U32P, U32P, C.c_uint64, U64P, U64P, U64P, F32P]),
     "tfidf_last_highlight_chunks": (C.c_int, [VP, U64P, U64P]),
+    "tfidf_fuzzy_terms_batch": _fuzzy_batch_sig(U32P),
+    "tfidf_reader_fuzzy_terms_batch": _fuzzy_batch_sig(U32P),
+    "tfidf_fuzzy_terms": _FUZZY_SINGLE_SIG,
+    "tfidf_reader_fuzzy_terms": _FUZZY_SINGLE_SIG,
+    "tfidf_last_fuzzy_chunks": (C.c_int, [VP, U64P, U64P]),
     "tfidf_query_positive_terms": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, U64P, U64P]),
     "tfidf_set_hash_attempt": (C.c_int, [VP, C.c_uint32]),
     "tfidf_get_commit_timing": (C.c_int, [VP, C.POINTER(CommitTiming)]),
@@ -199,6 +214,7 @@ SIGNATURES = {
                                            C.c_uint64, U64P, U64P, F32P]),
     "tfidf_node_snippets_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U64P, U64P, C.c_uint32, VP, C.c_uint64,
                                             U64P, U64P, U64P, U32P, U32P, C.c_uint64, U64P, U64P, U64P, F32P]),
+    "tfidf_node_fuzzy_terms_batch": _fuzzy_batch_sig(U64P),
     "tfidf_node_last_failed": (C.c_int, [VP, U64P]),
     "tfidf_node_stats_get": (C.c_int, [VP, VP]),
     "tfidf_device_free": (C.c_int, [C.c_int, VP]),

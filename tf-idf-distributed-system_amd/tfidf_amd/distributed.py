@@ -477,6 +477,15 @@ class Node:
         return E._per_query(E._snippet_lists(a[:8]), a[8])
 
 
+    def fuzzy_terms_batch(self, terms, max_edits=2, prefix_len=0, max_out=10):
+        """ShardIndex.fuzzy_terms_batch over the node's vocabulary: every shard
+        looks the batch up at once, df is summed over the shards and n_within
+        counts distinct terms (tfidf_node_fuzzy_terms_batch)."""
+        from . import engine as E
+        return E._fuzzy_lists(E._fuzzy_batch_arrays(L.load().tfidf_node_fuzzy_terms_batch, self._h, terms, max_edits,
+                                                    prefix_len, max_out, df_dtype=np.uint64))
+
+
 class NodeStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("n_shards", "num_docs", "doc_count", "sum_ttf", "num_terms", "transport")]
 

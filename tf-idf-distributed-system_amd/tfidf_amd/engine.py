@@ -217,6 +217,67 @@ def _snippets_batch_arrays(fn, handle, queries, docs_per_query, max_bytes, m_cap
             ms.value, d_offs)
 
 
+def _fuzzy_batch_arrays(fn, handle, terms, max_edits, prefix_len, max_out, df_dtype=np.uint32):
+    """tfidf_[reader_|node_]fuzzy_terms_batch: one call with room for max_out
+    candidates per term (32 bytes each on average), once more with the sizes
+    the library reports when that was too small.  -> (cand offsets uint64[n +
+    1], n_within uint64[n], term offsets uint64[m + 1], term blob bytes, df[m],
+    dist uint8[m], ms_device)."""
+    terms = list(terms)
+    blob, t_offs = _key_arrays(terms)
+    n = len(terms)
+    c_offs = np.zeros(n + 1, np.uint64)
+    within = np.zeros(max(n, 1), np.uint64)
+    nc, nb, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+    dfc = np.ctypeslib.as_ctypes_type(df_dtype)
+    m_cap = min(n * max(int(max_out), 0), 1 << 20)
+    b_cap = 32 * m_cap
+    for _ in range(2):
+        t_out = np.zeros(m_cap + 1, np.uint64)
+        text = np.empty(max(b_cap, 1), np.uint8)
+        df = np.zeros(max(m_cap, 1), df_dtype)
+        dist = np.zeros(max(m_cap, 1), np.uint8)
+        rc = fn(handle, blob, L.ptr(t_offs, C.c_uint64), n, max_edits, prefix_len, max_out,
+                L.ptr(c_offs, C.c_uint64), L.ptr(within, C.c_uint64), L.ptr(t_out, C.c_uint64),
+                text.ctypes.data_as(C.c_void_p), b_cap, L.ptr(df, dfc), L.ptr(dist, C.c_uint8), m_cap, C.byref(nc),
+                C.byref(nb), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        m_cap, b_cap = nc.value, nb.value
+    L.check(rc)
+    m, b = nc.value, nb.value
+    return c_offs, within[:n], t_out[:m + 1], text[:b].tobytes(), df[:m], dist[:m], ms.value
+
+
+def _fuzzy_lists(arrays):
+    """-> per input term ([(term bytes, df, dist)], n_within)."""
+    c_offs, within, t_out, text, df, dist, _ = arrays
+    c, t, f, d = c_offs.tolist(), t_out.tolist(), df.tolist(), dist.tolist()
+    cands = [(text[t[j]:t[j + 1]], f[j], d[j]) for j in range(len(t) - 1)]
+    return [(cands[c[i]:c[i + 1]], int(within[i])) for i in range(len(c) - 1)]
+
+
+def _fuzzy_single(fn, handle, term, max_edits, prefix_len, max_out):
+    """tfidf_fuzzy_terms / tfidf_reader_fuzzy_terms, sized as _fuzzy_batch_arrays sizes the batch."""
+    within, nc, nb, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+    m_cap = min(max(int(max_out), 0), 1 << 20)
+    b_cap = 32 * m_cap
+    for _ in range(2):
+        t_out = np.zeros(m_cap + 1, np.uint64)
+        text = np.empty(max(b_cap, 1), np.uint8)
+        df = np.zeros(max(m_cap, 1), np.uint32)
+        dist = np.zeros(max(m_cap, 1), np.uint8)
+        rc = fn(handle, term, len(term), max_edits, prefix_len, max_out, C.byref(within), L.ptr(t_out, C.c_uint64),
+                text.ctypes.data_as(C.c_void_p), b_cap, L.ptr(df, C.c_uint32), L.ptr(dist, C.c_uint8), m_cap,
+                C.byref(nc), C.byref(nb), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        m_cap, b_cap = nc.value, nb.value
+    L.check(rc)
+    raw, t = text[:nb.value].tobytes(), t_out.tolist()
+    return [(raw[t[j]:t[j + 1]], int(df[j]), int(dist[j])) for j in range(nc.value)], within.value
+
+
 def _per_query(rows, d_offs):
     f = d_offs.tolist()
     return [rows[f[i]:f[i + 1]] for i in range(len(f) - 1)]
@@ -360,6 +421,28 @@ class ShardIndex:
         this index or one of its readers (tfidf_last_highlight_chunks)."""
         a, b = C.c_uint64(), C.c_uint64()
         L.check(L.load().tfidf_last_highlight_chunks(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def fuzzy_terms(self, term: bytes, max_edits=2, prefix_len=0, max_out=10):
+        """([(term bytes, df, dist)], n_within): the vocabulary terms within
+        ``max_edits`` (0..2) edits of ``term`` (optimal string alignment over
+        code points) that share its first ``prefix_len`` code points, in
+        (dist, df descending, bytes) order, at most ``max_out`` (1..1024) of
+        the n_within there are; df is this shard's own (tfidf_fuzzy_terms)."""
+        return _fuzzy_single(L.load().tfidf_fuzzy_terms, self._h, term, max_edits, prefix_len, max_out)
+
+    def fuzzy_terms_batch(self, terms, max_edits=2, prefix_len=0, max_out=10):
+        """[fuzzy_terms(t, ...) for t in terms] from one pass over the
+        dictionary per chunk of terms (tfidf_fuzzy_terms_batch); a term that is
+        empty, not UTF-8 or longer than 255 UTF-16 units gives ([], 0)."""
+        return _fuzzy_lists(_fuzzy_batch_arrays(L.load().tfidf_fuzzy_terms_batch, self._h, terms, max_edits,
+                                                prefix_len, max_out))
+
+    def last_fuzzy_chunks(self):
+        """(dictionary scans, candidate chunks) of the last fuzzy lookup on
+        this index or one of its readers (tfidf_last_fuzzy_chunks)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        L.check(L.load().tfidf_last_fuzzy_chunks(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def set_hash_attempt(self, attempt):
@@ -712,6 +795,19 @@ class Reader:
         """ShardIndex.snippets_batch on this reader's snapshot."""
         a = self.snippets_batch_arrays(queries, docs_per_query, max_bytes)
         return _per_query(_snippet_lists(a[:8]), a[8])
+
+    def fuzzy_terms(self, term: bytes, max_edits=2, prefix_len=0, max_out=10):
+        """ShardIndex.fuzzy_terms on this reader's snapshot."""
+        return _fuzzy_single(L.load().tfidf_reader_fuzzy_terms, self._h, term, max_edits, prefix_len, max_out)
+
+    def fuzzy_terms_batch_arrays(self, terms, max_edits=2, prefix_len=0, max_out=10):
+        """(cand offsets, n_within, term offsets, term blob, df, dist, ms_device) of tfidf_reader_fuzzy_terms_batch."""
+        return _fuzzy_batch_arrays(L.load().tfidf_reader_fuzzy_terms_batch, self._h, terms, max_edits, prefix_len,
+                                   max_out)
+
+    def fuzzy_terms_batch(self, terms, max_edits=2, prefix_len=0, max_out=10):
+        """ShardIndex.fuzzy_terms_batch on this reader's snapshot."""
+        return _fuzzy_lists(self.fuzzy_terms_batch_arrays(terms, max_edits, prefix_len, max_out))
 
     def doc_keys(self):
         lib = L.load()

@@ -12,9 +12,10 @@ maintainer adds to the Java classes themselves.
                             Document_and_Data/Document.java:6-53
 """
 import os
+import re
 
 from . import _lib as L
-from .engine import ShardIndex, leader_merge
+from .engine import ShardIndex, leader_merge, query_positive_terms
 
 
 def extract_text(data: bytes) -> bytes:
@@ -190,6 +191,28 @@ class Worker:
                     info["matches"] = [[st, ln] for st, ln, _ in ms]
                     out[i].append(info)
         return out
+
+    # No reference counterpart (QueryParser.escape neutralises '~'): a query
+    # whose terms are misspelt is answered with the nearest spelling the index
+    # holds.  Every positive term of the query is looked up in one batched
+    # fuzzy call; a term that is not in the vocabulary itself is replaced by
+    # its first candidate (distance, then df, then bytes), if it has one.
+    # -> (corrected query or None, hits of the corrected-or-original query)
+    def search_did_you_mean(self, query: str, max_edits=2):
+        q = query.encode()
+        with self.index.reader() as rd:
+            terms = query_positive_terms(q)
+            corrected = query
+            for t, (cands, _) in zip(terms, rd.fuzzy_terms_batch(terms, max_edits, 0, 1)):
+                if cands and cands[0][2] != 0:
+                    # the misspelt word where the query spells it (any case): operators and boosts stay
+                    best = cands[0][0].decode()
+                    corrected = re.sub(r"(?<!\w)%s(?!\w)" % re.escape(t.decode()), lambda m: best, corrected,
+                                       flags=re.IGNORECASE)
+            changed = corrected != query
+            hits = rd.search(corrected.encode() if changed else q, 0)
+            out = [document_score_info(rd.doc_key(d).decode(), s) for d, s in hits]
+        return (corrected if changed else None), out
 
     # Worker.java:175-186 /worker/process: any exception -> empty list
     def process_documents(self, search_query: str):
