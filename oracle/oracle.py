@@ -190,9 +190,12 @@ class OracleIndex:
     def doc_terms(self, d):
         """{term bytes: tf} for doc d."""
         cap = self.doc_len(d) + 1
-        buf = C.create_string_buffer(cap * 260 + 16)
         tfs = np.zeros(cap, np.uint32)
-        n = lib().orc_doc_terms(self._ix, d, buf, len(buf), _p(tfs, C.c_uint32), cap)
+        for per in (260, 766):                    # a term: up to 255 units of 3 bytes, and its NUL
+            buf = C.create_string_buffer(cap * per + 16)
+            n = lib().orc_doc_terms(self._ix, d, buf, len(buf), _p(tfs, C.c_uint32), cap)
+            if n != E_CAP:
+                break
         if n < 0:
             raise RuntimeError("orc_doc_terms rc=%d" % n)
         terms = buf.raw.split(b"\0")[:n]
@@ -204,9 +207,12 @@ class OracleIndex:
     def vocab(self):
         """{term: df} for the shard."""
         V = self.num_terms
-        buf = C.create_string_buffer(V * 257 + 16)
         df = np.zeros(max(V, 1), np.uint32)
-        n = lib().orc_vocab(self._ix, buf, len(buf), _p(df, C.c_uint32), V)
+        for per in (257, 766):                    # a term: up to 255 units of 3 bytes, and its NUL
+            buf = C.create_string_buffer(V * per + 16)
+            n = lib().orc_vocab(self._ix, buf, len(buf), _p(df, C.c_uint32), V)
+            if n != E_CAP:
+                break
         if n < 0:
             raise RuntimeError("orc_vocab rc=%d" % n)
         terms = buf.raw.split(b"\0")[:n]

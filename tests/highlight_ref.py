@@ -175,7 +175,7 @@ def corpus(name):
         rng = random.Random(20261020)
         pieces = ["abc", "x.y", "o'neil", "3,5", "İstanbul", "日", "🇫🇷", "👨‍👩‍👧", "é́́", "a" * 300,
                   "สวัสดี", "__", "q_r", "a·b", "צה\"ל", "7", "カタカナ", "ひ", "Z" * 1100]
-        if name == "window":                 # without the tokens of more than 255 units (CPU only: "windowcut")
+        if name == "window":                 # without the tokens of more than 255 units ("windowcut" has them)
             pieces = [p for p in pieces if len(p) < 256]
         glue = ["\u00a0", "\u00a0\u00a0", "\u2026", "\u3002", "\u2009"]      # separators, none of them ASCII
         docs = []

@@ -115,6 +115,20 @@ def test_tokens_of_every_kind_across_the_lookahead_window():
         check_snippets("window", W)
 
 
+def test_tokens_over_255_units_across_the_lookahead_window():
+    """`window` with runs of 300 a and 1 100 Z between its pieces: the scan
+    cuts them at 255 units (a x 255 + a x 45; z x 255 four times + z x 80), and
+    the corpus commits under the first hash seed (test_gpu_token_cut.py: two
+    over-long runs in one unit's window once failed k_tokenize_uchunk)."""
+    got = check_matches("windowcut")
+    s = index_of("windowcut").stats()
+    assert (s["hash_rebuilds"], s["hash_seed"]) == (0, 0)
+    assert {o for m in got for _, _, o in m} == set(range(18))
+    assert {l for m in got for _, l, o in m if o >= 15} == {255, 80, 45}
+    for W in (16, 160, 1024):
+        check_snippets("windowcut", W)
+
+
 # 4. hashed keys
 @pytest.mark.parametrize("weak", [False, True])
 def test_hashed_keys_never_match_the_unqueried_twin(weak, monkeypatch):

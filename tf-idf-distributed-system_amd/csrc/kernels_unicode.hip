@@ -858,7 +858,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) k_
         }
         pos = p32;
         active = have;
-        have = have && ts32 >= m.core_lo;                     // tokens starting in the core only
+        // tokens starting in the core only.  A token over 255 units is not
+        // inserted (nor what its lane scans after it: the unit is discarded
+        // below): its span here is uncut, and a second such token with the
+        // same first 255 units — another length, or clipped by the window's
+        // end — would fail uc_same_term against it: a collision under every seed
+        have = have && ts32 >= m.core_lo && !overflow;
       }
       uint32_t slot = dict_hash(lo, khv) >> (32 - kUcSlotBits);
       bool done = !have;
