@@ -360,6 +360,13 @@ int tfidf_reader_doc_keys(const tfidf_reader *rd, uint8_t *buf, uint64_t cap, ui
  *   with NULL payload pointers asks for the sizes).  Snippet text never exceeds
  *   n_docs x max_bytes.  *ms_device (may be NULL): HIP events on the call's
  *   stream, first copy to last.
+ * A call is served as the batch of one query (below): its rows run in
+ *   consecutive chunks under the batch's scratch budgets, so a call that plans
+ *   more than 2^16 (row, 16 KiB) items or finds more than 2^22 matches takes
+ *   several chunks with bounded scratch instead of one pass with scratch for
+ *   all of it.  The planned items of one call are not limited (2^24 once);
+ *   n_docs > 2^26 is TFIDF_E_INVALID_ARG.  tfidf_last_highlight_chunks does
+ *   not report these calls.
  * The calls run on a search context (own stream and scratch) beside other
  *   readers, tfidf_add_docs and tfidf_commit, and never wait for a commit;
  *   tfidf_matches / tfidf_snippets use the snapshot published at the call. */

@@ -4,8 +4,9 @@ reader forms) against the restatement built from the oracle alone
 and wave boundary, documents without a split byte, Unicode folding, hashed
 keys (with and without forced collisions), operator queries, a malformed
 document, snippet ranges / packed bytes / in-snippet matches at several
-widths, the buffer protocol, snapshot pinning beside commits, and
-Worker.search_snippets."""
+widths, row chunks (the budget knobs, and one call over the default item
+budget), the buffer protocol and the order of its errors, snapshot pinning
+beside commits, and Worker.search_snippets."""
 import ctypes as C
 import threading
 
@@ -82,11 +83,64 @@ def test_edge_lengths_one_document_per_call():
         check_matches("edge", [d])
 
 
-def test_edge_lengths_reversed_with_repeats():
+def reversed_with_repeats():
     docs = list(range(H.N_EDGE))[::-1]
     docs[5], docs[200] = docs[6], docs[3]
+    return docs
+
+
+def test_edge_lengths_reversed_with_repeats():
+    docs = reversed_with_repeats()
     check_matches("edge", docs)
     check_snippets("edge", 160, docs[:40])
+
+
+@pytest.mark.parametrize("knobs", [{"TFIDF_HL_CHUNK_ITEMS": "1"}, {"TFIDF_HL_CHUNK_ITEMS": "3"},
+                                   {"TFIDF_HL_CHUNK_MATCHES": "1"}, {"TFIDF_HL_CHUNK_MATCHES": "7"},
+                                   {"TFIDF_HL_CHUNK_ITEMS": "3", "TFIDF_HL_CHUNK_MATCHES": "7"}],
+                         ids=["items1", "items3", "matches1", "matches7", "items3-matches7"])
+def test_single_forms_under_any_chunking(knobs, monkeypatch):
+    """A single-query call is a batch of one query, so the budget knobs cut its
+    rows too (read at call time: the shared index serves).  Items 1: every row
+    with work is a chunk; items 3: a 70 000-byte document (5 items) is a chunk
+    of its own beside chunks of several rows; matches 1 / 7: rows above the
+    budget alone, rows of 0 matches ride along."""
+    index_of("edge")
+    monkeypatch.setenv("TFIDF_DEBUG", "1")
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, v)
+    check_matches("edge")
+    check_matches("edge", reader=True)
+    check_snippets("edge", 160, reversed_with_repeats())
+
+
+def test_single_call_over_the_default_item_budget():
+    """2^16 + 1 rows of one short document: one item each, one more than a row
+    chunk's default item budget, so the call runs in two chunks (no knob set)."""
+    n = (1 << 16) + 1
+    d = H.LENGTHS.index(257)
+    texts, q, _ = H.corpus("edge")
+    m = H.expected_matches("edge")[d]
+    a, b, sm = H.expected_snippets("edge", 160)[d]
+    assert len(texts[d]) == 257 and len(m) > len(sm) > 0
+    docs = np.full(n, d, np.uint32)
+
+    def tiled(ms, col, dtype):
+        return np.tile(np.array([x[col] for x in ms], dtype), n)
+
+    def rows(k):
+        return np.arange(n + 1, dtype=np.uint64) * np.uint64(k)
+    with index_of("edge").reader() as rd:
+        st, ln, od, offs, _ = rd.matches_arrays(q, docs)
+        text, t_offs, d_starts, sst, sln, sod, m_offs, _ = rd.snippets_arrays(q, docs, 160)
+    assert len(st) == n * len(m) and len(sst) == n * len(sm)
+    assert (offs == rows(len(m))).all()
+    assert (st == tiled(m, 0, np.uint64)).all() and (ln == tiled(m, 1, np.uint32)).all()
+    assert (od == tiled(m, 2, np.uint32)).all()
+    assert text == texts[d][a:b] * n and (t_offs == rows(b - a)).all() and (d_starts == a).all()
+    assert (m_offs == rows(len(sm))).all()
+    assert (sst == tiled(sm, 0, np.uint64)).all() and (sln == tiled(sm, 1, np.uint32)).all()
+    assert (sod == tiled(sm, 2, np.uint32)).all()
 
 
 # 2. no split byte
@@ -263,6 +317,20 @@ def test_buffer_protocol():
             with pytest.raises(L.TfidfError) as e:
                 rd.matches(bq, [0])
             assert e.value.code == code
+            # ... and before any document check: the query's error wins, nothing is written
+            pay = [np.full(4, 7, t) for t in (np.uint64, np.uint32, np.uint32)]
+            pp = [L.ptr(a, t) for a, t in zip(pay, (C.c_uint64, C.c_uint32, C.c_uint32))]
+            tb, to, ds = np.full(320, 7, np.uint8), np.full(3, 7, np.uint64), np.full(2, 7, np.uint64)
+            ct = C.c_uint64(99)
+            o3[:] = 7
+            nn.value = 99
+            assert lib.tfidf_reader_matches(rd._h, bq, len(bq), L.ptr(bad, C.c_uint32), 2, *pp, 4,
+                                            L.ptr(o3, C.c_uint64), C.byref(nn), None) == code
+            assert lib.tfidf_reader_snippets(rd._h, bq, len(bq), L.ptr(bad, C.c_uint32), 2, 160,
+                                             tb.ctypes.data_as(C.c_void_p), 320, L.ptr(to, C.c_uint64),
+                                             L.ptr(ds, C.c_uint64), *pp, 4, L.ptr(o3, C.c_uint64), C.byref(ct),
+                                             C.byref(nn), None) == code
+            assert all((a == 7).all() for a in pay + [tb, to, ds, o3]) and (ct.value, nn.value) == (99, 99)
         assert rd.matches(b"nosuchword NOT alpha", [60, 61]) == [[], []]
         assert rd.snippets(b"nosuchword", [62], 64) == [(0, texts[62][:64], [])]
 

@@ -204,6 +204,24 @@ def test_any_chunking_gives_the_unchunked_output(knob, value, monkeypatch):
     assert sum(len(m) for m in want_matches(b)[1]) > 100 and len(whole_m[0]) > 20000
 
 
+def test_single_calls_leave_the_chunk_report_alone(monkeypatch):
+    """tfidf_last_highlight_chunks is of the last batched call: the single
+    forms run the same rows machinery (cut by the same knob) and do not report."""
+    b = batch()
+    g = index()
+    monkeypatch.setenv("TFIDF_DEBUG", "1")
+    monkeypatch.setenv("TFIDF_HL_CHUNK_ITEMS", "3")
+    g.matches_batch(*args(b))
+    report = g.last_highlight_chunks()
+    assert report[1] >= report[0] > 8
+    q, terms = own("edge")
+    docs = [doc("edge", i) for i in range(24, 32)]                  # 14 items: far fewer chunks than the batch's
+    assert g.matches(q, docs) == [exp_matches(terms, d) for d in docs]
+    assert g.last_highlight_chunks() == report
+    assert g.snippets(q, docs, 160) == [exp_snippet(terms, d, 160) for d in docs]
+    assert g.last_highlight_chunks() == report
+
+
 # 3. queries that do not parse
 def test_unparseable_queries_have_no_matches_and_head_snippets():
     g = index()

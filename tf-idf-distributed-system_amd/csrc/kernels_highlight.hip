@@ -5,16 +5,15 @@
 //
 //   k_hl_extents   row -> corpus byte range of its document (one gather)
 //   k_hl_scan      one wave per (row, chunk) item of the host's plan, one lane
-//                  per slice: <false> counts each slice's matches, <true>
-//                  writes them at the slice's offset (counts scanned between
-//                  the two passes), so the matches of a row are contiguous and
-//                  ascending by start and the fill never exceeds the total the
-//                  counting pass reported
-//   k_hl_scan_batch    the same item for a batch of queries (tfidf_matches_batch,
-//                  tfidf_snippets_batch): the keys are the segment of the row's
-//                  query, the match arrays start at a row chunk's first match
-//   k_hl_row_offsets   row -> its first match (the scanned counts at its first item)
-//   k_hl_row_offsets_rel   the same, relative to a row chunk's first match
+//                  per slice, against the key segment of the row's query:
+//                  <false> counts each slice's matches, <true> writes them at
+//                  the slice's offset (counts scanned between the two passes),
+//                  so the matches of a row are contiguous and ascending by
+//                  start and the fill never exceeds the total the counting
+//                  pass reported; the match arrays start at a row chunk's
+//                  first match.  A single-query call is a batch of one query.
+//   k_hl_row_offsets   row -> its first match (the scanned counts at its first
+//                  item), relative to a row chunk's first match
 //   k_hl_rank      one wave per row: every lane ranks the candidate windows it
 //                  owns, the wave's best gives the byte range [a, b); then the
 //                  run of matches inside [a, b)
@@ -72,27 +71,11 @@ __device__ __forceinline__ void hl_scan_item(const uint8_t *__restrict__ text, c
   }
 }
 
+// The keys are the segment of the row's query (hl_segment; wave-uniform, so the
+// two loads are scalar), and the match arrays hold only the rows from the one
+// whose first match is m_base on.
 template <bool FILL>
-__global__ void __launch_bounds__(64 * kHlScanWaves) k_hl_scan(const uint8_t *__restrict__ text,
-                                                               const uint64_t *__restrict__ ext,
-                                                               const HlItem *__restrict__ items, uint32_t n_items,
-                                                               const HlKey *__restrict__ keys, uint32_t n_keys,
-                                                               uint64_t seed, uint64_t *__restrict__ counts,
-                                                               uint64_t *__restrict__ starts,
-                                                               uint32_t *__restrict__ lens,
-                                                               uint32_t *__restrict__ ords) {
-  const uint32_t item = blockIdx.x * kHlScanWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
-  if (item >= n_items) return;
-  hl_scan_item<FILL>(text, ext, items[item], item, lane, keys, n_keys, seed, counts, 0, starts, lens, ords);
-}
-
-// The batch form: the keys are the segment of the row's query (hl_segment;
-// wave-uniform, so the two loads are scalar), and the match arrays hold only
-// the rows from the one whose first match is m_base on.  A kernel of its own
-// rather than three more operands on k_hl_scan: the single-query kernel, its
-// argument block and its code stay exactly as they were measured.
-template <bool FILL>
-__global__ void __launch_bounds__(64 * kHlScanWaves) k_hl_scan_batch(
+__global__ void __launch_bounds__(64 * kHlScanWaves) k_hl_scan(
     const uint8_t *__restrict__ text, const uint64_t *__restrict__ ext, const HlItem *__restrict__ items,
     uint32_t n_items, const HlKey *__restrict__ keys, const uint32_t *__restrict__ key_off,
     const uint32_t *__restrict__ row_q, uint64_t seed, uint64_t *__restrict__ counts, uint64_t m_base,
@@ -106,17 +89,10 @@ __global__ void __launch_bounds__(64 * kHlScanWaves) k_hl_scan_batch(
   hl_scan_item<FILL>(text, ext, it, item, lane, seg, n_keys, seed, counts, m_base, starts, lens, ords);
 }
 
+// offsets relative to the first match the arrays hold (base; 0 for the rows of a whole item chunk)
 __global__ void __launch_bounds__(256) k_hl_row_offsets(const uint64_t *__restrict__ scanned,
                                                         const uint64_t *__restrict__ first, uint64_t n,
-                                                        uint64_t *__restrict__ row_off) {
-  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i <= n) row_off[i] = scanned[first[i] * kHlLanes];
-}
-
-// rows of a match chunk: offsets relative to the chunk's first match
-__global__ void __launch_bounds__(256) k_hl_row_offsets_rel(const uint64_t *__restrict__ scanned,
-                                                            const uint64_t *__restrict__ first, uint64_t n,
-                                                            uint64_t base, uint64_t *__restrict__ row_off) {
+                                                        uint64_t base, uint64_t *__restrict__ row_off) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i <= n) row_off[i] = scanned[first[i] * kHlLanes] - base;
 }
@@ -210,48 +186,27 @@ hipError_t launch_hl_extents(const uint64_t *offsets, const uint32_t *staged, ui
 }
 
 // fill == false: counts[item * kHlLanes + lane] = matches of the slice;
-// fill == true: counts holds their exclusive scan (n_items * kHlLanes + 1 entries)
+// fill == true: counts holds their exclusive scan (n_items * kHlLanes + 1 entries).
+// items [0, n_items) of a row chunk (rows relative to ext / row_q), m_base the
+// first match the arrays hold
 hipError_t launch_hl_scan(bool fill, const uint8_t *text, const uint64_t *ext, const HlItem *items, uint32_t n_items,
-                          const HlKey *keys, uint32_t n_keys, uint64_t seed, uint64_t *counts, uint64_t *starts,
-                          uint32_t *lens, uint32_t *ords, hipStream_t s) {
+                          const HlKey *keys, const uint32_t *key_off, const uint32_t *row_q, uint64_t seed,
+                          uint64_t *counts, uint64_t m_base, uint64_t *starts, uint32_t *lens, uint32_t *ords,
+                          hipStream_t s) {
   if (n_items == 0) return hipSuccess;
   const dim3 grid(hl_grid(n_items, kHlScanWaves)), block(64 * kHlScanWaves);
   if (fill)
-    hipLaunchKernelGGL(k_hl_scan<true>, grid, block, 0, s, text, ext, items, n_items, keys, n_keys, seed, counts,
-                       starts, lens, ords);
-  else
-    hipLaunchKernelGGL(k_hl_scan<false>, grid, block, 0, s, text, ext, items, n_items, keys, n_keys, seed, counts,
-                       starts, lens, ords);
-  return hipGetLastError();
-}
-
-// the batch form of launch_hl_scan: items [0, n_items) of a row chunk (rows relative to
-// ext / row_q), counts their scanned slice counts, m_base the first match the arrays hold
-hipError_t launch_hl_scan_batch(bool fill, const uint8_t *text, const uint64_t *ext, const HlItem *items,
-                                uint32_t n_items, const HlKey *keys, const uint32_t *key_off, const uint32_t *row_q,
-                                uint64_t seed, uint64_t *counts, uint64_t m_base, uint64_t *starts, uint32_t *lens,
-                                uint32_t *ords, hipStream_t s) {
-  if (n_items == 0) return hipSuccess;
-  const dim3 grid(hl_grid(n_items, kHlScanWaves)), block(64 * kHlScanWaves);
-  if (fill)
-    hipLaunchKernelGGL(k_hl_scan_batch<true>, grid, block, 0, s, text, ext, items, n_items, keys, key_off, row_q, seed,
+    hipLaunchKernelGGL(k_hl_scan<true>, grid, block, 0, s, text, ext, items, n_items, keys, key_off, row_q, seed,
                        counts, m_base, starts, lens, ords);
   else
-    hipLaunchKernelGGL(k_hl_scan_batch<false>, grid, block, 0, s, text, ext, items, n_items, keys, key_off, row_q,
+    hipLaunchKernelGGL(k_hl_scan<false>, grid, block, 0, s, text, ext, items, n_items, keys, key_off, row_q,
                        seed, counts, m_base, starts, lens, ords);
   return hipGetLastError();
 }
 
-hipError_t launch_hl_row_offsets_rel(const uint64_t *scanned, const uint64_t *first, uint64_t n, uint64_t base,
-                                     uint64_t *row_off, hipStream_t s) {
-  hipLaunchKernelGGL(k_hl_row_offsets_rel, dim3(hl_grid(n + 1, 256)), dim3(256), 0, s, scanned, first, n, base,
-                     row_off);
-  return hipGetLastError();
-}
-
-hipError_t launch_hl_row_offsets(const uint64_t *scanned, const uint64_t *first, uint64_t n, uint64_t *row_off,
-                                 hipStream_t s) {
-  hipLaunchKernelGGL(k_hl_row_offsets, dim3(hl_grid(n + 1, 256)), dim3(256), 0, s, scanned, first, n, row_off);
+hipError_t launch_hl_row_offsets(const uint64_t *scanned, const uint64_t *first, uint64_t n, uint64_t base,
+                                 uint64_t *row_off, hipStream_t s) {
+  hipLaunchKernelGGL(k_hl_row_offsets, dim3(hl_grid(n + 1, 256)), dim3(256), 0, s, scanned, first, n, base, row_off);
   return hipGetLastError();
 }
 

@@ -41,27 +41,6 @@ hipError_t gather_df_canon(const uint32_t *dfc, const uint32_t *canon_of_slot, u
                            hipStream_t s);
 hipError_t launch_compact_text(const uint8_t *src, uint8_t *dst, const CompactRun *runs, uint64_t n_runs,
                                uint64_t total, hipStream_t s);
-// hit highlighting (kernels_highlight.hip)
-hipError_t launch_hl_extents(const uint64_t *offsets, const uint32_t *staged, uint64_t n, uint64_t *ext,
-                             hipStream_t s);
-hipError_t launch_hl_scan(bool fill, const uint8_t *text, const uint64_t *ext, const HlItem *items, uint32_t n_items,
-                          const HlKey *keys, uint32_t n_keys, uint64_t seed, uint64_t *counts, uint64_t *starts,
-                          uint32_t *lens, uint32_t *ords, hipStream_t s);
-hipError_t launch_hl_scan_batch(bool fill, const uint8_t *text, const uint64_t *ext, const HlItem *items,
-                                uint32_t n_items, const HlKey *keys, const uint32_t *key_off, const uint32_t *row_q,
-                                uint64_t seed, uint64_t *counts, uint64_t m_base, uint64_t *starts, uint32_t *lens,
-                                uint32_t *ords, hipStream_t s);
-hipError_t launch_hl_row_offsets_rel(const uint64_t *scanned, const uint64_t *first, uint64_t n, uint64_t base,
-                                     uint64_t *row_off, hipStream_t s);
-hipError_t launch_hl_row_offsets(const uint64_t *scanned, const uint64_t *first, uint64_t n, uint64_t *row_off,
-                                 hipStream_t s);
-hipError_t launch_hl_rank(const uint8_t *text, const uint64_t *ext, const uint64_t *row_off, const uint64_t *starts,
-                          const uint32_t *lens, const uint32_t *ords, uint32_t W, uint64_t n, uint64_t *sn_a,
-                          uint64_t *sn_len, uint64_t *in_first, uint64_t *in_cnt, hipStream_t s);
-hipError_t launch_hl_pack(const uint8_t *text, const uint64_t *ext, const uint64_t *sn_a, const uint64_t *text_off,
-                          uint8_t *out, const uint64_t *starts, const uint32_t *lens, const uint32_t *ords,
-                          const uint64_t *in_first, const uint64_t *m_off, uint64_t *o_starts, uint32_t *o_lens,
-                          uint32_t *o_ords, uint64_t n, hipStream_t s);
 }  // namespace tfidf
 
 using namespace tfidf;
@@ -2551,167 +2530,9 @@ struct HlOut {
   float *ms_device = nullptr;
 };
 
-static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-static int highlight_on(tfidf_index *ix, Snapshot &S, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
-                        uint64_t n, const HlOut &o) {
-  if (o.ms_device) *o.ms_device = 0.0f;
-  std::vector<std::string> terms;
-  const int prc = positive_terms(q, q_len, &terms);
-  if (prc == kQBadUtf8) return fail(TFIDF_E_UNSUPPORTED_QUERY, "query is not valid UTF-8");
-  if (prc == kQSyntax)
-    return fail(TFIDF_E_QUERY_SYNTAX, "query does not parse (QueryParser ParseException / TooManyClauses)");
-  if (n > (1ull << 26)) return fail(TFIDF_E_INVALID_ARG, "more than 2^26 documents in one call");
-  for (uint64_t i = 0; i < n; i++)
-    if (docs[i] >= S.n_docs) return fail(TFIDF_E_INVALID_ARG, "doc %u out of range", docs[i]);
-  for (uint64_t i = 0; i <= n; i++) {
-    o.match_offsets[i] = 0;
-    if (o.W) o.text_offsets[i] = 0;
-  }
-  *o.n_matches = 0;
-  if (o.W) *o.n_text = 0;
-  if (n == 0) return TFIDF_OK;
-
-  CtxLease lease(ix);
-  if (lease.rc) return lease.rc;
-  SearchCtx &X = *lease.c;
-  const hipStream_t s = lease.stream();
-  DeviceGuard g(ix->cfg.device);
-  const bool timed = o.ms_device != nullptr;
-  // ends the timed span and waits for everything queued
-  auto finish = [&]() -> int {
-    if (timed) HIP_TRY(hipEventRecord(X.ev[QEV_1], s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (timed) HIP_TRY(hipEventElapsedTime(o.ms_device, X.ev[QEV_0], X.ev[QEV_1]));
-    return TFIDF_OK;
-  };
-
-  // the positive terms this snapshot holds: dictionary keys (under its hash seed) with their ordinals
-  std::vector<HlKey> keys;
-  for (size_t t = 0; t < terms.size(); t++) {
-    const uint32_t slot = lookup_term(S, terms[t]);
-    if (slot != kInvalidSlot) keys.push_back(HlKey{S.h_dict[slot], S.h_dict[(size_t)S.C + slot], (uint32_t)t, 0});
-  }
-  std::sort(keys.begin(), keys.end(), [](const HlKey &x, const HlKey &y) { return hl_key_less(x, y); });
-
-  // document extents: one gather, one copy back (the plan and the sizes need them)
-  std::vector<uint32_t> h_staged(n);
-  for (uint64_t i = 0; i < n; i++) h_staged[i] = (uint32_t)S.staged_of(docs[i]);
-  std::vector<uint64_t> h_ext(2 * n);
-  HIP_TRY(X.hl_in.reserve(up16(n * 4) + n * 16));
-  uint32_t *d_staged = X.hl_in.as<uint32_t>();
-  uint64_t *d_ext = reinterpret_cast<uint64_t *>(X.hl_in.as<uint8_t>() + up16(n * 4));
-  const uint8_t *d_text = S.text->as<uint8_t>();
-  if (timed) HIP_TRY(hipEventRecord(X.ev[QEV_0], s));
-  HIP_TRY(hipMemcpyAsync(d_staged, h_staged.data(), n * 4, hipMemcpyHostToDevice, s));
-  HIP_TRY(launch_hl_extents(S.offsets->as<uint64_t>(), d_staged, n, d_ext, s));
-  HIP_TRY(hipMemcpyAsync(h_ext.data(), d_ext, n * 16, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-
-  // the (row, chunk) work items; nothing to scan for a malformed document
-  // (indexed empty) or when the snapshot holds none of the terms
-  std::vector<uint8_t> skip(n, keys.empty() ? 1 : 0);
-  if (!keys.empty() && !S.malformed.empty())
-    for (uint64_t i = 0; i < n; i++) skip[i] = std::binary_search(S.malformed.begin(), S.malformed.end(), docs[i]);
-  std::vector<HlItem> items;
-  std::vector<uint64_t> first;
-  hl_plan(h_ext.data(), skip.data(), n, &items, &first);
-  if (items.size() > (1ull << 24))
-    return fail(TFIDF_E_INVALID_ARG, "more than 2^24 chunks of %llu bytes in one call",
-                (unsigned long long)kHlChunkBytes);
-  const uint32_t n_items = (uint32_t)items.size(), n_keys = (uint32_t)keys.size();
-  const uint64_t n_cnt = (uint64_t)n_items * kHlLanes;
-  const size_t off_row = (n + 1) * 8, off_keys = 2 * off_row, off_items = off_keys + (size_t)n_keys * sizeof(HlKey),
-               off_counts = up16(off_items + (size_t)n_items * sizeof(HlItem));
-  HIP_TRY(X.hl_cnt.reserve(off_counts + (n_cnt + 1) * 8));
-  uint8_t *cb = X.hl_cnt.as<uint8_t>();
-  uint64_t *d_first = reinterpret_cast<uint64_t *>(cb), *d_row = reinterpret_cast<uint64_t *>(cb + off_row),
-           *d_counts = reinterpret_cast<uint64_t *>(cb + off_counts);
-  HlKey *d_keys = reinterpret_cast<HlKey *>(cb + off_keys);
-  HlItem *d_items = reinterpret_cast<HlItem *>(cb + off_items);
-  std::vector<uint64_t> h_row(n + 1, 0);
-  if (n_items) {
-    HIP_TRY(hipMemcpyAsync(d_first, first.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_keys, keys.data(), (size_t)n_keys * sizeof(HlKey), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_items, items.data(), (size_t)n_items * sizeof(HlItem), hipMemcpyHostToDevice, s));
-    // count per slice, scan, row offsets: the totals are known before any match is stored
-    HIP_TRY(launch_hl_scan(false, d_text, d_ext, d_items, n_items, d_keys, n_keys, S.hash_seed, d_counts, nullptr,
-                           nullptr, nullptr, s));
-    HIP_TRY(exclusive_scan_u64(d_counts, d_counts, n_cnt, s));
-    HIP_TRY(launch_hl_row_offsets(d_counts, d_first, n, d_row, s));
-    HIP_TRY(hipMemcpyAsync(h_row.data(), d_row, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-  } else {
-    HIP_TRY(hipMemsetAsync(d_row, 0, (n + 1) * 8, s));
-  }
-  const uint64_t T = h_row[n];
-
-  if (!o.W) {
-    memcpy(o.match_offsets, h_row.data(), (n + 1) * 8);
-    *o.n_matches = T;
-    if (T > o.m_cap || (T && (!o.starts || !o.lens || !o.ordinals))) {
-      if (int rc = finish()) return rc;
-      return fail(TFIDF_E_BUFFER, "need %llu match slots", (unsigned long long)T);
-    }
-    if (T) {
-      HIP_TRY(X.hl_m.reserve(T * 16));
-      uint64_t *m_st = X.hl_m.as<uint64_t>();
-      uint32_t *m_ln = reinterpret_cast<uint32_t *>(m_st + T), *m_od = m_ln + T;
-      HIP_TRY(launch_hl_scan(true, d_text, d_ext, d_items, n_items, d_keys, n_keys, S.hash_seed, d_counts, m_st, m_ln,
-                             m_od, s));
-      HIP_TRY(hipMemcpyAsync(o.starts, m_st, T * 8, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipMemcpyAsync(o.lens, m_ln, T * 4, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipMemcpyAsync(o.ordinals, m_od, T * 4, hipMemcpyDeviceToHost, s));
-    }
-    return finish();
-  }
-
-  // snippets: all matches of the documents stay on the device; only the
-  // packed snippets, their offsets and the matches inside them come back
-  uint64_t text_bound = 0;
-  for (uint64_t i = 0; i < n; i++) text_bound += std::min<uint64_t>(h_ext[2 * i + 1] - h_ext[2 * i], o.W);
-  HIP_TRY(X.hl_m.reserve(std::max<uint64_t>(T, 1) * 16));
-  HIP_TRY(X.hl_s.reserve((4 * n + 2) * 8));
-  HIP_TRY(X.hl_o.reserve(std::max<uint64_t>(T, 1) * 16 + text_bound + 16));
-  uint64_t *m_st = X.hl_m.as<uint64_t>();
-  uint32_t *m_ln = reinterpret_cast<uint32_t *>(m_st + std::max<uint64_t>(T, 1)), *m_od = m_ln + std::max<uint64_t>(T, 1);
-  uint64_t *sn_a = X.hl_s.as<uint64_t>(), *sn_len = sn_a + n, *in_first = sn_len + n + 1, *in_cnt = in_first + n;
-  uint64_t *o_st = X.hl_o.as<uint64_t>();
-  uint32_t *o_ln = reinterpret_cast<uint32_t *>(o_st + std::max<uint64_t>(T, 1)), *o_od = o_ln + std::max<uint64_t>(T, 1);
-  uint8_t *o_text = reinterpret_cast<uint8_t *>(o_od + std::max<uint64_t>(T, 1));
-  if (T)
-    HIP_TRY(launch_hl_scan(true, d_text, d_ext, d_items, n_items, d_keys, n_keys, S.hash_seed, d_counts, m_st, m_ln,
-                           m_od, s));
-  HIP_TRY(launch_hl_rank(d_text, d_ext, d_row, m_st, m_ln, m_od, o.W, n, sn_a, sn_len, in_first, in_cnt, s));
-  HIP_TRY(exclusive_scan_u64(sn_len, sn_len, n, s));
-  HIP_TRY(exclusive_scan_u64(in_cnt, in_cnt, n, s));
-  HIP_TRY(launch_hl_pack(d_text, d_ext, sn_a, sn_len, o_text, m_st, m_ln, m_od, in_first, in_cnt, o_st, o_ln, o_od, n,
-                         s));
-  HIP_TRY(hipMemcpyAsync(o.text_offsets, sn_len, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(o.match_offsets, in_cnt, (n + 1) * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipMemcpyAsync(o.doc_starts, sn_a, n * 8, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const uint64_t nt = o.text_offsets[n], nm = o.match_offsets[n];
-  *o.n_text = nt;
-  *o.n_matches = nm;
-  if (nt > o.text_cap || nm > o.m_cap || (nt && !o.text) || (nm && (!o.starts || !o.lens || !o.ordinals))) {
-    if (int rc = finish()) return rc;
-    return fail(TFIDF_E_BUFFER, "need %llu text bytes and %llu match slots", (unsigned long long)nt,
-                (unsigned long long)nm);
-  }
-  if (nt) HIP_TRY(hipMemcpyAsync(o.text, o_text, nt, hipMemcpyDeviceToHost, s));
-  if (nm) {
-    HIP_TRY(hipMemcpyAsync(o.starts, o_st, nm * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(o.lens, o_ln, nm * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(o.ordinals, o_od, nm * 4, hipMemcpyDeviceToHost, s));
-  }
-  return finish();
-}
-
-static int matches_on(tfidf_index *ix, Snapshot &S, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
-                      uint64_t n_docs, uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t cap,
-                      uint64_t *match_offsets, uint64_t *n_out, float *ms_device) {
-  if ((!q && q_len) || (!docs && n_docs) || !match_offsets || !n_out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+// what tfidf_matches[_batch] fill
+static HlOut hl_out_matches(uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t cap,
+                            uint64_t *match_offsets, uint64_t *n_out, float *ms_device) {
   HlOut o;
   o.starts = starts;
   o.lens = lens;
@@ -2720,79 +2541,25 @@ static int matches_on(tfidf_index *ix, Snapshot &S, const uint8_t *q, uint64_t q
   o.match_offsets = match_offsets;
   o.n_matches = n_out;
   o.ms_device = ms_device;
-  return highlight_on(ix, S, q, q_len, docs, n_docs, o);
+  return o;
 }
 
-static int snippets_on(tfidf_index *ix, Snapshot &S, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
-                       uint64_t n_docs, uint32_t max_bytes, uint8_t *text, uint64_t text_cap, uint64_t *text_offsets,
-                       uint64_t *doc_starts, uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t m_cap,
-                       uint64_t *match_offsets, uint64_t *n_text, uint64_t *n_matches, float *ms_device) {
-  if ((!q && q_len) || (!docs && n_docs) || !text_offsets || (!doc_starts && n_docs) || !match_offsets || !n_text ||
-      !n_matches)
-    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
-  if (max_bytes < kHlMinBytes || max_bytes > kHlMaxBytes)
-    return fail(TFIDF_E_INVALID_ARG, "max_bytes %u outside %u..%u", max_bytes, kHlMinBytes, kHlMaxBytes);
-  HlOut o;
+// what tfidf_snippets[_batch] fill
+static HlOut hl_out_snippets(uint32_t max_bytes, uint8_t *text, uint64_t text_cap, uint64_t *text_offsets,
+                             uint64_t *doc_starts, uint64_t *starts, uint32_t *lens, uint32_t *ordinals,
+                             uint64_t m_cap, uint64_t *match_offsets, uint64_t *n_text, uint64_t *n_matches,
+                             float *ms_device) {
+  HlOut o = hl_out_matches(starts, lens, ordinals, m_cap, match_offsets, n_matches, ms_device);
   o.W = max_bytes;
   o.text = text;
   o.text_cap = text_cap;
   o.text_offsets = text_offsets;
   o.doc_starts = doc_starts;
   o.n_text = n_text;
-  o.starts = starts;
-  o.lens = lens;
-  o.ordinals = ordinals;
-  o.m_cap = m_cap;
-  o.match_offsets = match_offsets;
-  o.n_matches = n_matches;
-  o.ms_device = ms_device;
-  return highlight_on(ix, S, q, q_len, docs, n_docs, o);
+  return o;
 }
 
-extern "C" int tfidf_reader_matches(tfidf_reader *rd, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
-                                    uint64_t n_docs, uint64_t *starts, uint32_t *lens, uint32_t *ordinals,
-                                    uint64_t cap, uint64_t *match_offsets, uint64_t *n_out, float *ms_device) {
-  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
-  return matches_on(rd->ix, *rd->S, q, q_len, docs, n_docs, starts, lens, ordinals, cap, match_offsets, n_out,
-                    ms_device);
-}
-
-extern "C" int tfidf_matches(tfidf_index *ix, const uint8_t *q, uint64_t q_len, const uint32_t *docs, uint64_t n_docs,
-                             uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t cap,
-                             uint64_t *match_offsets, uint64_t *n_out, float *ms_device) {
-  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
-  const std::shared_ptr<Snapshot> snap = current(ix);
-  if (!snap) return fail(TFIDF_E_STATE, "matches before commit");
-  return matches_on(ix, *snap, q, q_len, docs, n_docs, starts, lens, ordinals, cap, match_offsets, n_out, ms_device);
-}
-
-extern "C" int tfidf_reader_snippets(tfidf_reader *rd, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
-                                     uint64_t n_docs, uint32_t max_bytes, uint8_t *text, uint64_t text_cap,
-                                     uint64_t *text_offsets, uint64_t *doc_starts, uint64_t *starts, uint32_t *lens,
-                                     uint32_t *ordinals, uint64_t m_cap, uint64_t *match_offsets, uint64_t *n_text,
-                                     uint64_t *n_matches, float *ms_device) {
-  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
-  return snippets_on(rd->ix, *rd->S, q, q_len, docs, n_docs, max_bytes, text, text_cap, text_offsets, doc_starts,
-                     starts, lens, ordinals, m_cap, match_offsets, n_text, n_matches, ms_device);
-}
-
-extern "C" int tfidf_snippets(tfidf_index *ix, const uint8_t *q, uint64_t q_len, const uint32_t *docs, uint64_t n_docs,
-                              uint32_t max_bytes, uint8_t *text, uint64_t text_cap, uint64_t *text_offsets,
-                              uint64_t *doc_starts, uint64_t *starts, uint32_t *lens, uint32_t *ordinals,
-                              uint64_t m_cap, uint64_t *match_offsets, uint64_t *n_text, uint64_t *n_matches,
-                              float *ms_device) {
-  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
-  const std::shared_ptr<Snapshot> snap = current(ix);
-  if (!snap) return fail(TFIDF_E_STATE, "snippets before commit");
-  return snippets_on(ix, *snap, q, q_len, docs, n_docs, max_bytes, text, text_cap, text_offsets, doc_starts, starts,
-                     lens, ordinals, m_cap, match_offsets, n_text, n_matches, ms_device);
-}
-
-// ---------------------------------------------------------------------------
-// batched hit highlighting: the rows (query, document) of many queries in one
-// call.  Row r's result is highlight_on's for (its query, docs[r]); the chain
-// of launches, copies and synchronisations is paid per call (per row chunk
-// when the scratch budgets cut the rows), never per query.
+static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 static uint64_t hl_budget(const char *name, uint64_t dflt) {
   if (const char *e = knob(name)) return (uint64_t)std::max<long long>(1, atoll(e));   // tests: chunk edges anywhere
@@ -2802,39 +2569,37 @@ static uint64_t hl_budget(const char *name, uint64_t dflt) {
 constexpr uint64_t kHlChunkItems = 1ull << 16;     // (row, chunk) items per row chunk: 32 MiB of slice counts
 constexpr uint64_t kHlChunkMatches = 1ull << 22;   // matches per row chunk: 128 MiB over hl_m + hl_o
 
-static int highlight_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf8, const uint64_t *q_offsets,
-                              uint32_t n_q, const uint32_t *docs, const uint64_t *doc_offsets, const HlOut &o) {
-  if (o.ms_device) *o.ms_device = 0.0f;
-  if (doc_offsets[0] != 0) return fail(TFIDF_E_INVALID_ARG, "doc_offsets[0] is not 0");
-  for (uint32_t i = 0; i < n_q; i++) {
-    if (doc_offsets[i + 1] < doc_offsets[i]) return fail(TFIDF_E_INVALID_ARG, "doc_offsets decrease at query %u", i);
-    if (q_offsets[i + 1] < q_offsets[i]) return fail(TFIDF_E_INVALID_ARG, "q_offsets decrease at query %u", i);
-  }
-  const uint64_t R = doc_offsets[n_q];
+// the rows of one call: at most 2^26, each a document of the snapshot
+static int hl_check_rows(const Snapshot &S, const uint32_t *docs, uint64_t R) {
   if (R > (1ull << 26)) return fail(TFIDF_E_INVALID_ARG, "more than 2^26 rows in one call");
   for (uint64_t r = 0; r < R; r++)
     if (docs[r] >= S.n_docs) return fail(TFIDF_E_INVALID_ARG, "doc %u out of range", docs[r]);
+  return TFIDF_OK;
+}
 
-  // every query's present positive terms: one segment of keys each, sorted on
-  // its own; a query that does not parse has an empty segment (no matches)
-  std::vector<HlKey> keys;
-  std::vector<uint32_t> key_off((size_t)n_q + 1, 0), row_q(R);
-  std::vector<std::string> terms;
-  for (uint32_t i = 0; i < n_q; i++) {
-    key_off[i] = (uint32_t)keys.size();
-    for (uint64_t r = doc_offsets[i]; r < doc_offsets[i + 1]; r++) row_q[r] = i;
-    if (doc_offsets[i + 1] == doc_offsets[i]) continue;
-    terms.clear();
-    if (positive_terms(q_utf8 + q_offsets[i], q_offsets[i + 1] - q_offsets[i], &terms) != 0) continue;
-    for (size_t t = 0; t < terms.size(); t++) {
-      const uint32_t slot = lookup_term(S, terms[t]);
-      if (slot != kInvalidSlot) keys.push_back(HlKey{S.h_dict[slot], S.h_dict[(size_t)S.C + slot], (uint32_t)t, 0});
-    }
-    std::sort(keys.begin() + key_off[i], keys.end(), [](const HlKey &x, const HlKey &y) { return hl_key_less(x, y); });
-    if (keys.size() > (1ull << 31)) return fail(TFIDF_E_INVALID_ARG, "more than 2^31 query terms in one call");
+// one query's key segment, appended to *keys: its positive terms that this
+// snapshot holds, as dictionary keys (under its hash seed) with their ordinals,
+// sorted on their own
+static void hl_append_keys(Snapshot &S, const std::vector<std::string> &terms, std::vector<HlKey> *keys) {
+  const size_t k0 = keys->size();
+  for (size_t t = 0; t < terms.size(); t++) {
+    const uint32_t slot = lookup_term(S, terms[t]);
+    if (slot != kInvalidSlot) keys->push_back(HlKey{S.h_dict[slot], S.h_dict[(size_t)S.C + slot], (uint32_t)t, 0});
   }
-  key_off[n_q] = (uint32_t)keys.size();
-  const size_t n_keys = keys.size();
+  std::sort(keys->begin() + k0, keys->end(), [](const HlKey &x, const HlKey &y) { return hl_key_less(x, y); });
+}
+
+// The rows (query, document) of one call, single-query or batched: row r is
+// docs[r] against the key segment [key_off[row_q[r]], key_off[row_q[r] + 1]) of
+// its query (hl_check_rows has passed).  The chain of launches, copies and
+// synchronisations is paid per call (per row chunk when the scratch budgets cut
+// the rows), never per query.  report_chunks: the call is a batched one, whose
+// chunks tfidf_last_highlight_chunks reports.
+static int highlight_rows(tfidf_index *ix, Snapshot &S, const std::vector<HlKey> &keys,
+                          const std::vector<uint32_t> &key_off, const std::vector<uint32_t> &row_q,
+                          const uint32_t *docs, const HlOut &o, bool report_chunks) {
+  const uint64_t R = row_q.size();
+  const size_t n_q = key_off.size() - 1, n_keys = keys.size();
   for (uint64_t r = 0; r <= R; r++) {
     o.match_offsets[r] = 0;
     if (o.W) o.text_offsets[r] = 0;
@@ -2856,13 +2621,18 @@ static int highlight_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf
     return TFIDF_OK;
   };
 
-  // the call's inputs on the device: staged ids, extents, row -> query, keys, key segments
-  std::vector<uint32_t> h_staged(R);
+  // the call's inputs, laid out on the host as on the device and sent in one copy: staged
+  // ids, row -> query, key segments, keys; the extents follow them on the device
+  const size_t in_rowq = up16(R * 4), in_koff = up16(in_rowq + R * 4), in_keys = up16(in_koff + (n_q + 1) * 4),
+               in_ext = up16(in_keys + n_keys * sizeof(HlKey));
+  std::vector<uint8_t> h_in(in_ext);
+  uint32_t *h_staged = reinterpret_cast<uint32_t *>(h_in.data());
   for (uint64_t r = 0; r < R; r++) h_staged[r] = (uint32_t)S.staged_of(docs[r]);
+  memcpy(h_in.data() + in_rowq, row_q.data(), R * 4);
+  memcpy(h_in.data() + in_koff, key_off.data(), (n_q + 1) * 4);
+  if (n_keys) memcpy(h_in.data() + in_keys, keys.data(), n_keys * sizeof(HlKey));
   std::vector<uint64_t> h_ext(2 * R);
-  const size_t in_ext = up16(R * 4), in_rowq = in_ext + R * 16, in_koff = up16(in_rowq + R * 4),
-               in_keys = up16(in_koff + ((size_t)n_q + 1) * 4);
-  HIP_TRY(X.hl_in.reserve(in_keys + n_keys * sizeof(HlKey)));
+  HIP_TRY(X.hl_in.reserve(in_ext + R * 16));
   uint8_t *ib = X.hl_in.as<uint8_t>();
   uint32_t *d_staged = reinterpret_cast<uint32_t *>(ib), *d_rowq = reinterpret_cast<uint32_t *>(ib + in_rowq),
            *d_koff = reinterpret_cast<uint32_t *>(ib + in_koff);
@@ -2870,14 +2640,9 @@ static int highlight_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf
   HlKey *d_keys = reinterpret_cast<HlKey *>(ib + in_keys);
   const uint8_t *d_text = S.text->as<uint8_t>();
   if (timed) HIP_TRY(hipEventRecord(X.ev[QEV_0], s));
-  HIP_TRY(hipMemcpyAsync(d_staged, h_staged.data(), R * 4, hipMemcpyHostToDevice, s));
+  HIP_TRY(hipMemcpyAsync(ib, h_in.data(), in_ext, hipMemcpyHostToDevice, s));
   HIP_TRY(launch_hl_extents(S.offsets->as<uint64_t>(), d_staged, R, d_ext, s));
   HIP_TRY(hipMemcpyAsync(h_ext.data(), d_ext, R * 16, hipMemcpyDeviceToHost, s));
-  if (n_keys) {
-    HIP_TRY(hipMemcpyAsync(d_rowq, row_q.data(), R * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_koff, key_off.data(), ((size_t)n_q + 1) * 4, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(d_keys, keys.data(), n_keys * sizeof(HlKey), hipMemcpyHostToDevice, s));
-  }
   HIP_TRY(hipStreamSynchronize(s));
 
   // rows without work: an empty key segment, a malformed document (indexed empty)
@@ -2918,10 +2683,10 @@ static int highlight_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf
       // count per slice, scan, row offsets: the chunk's totals before any match is stored
       HIP_TRY(hipMemcpyAsync(d_first, first.data(), (nr + 1) * 8, hipMemcpyHostToDevice, s));
       HIP_TRY(hipMemcpyAsync(d_items, items.data(), (size_t)n_items * sizeof(HlItem), hipMemcpyHostToDevice, s));
-      HIP_TRY(launch_hl_scan_batch(false, d_text, d_ext + 2 * r0, d_items, n_items, d_keys, d_koff, d_rowq + r0,
+      HIP_TRY(launch_hl_scan(false, d_text, d_ext + 2 * r0, d_items, n_items, d_keys, d_koff, d_rowq + r0,
                                    S.hash_seed, d_counts, 0, nullptr, nullptr, nullptr, s));
       HIP_TRY(exclusive_scan_u64(d_counts, d_counts, n_cnt, s));
-      HIP_TRY(launch_hl_row_offsets(d_counts, d_first, nr, d_row, s));
+      HIP_TRY(launch_hl_row_offsets(d_counts, d_first, nr, 0, d_row, s));
       HIP_TRY(hipMemcpyAsync(h_row.data(), d_row, (nr + 1) * 8, hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
     } else {
@@ -2950,7 +2715,7 @@ static int highlight_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf
       uint64_t *m_st = X.hl_m.as<uint64_t>();
       uint32_t *m_ln = reinterpret_cast<uint32_t *>(m_st + Tc), *m_od = m_ln + Tc;
       if (T)
-        HIP_TRY(launch_hl_scan_batch(true, d_text, d_ext + 2 * r0, d_items + i0, ni, d_keys, d_koff, d_rowq + r0,
+        HIP_TRY(launch_hl_scan(true, d_text, d_ext + 2 * r0, d_items + i0, ni, d_keys, d_koff, d_rowq + r0,
                                      S.hash_seed, d_counts + (uint64_t)i0 * kHlLanes, m_base, m_st, m_ln, m_od, s));
       if (!o.W) {
         if (T) {
@@ -2966,7 +2731,7 @@ static int highlight_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf
       const uint64_t *d_ext_s = d_ext + 2 * (r0 + s0);
       const uint64_t *d_row_s = d_row + s0;
       if (m_base) {
-        HIP_TRY(launch_hl_row_offsets_rel(d_counts, d_first + s0, ns, m_base, d_row_sub, s));
+        HIP_TRY(launch_hl_row_offsets(d_counts, d_first + s0, ns, m_base, d_row_sub, s));
         d_row_s = d_row_sub;
       }
       uint64_t text_bound = 0;
@@ -3014,7 +2779,7 @@ static int highlight_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf
   *o.n_matches = run_m;
   if (o.W) *o.n_text = run_t;
   if (int rc = finish()) return rc;
-  {
+  if (report_chunks) {
     std::lock_guard<std::mutex> lk(ix->ms_mu);
     ix->last_hl_item_chunks = cuts.size() - 1;
     ix->last_hl_row_chunks = n_row_chunks;
@@ -3028,6 +2793,116 @@ static int highlight_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf
   return TFIDF_OK;
 }
 
+// The single-query forms: the batch of one query over all n rows.  Unlike a
+// batch, they report a query that does not parse, before any other check.
+static int highlight_one_on(tfidf_index *ix, Snapshot &S, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
+                            uint64_t n, const HlOut &o) {
+  if (o.ms_device) *o.ms_device = 0.0f;
+  std::vector<std::string> terms;
+  const int prc = positive_terms(q, q_len, &terms);
+  if (prc == kQBadUtf8) return fail(TFIDF_E_UNSUPPORTED_QUERY, "query is not valid UTF-8");
+  if (prc == kQSyntax)
+    return fail(TFIDF_E_QUERY_SYNTAX, "query does not parse (QueryParser ParseException / TooManyClauses)");
+  if (int rc = hl_check_rows(S, docs, n)) return rc;
+  std::vector<HlKey> keys;
+  hl_append_keys(S, terms, &keys);
+  return highlight_rows(ix, S, keys, {0, (uint32_t)keys.size()}, std::vector<uint32_t>(n, 0), docs, o, false);
+}
+
+static int matches_on(tfidf_index *ix, Snapshot &S, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
+                      uint64_t n_docs, uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t cap,
+                      uint64_t *match_offsets, uint64_t *n_out, float *ms_device) {
+  if ((!q && q_len) || (!docs && n_docs) || !match_offsets || !n_out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  return highlight_one_on(ix, S, q, q_len, docs, n_docs,
+                          hl_out_matches(starts, lens, ordinals, cap, match_offsets, n_out, ms_device));
+}
+
+static int snippets_on(tfidf_index *ix, Snapshot &S, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
+                       uint64_t n_docs, uint32_t max_bytes, uint8_t *text, uint64_t text_cap, uint64_t *text_offsets,
+                       uint64_t *doc_starts, uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t m_cap,
+                       uint64_t *match_offsets, uint64_t *n_text, uint64_t *n_matches, float *ms_device) {
+  if ((!q && q_len) || (!docs && n_docs) || !text_offsets || (!doc_starts && n_docs) || !match_offsets || !n_text ||
+      !n_matches)
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (max_bytes < kHlMinBytes || max_bytes > kHlMaxBytes)
+    return fail(TFIDF_E_INVALID_ARG, "max_bytes %u outside %u..%u", max_bytes, kHlMinBytes, kHlMaxBytes);
+  return highlight_one_on(ix, S, q, q_len, docs, n_docs,
+                          hl_out_snippets(max_bytes, text, text_cap, text_offsets, doc_starts, starts, lens, ordinals,
+                                          m_cap, match_offsets, n_text, n_matches, ms_device));
+}
+
+extern "C" int tfidf_reader_matches(tfidf_reader *rd, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
+                                    uint64_t n_docs, uint64_t *starts, uint32_t *lens, uint32_t *ordinals,
+                                    uint64_t cap, uint64_t *match_offsets, uint64_t *n_out, float *ms_device) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  return matches_on(rd->ix, *rd->S, q, q_len, docs, n_docs, starts, lens, ordinals, cap, match_offsets, n_out,
+                    ms_device);
+}
+
+extern "C" int tfidf_matches(tfidf_index *ix, const uint8_t *q, uint64_t q_len, const uint32_t *docs, uint64_t n_docs,
+                             uint64_t *starts, uint32_t *lens, uint32_t *ordinals, uint64_t cap,
+                             uint64_t *match_offsets, uint64_t *n_out, float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "matches before commit");
+  return matches_on(ix, *snap, q, q_len, docs, n_docs, starts, lens, ordinals, cap, match_offsets, n_out, ms_device);
+}
+
+extern "C" int tfidf_reader_snippets(tfidf_reader *rd, const uint8_t *q, uint64_t q_len, const uint32_t *docs,
+                                     uint64_t n_docs, uint32_t max_bytes, uint8_t *text, uint64_t text_cap,
+                                     uint64_t *text_offsets, uint64_t *doc_starts, uint64_t *starts, uint32_t *lens,
+                                     uint32_t *ordinals, uint64_t m_cap, uint64_t *match_offsets, uint64_t *n_text,
+                                     uint64_t *n_matches, float *ms_device) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  return snippets_on(rd->ix, *rd->S, q, q_len, docs, n_docs, max_bytes, text, text_cap, text_offsets, doc_starts,
+                     starts, lens, ordinals, m_cap, match_offsets, n_text, n_matches, ms_device);
+}
+
+extern "C" int tfidf_snippets(tfidf_index *ix, const uint8_t *q, uint64_t q_len, const uint32_t *docs, uint64_t n_docs,
+                              uint32_t max_bytes, uint8_t *text, uint64_t text_cap, uint64_t *text_offsets,
+                              uint64_t *doc_starts, uint64_t *starts, uint32_t *lens, uint32_t *ordinals,
+                              uint64_t m_cap, uint64_t *match_offsets, uint64_t *n_text, uint64_t *n_matches,
+                              float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "snippets before commit");
+  return snippets_on(ix, *snap, q, q_len, docs, n_docs, max_bytes, text, text_cap, text_offsets, doc_starts, starts,
+                     lens, ordinals, m_cap, match_offsets, n_text, n_matches, ms_device);
+}
+
+// ---------------------------------------------------------------------------
+// batched hit highlighting: the rows (query, document) of many queries in one
+// call.  Row r's result is the single-query call's for (its query, docs[r]):
+// both are highlight_rows.
+
+static int highlight_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf8, const uint64_t *q_offsets,
+                              uint32_t n_q, const uint32_t *docs, const uint64_t *doc_offsets, const HlOut &o) {
+  if (o.ms_device) *o.ms_device = 0.0f;
+  if (doc_offsets[0] != 0) return fail(TFIDF_E_INVALID_ARG, "doc_offsets[0] is not 0");
+  for (uint32_t i = 0; i < n_q; i++) {
+    if (doc_offsets[i + 1] < doc_offsets[i]) return fail(TFIDF_E_INVALID_ARG, "doc_offsets decrease at query %u", i);
+    if (q_offsets[i + 1] < q_offsets[i]) return fail(TFIDF_E_INVALID_ARG, "q_offsets decrease at query %u", i);
+  }
+  const uint64_t R = doc_offsets[n_q];
+  if (int rc = hl_check_rows(S, docs, R)) return rc;
+
+  // every query's key segment; a query that does not parse has an empty one (no matches)
+  std::vector<HlKey> keys;
+  std::vector<uint32_t> key_off((size_t)n_q + 1, 0), row_q(R);
+  std::vector<std::string> terms;
+  for (uint32_t i = 0; i < n_q; i++) {
+    key_off[i] = (uint32_t)keys.size();
+    for (uint64_t r = doc_offsets[i]; r < doc_offsets[i + 1]; r++) row_q[r] = i;
+    if (doc_offsets[i + 1] == doc_offsets[i]) continue;
+    terms.clear();
+    if (positive_terms(q_utf8 + q_offsets[i], q_offsets[i + 1] - q_offsets[i], &terms) != 0) continue;
+    hl_append_keys(S, terms, &keys);
+    if (keys.size() > (1ull << 31)) return fail(TFIDF_E_INVALID_ARG, "more than 2^31 query terms in one call");
+  }
+  key_off[n_q] = (uint32_t)keys.size();
+  return highlight_rows(ix, S, keys, key_off, row_q, docs, o, true);
+}
+
 static int matches_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf8, const uint64_t *q_offsets,
                             uint32_t n_q, const uint32_t *docs, const uint64_t *doc_offsets, uint64_t *starts,
                             uint32_t *lens, uint32_t *ordinals, uint64_t cap, uint64_t *match_offsets, uint64_t *n_out,
@@ -3035,15 +2910,8 @@ static int matches_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf8,
   if ((n_q && (!q_offsets || (!q_utf8 && q_offsets[n_q]))) || !doc_offsets || (!docs && doc_offsets[n_q]) ||
       !match_offsets || !n_out)
     return fail(TFIDF_E_INVALID_ARG, "NULL argument");
-  HlOut o;
-  o.starts = starts;
-  o.lens = lens;
-  o.ordinals = ordinals;
-  o.m_cap = cap;
-  o.match_offsets = match_offsets;
-  o.n_matches = n_out;
-  o.ms_device = ms_device;
-  return highlight_batch_on(ix, S, q_utf8, q_offsets, n_q, docs, doc_offsets, o);
+  return highlight_batch_on(ix, S, q_utf8, q_offsets, n_q, docs, doc_offsets,
+                            hl_out_matches(starts, lens, ordinals, cap, match_offsets, n_out, ms_device));
 }
 
 static int snippets_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf8, const uint64_t *q_offsets,
@@ -3056,21 +2924,9 @@ static int snippets_batch_on(tfidf_index *ix, Snapshot &S, const uint8_t *q_utf8
     return fail(TFIDF_E_INVALID_ARG, "NULL argument");
   if (max_bytes < kHlMinBytes || max_bytes > kHlMaxBytes)
     return fail(TFIDF_E_INVALID_ARG, "max_bytes %u outside %u..%u", max_bytes, kHlMinBytes, kHlMaxBytes);
-  HlOut o;
-  o.W = max_bytes;
-  o.text = text;
-  o.text_cap = text_cap;
-  o.text_offsets = text_offsets;
-  o.doc_starts = doc_starts;
-  o.n_text = n_text;
-  o.starts = starts;
-  o.lens = lens;
-  o.ordinals = ordinals;
-  o.m_cap = m_cap;
-  o.match_offsets = match_offsets;
-  o.n_matches = n_matches;
-  o.ms_device = ms_device;
-  return highlight_batch_on(ix, S, q_utf8, q_offsets, n_q, docs, doc_offsets, o);
+  return highlight_batch_on(ix, S, q_utf8, q_offsets, n_q, docs, doc_offsets,
+                            hl_out_snippets(max_bytes, text, text_cap, text_offsets, doc_starts, starts, lens,
+                                            ordinals, m_cap, match_offsets, n_text, n_matches, ms_device));
 }
 
 extern "C" int tfidf_reader_matches_batch(tfidf_reader *rd, const uint8_t *q_utf8, const uint64_t *q_offsets,

@@ -427,6 +427,25 @@ hipError_t vocab_reduce(const uint64_t *records, uint64_t n, uint64_t *table, ui
                         uint32_t *rslot, uint32_t *out, unsigned long long *n_unique, hipStream_t s);
 hipError_t vocab_import(const uint32_t *sent_slot, const uint32_t *gdf_in, uint64_t n, uint32_t *gdf, hipStream_t s);
 
+// --- hit highlighting (kernels_highlight.hip; rules in snippet_plan.h) ---
+struct HlItem;
+struct HlKey;
+hipError_t launch_hl_extents(const uint64_t *offsets, const uint32_t *staged, uint64_t n, uint64_t *ext,
+                             hipStream_t s);
+hipError_t launch_hl_scan(bool fill, const uint8_t *text, const uint64_t *ext, const HlItem *items, uint32_t n_items,
+                          const HlKey *keys, const uint32_t *key_off, const uint32_t *row_q, uint64_t seed,
+                          uint64_t *counts, uint64_t m_base, uint64_t *starts, uint32_t *lens, uint32_t *ords,
+                          hipStream_t s);
+hipError_t launch_hl_row_offsets(const uint64_t *scanned, const uint64_t *first, uint64_t n, uint64_t base,
+                                 uint64_t *row_off, hipStream_t s);
+hipError_t launch_hl_rank(const uint8_t *text, const uint64_t *ext, const uint64_t *row_off, const uint64_t *starts,
+                          const uint32_t *lens, const uint32_t *ords, uint32_t W, uint64_t n, uint64_t *sn_a,
+                          uint64_t *sn_len, uint64_t *in_first, uint64_t *in_cnt, hipStream_t s);
+hipError_t launch_hl_pack(const uint8_t *text, const uint64_t *ext, const uint64_t *sn_a, const uint64_t *text_off,
+                          uint8_t *out, const uint64_t *starts, const uint32_t *lens, const uint32_t *ords,
+                          const uint64_t *in_first, const uint64_t *m_off, uint64_t *o_starts, uint32_t *o_lens,
+                          uint32_t *o_ords, uint64_t n, hipStream_t s);
+
 // --- fuzzy term lookup (kernels_fuzzy.hip; rules in fuzzy_plan.h) ---
 // One pass of a chunk of staged input terms over the dictionary.  t_off[i] ..
 // t_off[i + 1] index t_cps (lower-cased code points; an empty range = a term

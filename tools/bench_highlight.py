@@ -27,7 +27,12 @@ the two, buffers allocated once):
                       per (query, shard), routed by hand
 Per shape: device and wall median [min, max] of both routes, bytes scanned per
 device second of both, the row chunks of the batched call, and whether the
-batch's slowest round beat the loop's fastest.
+batch's slowest round beat the loop's fastest.  The loop of single calls is
+still the route to compare against: Q chains of launches against one.  At
+Q = 1 the two are the same code (the library serves a single-query call as the
+batch of one query), so cfg2-batch-1 measures the ctypes call path alone.
+The single-query shapes record item_chunks / row_chunks through a one-query
+batch call over the same rows: a single-form call does not report its chunks.
 """
 import argparse
 import ctypes as C
@@ -61,7 +66,7 @@ def download_scan(rd, docs, buf):
     return total
 
 
-def measure(name, rd, q, docs, runs, warmup, extra):
+def measure(name, g, rd, q, docs, runs, warmup, extra):
     docs = np.ascontiguousarray(docs, dtype=np.uint32)
     sizes = [len(rd.doc_text(int(d))) for d in docs]
     buf = C.create_string_buffer(2 * max(sizes + [1]) + 64)
@@ -78,12 +83,14 @@ def measure(name, rd, q, docs, runs, warmup, extra):
             wall.append((t1 - t0) * 1e3)
             par.append((t2 - t1) * 1e3)
     text, _, _, st, _, _, _, _ = out
+    rd.snippets_batch_arrays([q], [docs], 160)             # the same rows as a batch of one: only batched calls
+    item_chunks, row_chunks = g.last_highlight_chunks()    # report their row chunks
     nbytes = int(sum(sizes))
     res = {"shape": name, "query": q.decode(), "hits": int(len(docs)), "runs": runs, "warmup": warmup,
            "document_bytes": nbytes, "snippet_bytes": len(text), "snippet_matches": int(len(st)),
            "returned_bytes": len(text) + 16 * int(len(st)) + 24 * int(len(docs)),
            "snippets": {"device_ms": spread(dev), "wall_ms": spread(wall)},
-           "download_scan": {"wall_ms": spread(par)}}
+           "download_scan": {"wall_ms": spread(par)}, "item_chunks": item_chunks, "row_chunks": row_chunks}
     res["scan_GBs_device"] = nbytes / (res["snippets"]["device_ms"]["median"] * 1e-3) / 1e9
     res["wall_speedup_over_download_scan"] = res["download_scan"]["wall_ms"]["median"] / \
         res["snippets"]["wall_ms"]["median"]
@@ -298,8 +305,8 @@ def main():
                 rd.search_arrays(q, 10)
                 lat.append((time.perf_counter() - t0) * 1e3)
             extra["search_top10_wall_ms_p50"] = float(np.median(lat[args.warmup:]))
-            emit(measure("cfg2-top10", rd, q, top[:10], args.runs, args.warmup, extra))
-            emit(measure("cfg2-top1024", rd, q, top, args.runs, args.warmup, extra))
+            emit(measure("cfg2-top10", g, rd, q, top[:10], args.runs, args.warmup, extra))
+            emit(measure("cfg2-top1024", g, rd, q, top, args.runs, args.warmup, extra))
             if "batch" not in skip:
                 lens = doc_lengths(dc)
                 bx = {"corpus": extra["corpus"]}
@@ -321,8 +328,8 @@ def main():
         q = synth.queries(1, n_terms=3)[0]
         extra = dict(commit_rates(g), corpus="books: %d docs x %d tokens, V=100000" % (nb, T))
         with g.reader() as rd:
-            emit(measure("book-1", rd, q, [0], args.runs, args.warmup, extra))
-            emit(measure("book-%d" % nb, rd, q, list(range(nb)), args.runs, args.warmup, extra))
+            emit(measure("book-1", g, rd, q, [0], args.runs, args.warmup, extra))
+            emit(measure("book-%d" % nb, g, rd, q, list(range(nb)), args.runs, args.warmup, extra))
         g.close()
         dc.free()
     return 0
