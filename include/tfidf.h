@@ -499,7 +499,42 @@ int tfidf_reader_fuzzy_terms(tfidf_reader *rd, const uint8_t *term, uint64_t len
  * chunks filled and sorted (1, 1 when everything fitted; 0, 0 when no input
  * term could have candidates). */
 int tfidf_last_fuzzy_chunks(const tfidf_index *ix, uint64_t *scan_chunks, uint64_t *cand_chunks);
-/* Per-query device time of the last search call on this index (HIP events on the search's stream). */
+/* ---- exact phrase search (no reference counterpart: Worker.java:225-227
+ * escapes the quotes away; DESIGN.md section 2, "Phrase search") ----
+ * The phrase bytes are analysed as a whole the way a document is (they are not
+ * parsed as a query): terms t_0 .. t_{m-1}, every position increment 1.  The
+ * hits are the live documents whose tokens hold the terms next to each other in
+ * this order at least once; freq counts every start position (overlaps count),
+ * and score = BM25 over freq with idf = the float of the sum of the positions'
+ * idf (PhraseWeight / BM25Similarity.idfExplain of Lucene 9.8), on the
+ * statistics tfidf_search uses.  For m = 1 the hits, order and score bits are
+ * those of tfidf_search(term, k = 0).  Order: score descending, doc ascending.
+ * Phrase i is p_utf8[p_offsets[i], p_offsets[i + 1]); p_offsets start at 0 and
+ * never decrease.  A phrase without terms, with a term this shard lacks or that
+ * is not UTF-8 has no hits; one of more than 1024 terms is TFIDF_E_INVALID_ARG
+ * with nothing written.  Output in CSR like tfidf_search_batch_all:
+ * hit_offsets[n_p + 1] and *n_out are always written in full, the payload
+ * (doc_ids, scores, freqs) when *n_out <= cap, else TFIDF_E_BUFFER (cap = 0
+ * with NULL payload pointers asks for the sizes).  The candidates (documents
+ * holding every term) are found by the batched all-hits scorer and re-scanned
+ * on the device; no document text crosses to the host. */
+int tfidf_search_phrase_batch(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                              uint32_t *doc_ids, float *scores, uint32_t *freqs, uint64_t cap, uint64_t *hit_offsets,
+                              uint64_t *n_out);
+int tfidf_reader_search_phrase_batch(tfidf_reader *rd, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                                     uint32_t *doc_ids, float *scores, uint32_t *freqs, uint64_t cap,
+                                     uint64_t *hit_offsets, uint64_t *n_out);
+/* The batch of one phrase. */
+int tfidf_search_phrase(tfidf_index *ix, const uint8_t *p, uint64_t p_len, uint32_t *doc_ids, float *scores,
+                        uint32_t *freqs, uint64_t cap, uint64_t *n_out);
+int tfidf_reader_search_phrase(tfidf_reader *rd, const uint8_t *p, uint64_t p_len, uint32_t *doc_ids, float *scores,
+                               uint32_t *freqs, uint64_t cap, uint64_t *n_out);
+/* Of the last phrase search that ran on this index (any form): the (phrase,
+ * document) rows that were scanned and the row chunks they ran in (test and
+ * bench instruments). */
+int tfidf_last_phrase_stats(const tfidf_index *ix, uint64_t *candidates, uint64_t *row_chunks);
+/* Per-query device time of the last search call on this index (HIP events on the search's stream);
+ * after a phrase search: the last conjunction chunk's scoring, and the whole call as the total. */
 int tfidf_last_search_ms(const tfidf_index *ix, float *ms_scoring, float *ms_total);
 /* Device-time measurement of searches (HIP events around scoring; on by
  * default).  Off for serving: the three event records cost ~17 us per single
@@ -868,6 +903,15 @@ int tfidf_node_fuzzy_terms_batch(tfidf_node *n, const uint8_t *t_utf8, const uin
                                  uint64_t *n_within, uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap,
                                  uint64_t *df, uint8_t *dist, uint64_t cand_cap, uint64_t *n_cands,
                                  uint64_t *n_term_bytes, float *ms_device);
+/* tfidf_search_phrase_batch over the node, after tfidf_node_commit, in both
+ * statistics modes: every shard with documents runs the batch at once on its
+ * own device, doc_ids become global by the shard's doc_base, and the host
+ * merges each phrase's ordered lists by (score descending, global id
+ * ascending); the shards' scores are comparable in GLOBAL mode by
+ * construction.  A shard's failure fails the call with that shard's code. */
+int tfidf_node_search_phrase_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                                   uint64_t *doc_ids, float *scores, uint32_t *freqs, uint64_t cap,
+                                   uint64_t *hit_offsets, uint64_t *n_out);
 typedef struct tfidf_node_stats {
   uint64_t n_shards;
   uint64_t num_docs;      /* all shards */

@@ -26,6 +26,7 @@
 #include "analysis.h"
 #include "compact_plan.h"
 #include "fuzzy_plan.h"
+#include "phrase_plan.h"
 #include "snippet_plan.h"
 #include "tfidf_common.h"
 #include "tfidf_internal.h"
@@ -141,7 +142,7 @@ struct DeviceGuard {
 constexpr uint32_t kMaxBlockCapLog2 = 21;
 
 enum { EV_START, EV_TOK, EV_L0, EV_LONG, EV_D0, EV_DF, EV_BSCAN, EV_CSCAN, EV_SCAT, EV_N };
-enum { QEV_0, QEV_1, QEV_2, QEV_N };   // search timing events (per search context)
+enum { QEV_0, QEV_1, QEV_2, QEV_P0, QEV_P1, QEV_N };   // search timing events (per search context); P0 / P1: a whole phrase search
 
 constexpr size_t kCoalesceMaxDefault = 8192;   // tfidf_search_coalesced: requests per batch
 
@@ -342,6 +343,7 @@ struct SearchCtx {
   DevMem q_in, q_out, cand, cand_n, out_doc, out_score, hits, hits_n, hits_c, hits_s, hits_P, ovf;
   DevMem hl_in, hl_cnt, hl_m, hl_s, hl_o;   // hit highlighting: plan, slice counts, matches, per-row ranges, packed output
   DevMem fz_in, fz_hs, fz_c, fz_tmp;        // fuzzy lookup: staged terms + counters, hashed slots, candidates, sort scratch
+  DevMem ph_in, ph_s, ph_o, ph_tmp;         // phrase search: phrases' keys / sequences / weights, per-row arrays, ordered hits, sort scratch
   PinnedVec<uint32_t> q_host, q_res, q_cand_h;   // q_cand_h: fused single query's block candidates (host merge)
   std::vector<uint64_t> q_merge;
   std::vector<uint32_t> q_units;            // batch scoring units {q, b0, b1, 0} (run_scoring)
@@ -350,7 +352,7 @@ struct SearchCtx {
   explicit SearchCtx(int d)
       : dev(d), q_in(d), q_out(d), cand(d), cand_n(d), out_doc(d), out_score(d), hits(d), hits_n(d), hits_c(d),
         hits_s(d), hits_P(d), ovf(d), hl_in(d), hl_cnt(d), hl_m(d), hl_s(d), hl_o(d), fz_in(d), fz_hs(d), fz_c(d),
-        fz_tmp(d) {}
+        fz_tmp(d), ph_in(d), ph_s(d), ph_o(d), ph_tmp(d) {}
   int init() {
     DeviceGuard g(dev);
     if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess ||
@@ -398,6 +400,7 @@ struct tfidf_index {
   float last_ms_scoring = 0, last_ms_total = 0;
   uint64_t last_hl_item_chunks = 0, last_hl_row_chunks = 0;   // of the last batched highlighting call (ms_mu)
   uint64_t last_fz_scan_chunks = 0, last_fz_cand_chunks = 0;  // of the last fuzzy term lookup (ms_mu)
+  uint64_t last_ph_candidates = 0, last_ph_row_chunks = 0;    // of the last phrase search (ms_mu)
 
   // staged corpus (builder)
   std::shared_ptr<DevMem> text, offsets;   // offsets: u64[n_staged + 1]
@@ -3595,6 +3598,386 @@ extern "C" int tfidf_reader_search_batch_all(tfidf_reader *rd, const uint8_t *q_
   if (!rd || !hit_offsets || !n_out || (n_q && !q_offsets) || (cap && (!doc_ids || !scores)))
     return fail(TFIDF_E_INVALID_ARG, "NULL argument");
   return batch_all_on(rd->ix, *rd->S, *rd->V, q_utf8, q_offsets, n_q, doc_ids, scores, cap, hit_offsets, n_out);
+}
+
+// ---------------------------------------------------------------------------
+// exact phrase search (phrase_plan.h, kernels_phrase.hip): the documents that
+// hold the phrase's terms next to each other in order, scored by BM25 over the
+// phrase frequency (Lucene's PhraseQuery with slop 0).
+//
+// Per call: the phrases are analysed and looked up on the host, one upload
+// carries their key segments, ordinal sequences and weights.  Per all-hits chunk
+// of phrases (all_hits_chunk): the conjunction of each phrase's distinct terms
+// gives the candidate rows (phrase, document), phrase-major on the device; their
+// ids come to the host, their staged ids go back, the extents come to the host
+// (three copies, two synchronisations).  Per item chunk of rows (hl_plan_chunks
+// by the (row, chunk) items): plan upload, count pass, two scans, row offsets,
+// one copy back and a synchronisation.  Per row chunk (by the listed tokens):
+// fill, frequency, score, flag scan, compaction, one copy of the scanned flags
+// and a synchronisation (the hit count sizes the sort), two stable radix passes,
+// emit, and three copies of the chunk's ordered hits to the caller's arrays.
+// Rows are whole documents, so a row chunk's frequencies are final.  A phrase
+// whose rows span several row chunks has one ordered run per chunk, contiguous
+// in the output; the host merges them after the last chunk.
+
+struct PhrasePrep {
+  std::vector<uint32_t> seq;         // ordinal of the term at each phrase position
+  std::vector<uint32_t> slot;        // dictionary slot per distinct term, in order of first appearance
+  std::vector<std::string> terms;    // the distinct terms
+  float w = 0.0f;                    // 1.0f * (float) sum of the positions' idf
+  bool work = false;
+};
+
+// analysed, deduplicated and looked up; a phrase without work (no term, not
+// UTF-8, a term this snapshot lacks) keeps work == false
+static int phrase_prepare(Snapshot &S, StatsView &V, const uint8_t *p, uint64_t n, uint32_t index, PhrasePrep *pp) {
+  std::vector<std::string> toks;
+  if (!analyze(p, n, &toks)) return TFIDF_OK;
+  if (toks.size() > kPhMaxTerms)
+    return fail(TFIDF_E_INVALID_ARG, "phrase %u has %zu terms (more than %u)", index, toks.size(), kPhMaxTerms);
+  if (toks.empty() || V.doc_count == 0) return TFIDF_OK;
+  std::unordered_map<std::string, uint32_t> ordinal;
+  for (const std::string &t : toks) {
+    auto it = ordinal.find(t);
+    if (it == ordinal.end()) {
+      it = ordinal.emplace(t, (uint32_t)pp->terms.size()).first;
+      pp->terms.push_back(t);
+    }
+    pp->seq.push_back(it->second);
+  }
+  for (const std::string &t : pp->terms) {
+    const uint32_t s = lookup_term(S, t);
+    if (s == kInvalidSlot || S.h_df[s] == 0) return TFIDF_OK;
+    pp->slot.push_back(s);
+  }
+  // PhraseWeight.getStats / BM25Similarity.idfExplain(CollectionStatistics, TermStatistics[])
+  double idf = 0.0;
+  for (uint32_t o : pp->seq) {
+    const uint32_t s = pp->slot[o];
+    idf += (double)bm25_idf(V.global ? V.gdf[s] : S.h_df[s], V.doc_count);
+  }
+  volatile float w = 1.0f * (float)idf;
+  pp->w = w;
+  pp->work = true;
+  return TFIDF_OK;
+}
+
+static int phrase_batch_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *p_utf8,
+                           const uint64_t *p_offsets, uint32_t n_p, uint32_t *doc_ids, float *scores, uint32_t *freqs,
+                           uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out) {
+  if (n_p && p_offsets[0] != 0) return fail(TFIDF_E_INVALID_ARG, "p_offsets[0] is not 0");
+  for (uint32_t i = 0; i < n_p; i++)
+    if (p_offsets[i + 1] < p_offsets[i]) return fail(TFIDF_E_INVALID_ARG, "p_offsets decrease at phrase %u", i);
+  if (int e = V.wait_gdf()) return e;
+  DeviceGuard g(ix->cfg.device);                       // slot_term may read a reference occurrence
+  std::vector<PhrasePrep> pp(n_p);
+  for (uint32_t i = 0; i < n_p; i++)
+    if (int rc = phrase_prepare(S, V, p_utf8 + p_offsets[i], p_offsets[i + 1] - p_offsets[i], i, &pp[i])) return rc;
+  for (uint32_t i = 0; i <= n_p; i++) hit_offsets[i] = 0;
+  *n_out = 0;
+  uint64_t n_cand = 0, n_row_chunks = 0;
+  auto report = [&]() {
+    std::lock_guard<std::mutex> lk(ix->ms_mu);
+    ix->last_ph_candidates = n_cand;
+    ix->last_ph_row_chunks = n_row_chunks;
+  };
+  bool any_work = false;
+  for (const PhrasePrep &p : pp) any_work |= p.work;
+  if (!any_work || S.n_docs == 0) {
+    report();
+    return TFIDF_OK;
+  }
+
+  // the conjunctions: every distinct term a MUST clause of its own
+  QueryBatch qb;
+  std::vector<HlKey> keys;
+  std::vector<uint32_t> key_off((size_t)n_p + 1, 0), seq_off((size_t)n_p + 1, 0), seq;
+  std::vector<float> w(n_p, 0.0f);
+  for (uint32_t i = 0; i < n_p; i++) {
+    key_off[i] = (uint32_t)keys.size();
+    seq_off[i] = (uint32_t)seq.size();
+    PreparedQuery pq;
+    if (pp[i].work) {
+      for (size_t o = 0; o < pp[i].slot.size(); o++) {
+        const uint32_t s = pp[i].slot[o];
+        pq.slot.push_back(S.col_of(s));
+        pq.ldf.push_back(S.h_df[s]);
+        pq.w.push_back(bm25_idf(V.global ? V.gdf[s] : S.h_df[s], V.doc_count));
+        pq.role.push_back(kRoleMust << 24 | (uint32_t)o);
+      }
+      pq.meta = (uint32_t)pp[i].slot.size();
+      hl_append_keys(S, pp[i].terms, &keys);
+      seq.insert(seq.end(), pp[i].seq.begin(), pp[i].seq.end());
+      w[i] = pp[i].w;
+      if (keys.size() > (1ull << 30) || seq.size() > (1ull << 30))
+        return fail(TFIDF_E_INVALID_ARG, "more than 2^30 phrase terms in one call");
+    }
+    qb.add(pq);
+  }
+  key_off[n_p] = (uint32_t)keys.size();
+  seq_off[n_p] = (uint32_t)seq.size();
+
+  CtxLease lease(ix);
+  if (lease.rc) return lease.rc;
+  SearchCtx &X = *lease.c;
+  const hipStream_t s = lease.stream();
+
+  // one upload: key segments, ordinal sequences, weights
+  const size_t in_soff = up16(((size_t)n_p + 1) * 4), in_w = up16(in_soff + ((size_t)n_p + 1) * 4),
+               in_seq = up16(in_w + (size_t)n_p * 4), in_keys = up16(in_seq + seq.size() * 4),
+               in_end = up16(in_keys + keys.size() * sizeof(HlKey));
+  std::vector<uint8_t> h_in(in_end);
+  memcpy(h_in.data(), key_off.data(), ((size_t)n_p + 1) * 4);
+  memcpy(h_in.data() + in_soff, seq_off.data(), ((size_t)n_p + 1) * 4);
+  memcpy(h_in.data() + in_w, w.data(), (size_t)n_p * 4);
+  memcpy(h_in.data() + in_seq, seq.data(), seq.size() * 4);
+  memcpy(h_in.data() + in_keys, keys.data(), keys.size() * sizeof(HlKey));
+  HIP_TRY(X.ph_in.reserve(in_end));
+  uint8_t *pb = X.ph_in.as<uint8_t>();
+  if (X.q_timing) HIP_TRY(hipEventRecord(X.ev[QEV_P0], s));
+  HIP_TRY(hipMemcpyAsync(pb, h_in.data(), in_end, hipMemcpyHostToDevice, s));
+  const uint32_t *d_koff = reinterpret_cast<uint32_t *>(pb), *d_soff = reinterpret_cast<uint32_t *>(pb + in_soff),
+                 *d_seq = reinterpret_cast<uint32_t *>(pb + in_seq);
+  const float *d_w = reinterpret_cast<float *>(pb + in_w);
+  const HlKey *d_keys = reinterpret_cast<HlKey *>(pb + in_keys);
+  const uint8_t *d_text = S.text->as<uint8_t>();
+
+  const uint64_t budget_i = hl_budget("TFIDF_HL_CHUNK_ITEMS", kHlChunkItems),
+                 budget_m = hl_budget("TFIDF_HL_CHUNK_MATCHES", kHlChunkMatches);
+  const uint32_t fixed = all_hits_fixed_chunk();
+  std::vector<uint64_t> cnt(n_p, 0), qoff_h, h_ext, row_items, cuts, first, h_row, row_m, sub, h_at;
+  std::vector<uint32_t> runs(n_p, 0), h_docs, h_in2;
+  std::vector<uint8_t> skip;
+  std::vector<HlItem> items;
+  uint64_t run = 0;
+  bool any = false, fits = true;
+  for (uint32_t a = 0; a < n_p;) {
+    uint32_t z = a;
+    uint64_t bound = 0;
+    all_hits_chunk(qb, S, a, n_p, fixed, &z, &bound);
+    const uint32_t nc = z - a;
+    if (int rc = all_hits_score_chunk(ix, S, V, X, s, qb, a, z, bound, &any, nullptr, 0, &qoff_h)) return rc;
+    const uint32_t q_lo = a;
+    a = z;
+    if (qoff_h.empty() || qoff_h[nc] == 0) continue;
+    const uint64_t R = qoff_h[nc];
+    if (R > 0xFFFFFFFFull) return fail(TFIDF_E_INVALID_ARG, "more than 2^32 candidate rows in one chunk of phrases");
+    n_cand += R;
+    const uint32_t *d_docs = X.out_doc.as<uint32_t>();
+    h_docs.resize(R);
+    HIP_TRY(hipMemcpyAsync(h_docs.data(), d_docs, R * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    // staged ids and row -> phrase up, extents back
+    const size_t in_rowq = up16(R * 4), in_ext = up16(in_rowq + R * 4);
+    h_in2.resize(in_ext / 4);
+    for (uint64_t r = 0; r < R; r++) h_in2[r] = (uint32_t)S.staged_of(h_docs[r]);
+    for (uint32_t i = 0; i < nc; i++)
+      for (uint64_t r = qoff_h[i]; r < qoff_h[i + 1]; r++) h_in2[in_rowq / 4 + r] = q_lo + i;
+    HIP_TRY(X.hl_in.reserve(in_ext + R * 16));
+    uint8_t *ib = X.hl_in.as<uint8_t>();
+    const uint32_t *d_staged = reinterpret_cast<uint32_t *>(ib), *d_rowq = reinterpret_cast<uint32_t *>(ib + in_rowq);
+    uint64_t *d_ext = reinterpret_cast<uint64_t *>(ib + in_ext);
+    h_ext.resize(2 * R);
+    HIP_TRY(hipMemcpyAsync(ib, h_in2.data(), in_ext, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_hl_extents(S.offsets->as<uint64_t>(), d_staged, R, d_ext, s));
+    HIP_TRY(hipMemcpyAsync(h_ext.data(), d_ext, R * 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    skip.assign(R, 0);
+    row_items.assign(R, 0);
+    for (uint64_t r = 0; r < R; r++) {
+      const uint64_t L = h_ext[2 * r + 1] - h_ext[2 * r];
+      if (L > 0xFFFFFFFFull) return fail(TFIDF_E_INVALID_ARG, "a candidate document of more than 2^32 bytes");
+      skip[r] = !S.malformed.empty() && std::binary_search(S.malformed.begin(), S.malformed.end(), h_docs[r]);
+      row_items[r] = skip[r] ? 0 : hl_num_chunks(L);
+    }
+    cuts.clear();
+    hl_plan_chunks(row_items.data(), nullptr, 0, R, budget_i, ~0ull, &cuts);
+    for (size_t ci = 0; ci + 1 < cuts.size(); ci++) {
+      const uint64_t r0 = cuts[ci], nr = cuts[ci + 1] - r0;
+      hl_plan(h_ext.data() + 2 * r0, skip.data() + r0, nr, &items, &first);
+      if (items.size() > (1ull << 24))
+        return fail(TFIDF_E_INVALID_ARG, "a document of more than 2^24 chunks of %llu bytes",
+                    (unsigned long long)kHlChunkBytes);
+      const uint32_t n_items = (uint32_t)items.size();
+      const uint64_t n_cnt = (uint64_t)n_items * kHlLanes;
+      const size_t off_row = (nr + 1) * 8, off_items = 2 * off_row,
+                   off_all = up16(off_items + (size_t)n_items * sizeof(HlItem)), off_listed = off_all + (n_cnt + 1) * 8;
+      HIP_TRY(X.hl_cnt.reserve(off_listed + (n_cnt + 1) * 8));
+      uint8_t *cb = X.hl_cnt.as<uint8_t>();
+      uint64_t *d_first = reinterpret_cast<uint64_t *>(cb), *d_row = reinterpret_cast<uint64_t *>(cb + off_row),
+               *d_all = reinterpret_cast<uint64_t *>(cb + off_all),
+               *d_listed = reinterpret_cast<uint64_t *>(cb + off_listed);
+      HlItem *d_items = reinterpret_cast<HlItem *>(cb + off_items);
+      h_row.assign(nr + 1, 0);
+      if (n_items) {
+        // tokens and listed tokens per slice, their scans, the rows' offsets
+        HIP_TRY(hipMemcpyAsync(d_first, first.data(), (nr + 1) * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(d_items, items.data(), (size_t)n_items * sizeof(HlItem), hipMemcpyHostToDevice, s));
+        HIP_TRY(launch_ph_scan(false, d_text, d_ext + 2 * r0, d_items, 0, n_items, d_keys, d_koff, d_rowq + r0,
+                               S.hash_seed, d_first, d_all, d_listed, 0, nullptr, nullptr, s));
+        HIP_TRY(exclusive_scan_u64(d_all, d_all, n_cnt, s));
+        HIP_TRY(exclusive_scan_u64(d_listed, d_listed, n_cnt, s));
+        HIP_TRY(launch_hl_row_offsets(d_listed, d_first, nr, 0, d_row, s));
+        HIP_TRY(hipMemcpyAsync(h_row.data(), d_row, (nr + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+      } else {
+        HIP_TRY(hipMemsetAsync(d_row, 0, (nr + 1) * 8, s));
+      }
+      row_m.resize(nr);
+      for (uint64_t i = 0; i < nr; i++) row_m[i] = h_row[i + 1] - h_row[i];
+      sub.clear();
+      hl_plan_chunks(nullptr, row_m.data(), 0, nr, ~0ull, budget_m, &sub);
+      for (size_t si = 0; si + 1 < sub.size(); si++) {
+        const uint64_t s0 = sub[si], ns = sub[si + 1] - s0, m_base = h_row[s0], T = h_row[s0 + ns] - m_base;
+        const uint64_t Tc = std::max<uint64_t>(T, 1), g0 = r0 + s0;
+        n_row_chunks++;
+        const uint32_t i0 = (uint32_t)first[s0], ni = (uint32_t)first[s0 + ns] - i0;
+        HIP_TRY(X.hl_m.reserve(Tc * 8));
+        uint32_t *m_pos = X.hl_m.as<uint32_t>(), *m_ord = m_pos + Tc;
+        if (T)
+          HIP_TRY(launch_ph_scan(true, d_text, d_ext + 2 * r0, d_items, i0, ni, d_keys, d_koff, d_rowq + r0,
+                                 S.hash_seed, d_first, d_all, d_listed, m_base, m_pos, m_ord, s));
+        // per row: freq, key, flag (scanned in place), then the packed hits
+        const size_t s_flag = up16(ns * 8), s_ckey = up16(s_flag + (ns + 1) * 8), s_freq = up16(s_ckey + ns * 8),
+                     s_crow = up16(s_freq + ns * 4), s_end = up16(s_crow + ns * 4);
+        HIP_TRY(X.ph_s.reserve(s_end));
+        uint8_t *sb = X.ph_s.as<uint8_t>();
+        uint64_t *r_key = reinterpret_cast<uint64_t *>(sb), *r_flag = reinterpret_cast<uint64_t *>(sb + s_flag),
+                 *c_key = reinterpret_cast<uint64_t *>(sb + s_ckey);
+        uint32_t *r_freq = reinterpret_cast<uint32_t *>(sb + s_freq), *c_row = reinterpret_cast<uint32_t *>(sb + s_crow);
+        HIP_TRY(launch_ph_freq(d_row + s0, m_base, m_pos, m_ord, d_rowq + g0, d_seq, d_soff, ns, r_freq, s));
+        HIP_TRY(launch_ph_score(r_freq, d_docs + g0, d_rowq + g0, d_w, V.cache.as<float>(),
+                                S.doc_norm.as<uint8_t>(), ns, r_key, r_flag, s));
+        HIP_TRY(exclusive_scan_u64(r_flag, r_flag, ns, s));
+        HIP_TRY(launch_ph_compact(r_key, r_freq, r_flag, ns, c_key, c_row, s));
+        h_at.resize(ns + 1);
+        HIP_TRY(hipMemcpyAsync(h_at.data(), r_flag, (ns + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        const uint64_t Hn = h_at[ns];
+        if (Hn == 0) continue;
+        // the chunk's phrases and their hits
+        const uint32_t qa = h_in2[in_rowq / 4 + g0], qz = h_in2[in_rowq / 4 + g0 + ns - 1];
+        for (uint32_t q = qa; q <= qz; q++) {
+          const uint64_t lo = std::max<uint64_t>(qoff_h[q - q_lo], g0), hi = std::min<uint64_t>(qoff_h[q - q_lo + 1], g0 + ns);
+          if (hi <= lo) continue;
+          const uint64_t c = h_at[hi - g0] - h_at[lo - g0];
+          cnt[q] += c;
+          if (c) runs[q]++;
+        }
+        fits = fits && run + Hn <= cap && doc_ids && scores && freqs;
+        if (fits) {
+          size_t tb = 0;
+          HIP_TRY(ph_sort_bytes(&tb, (uint32_t)Hn));
+          HIP_TRY(X.ph_tmp.reserve(tb));
+          const size_t o_rowa = up16(Hn * 8), o_qa = up16(o_rowa + Hn * 4), o_qb = up16(o_qa + Hn * 4),
+                       o_doc = up16(o_qb + Hn * 4), o_sc = up16(o_doc + Hn * 4), o_fr = up16(o_sc + Hn * 4),
+                       o_end = up16(o_fr + Hn * 4);
+          HIP_TRY(X.ph_o.reserve(o_end));
+          uint8_t *ob = X.ph_o.as<uint8_t>();
+          uint64_t *key_a = reinterpret_cast<uint64_t *>(ob);
+          uint32_t *row_a = reinterpret_cast<uint32_t *>(ob + o_rowa), *q_a = reinterpret_cast<uint32_t *>(ob + o_qa),
+                   *q_b = reinterpret_cast<uint32_t *>(ob + o_qb), *e_doc = reinterpret_cast<uint32_t *>(ob + o_doc),
+                   *e_fr = reinterpret_cast<uint32_t *>(ob + o_fr);
+          float *e_sc = reinterpret_cast<float *>(ob + o_sc);
+          const uint32_t *rows = nullptr;
+          HIP_TRY(ph_sort(X.ph_tmp.p, tb, c_key, key_a, c_row, row_a, q_a, q_b, d_rowq + g0, qa, qz - qa + 1,
+                          (uint32_t)Hn, &rows, s));
+          HIP_TRY(launch_ph_emit(rows, r_key, r_freq, Hn, e_doc, e_sc, e_fr, s));
+          HIP_TRY(hipMemcpyAsync(doc_ids + run, e_doc, Hn * 4, hipMemcpyDeviceToHost, s));
+          HIP_TRY(hipMemcpyAsync(scores + run, e_sc, Hn * 4, hipMemcpyDeviceToHost, s));
+          HIP_TRY(hipMemcpyAsync(freqs + run, e_fr, Hn * 4, hipMemcpyDeviceToHost, s));
+          HIP_TRY(hipStreamSynchronize(s));
+        }
+        run += Hn;
+      }
+    }
+  }
+  if (X.q_timing) HIP_TRY(hipEventRecord(X.ev[QEV_P1], s));
+  HIP_TRY(hipStreamSynchronize(s));
+  // tfidf_last_search_ms: the conjunctions' scoring of the last chunk of phrases, the whole call on the device
+  set_last_ms(ix, any ? qev_ms(X, QEV_0, QEV_1) : 0.0f, qev_ms(X, QEV_P0, QEV_P1));
+  for (uint32_t i = 0; i < n_p; i++) hit_offsets[i + 1] = hit_offsets[i] + cnt[i];
+  *n_out = run;
+  report();
+  if (!fits) return fail(TFIDF_E_BUFFER, "need %llu result slots", (unsigned long long)run);
+  // a phrase whose rows spanned several row chunks: merge its ordered runs
+  std::vector<uint64_t> order;
+  std::vector<uint32_t> t_doc, t_fr;
+  std::vector<float> t_sc;
+  for (uint32_t q = 0; q < n_p; q++) {
+    if (runs[q] <= 1) continue;
+    const uint64_t b = hit_offsets[q], n = cnt[q];
+    order.resize(n);
+    for (uint64_t i = 0; i < n; i++) {
+      uint32_t bits;
+      memcpy(&bits, scores + b + i, 4);
+      order[i] = ph_sort_key(bits, doc_ids[b + i]);
+    }
+    std::vector<uint64_t> idx(n);
+    for (uint64_t i = 0; i < n; i++) idx[i] = i;
+    std::sort(idx.begin(), idx.end(), [&](uint64_t x, uint64_t y) { return order[x] < order[y]; });
+    t_doc.assign(doc_ids + b, doc_ids + b + n);
+    t_sc.assign(scores + b, scores + b + n);
+    t_fr.assign(freqs + b, freqs + b + n);
+    for (uint64_t i = 0; i < n; i++) {
+      doc_ids[b + i] = t_doc[idx[i]];
+      scores[b + i] = t_sc[idx[i]];
+      freqs[b + i] = t_fr[idx[i]];
+    }
+  }
+  return TFIDF_OK;
+}
+
+static bool phrase_null_args(const void *h, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                             const uint32_t *doc_ids, const float *scores, const uint32_t *freqs, uint64_t cap,
+                             const uint64_t *hit_offsets, const uint64_t *n_out) {
+  return !h || !hit_offsets || !n_out || (n_p && (!p_offsets || (!p_utf8 && p_offsets[n_p]))) ||
+         (cap && (!doc_ids || !scores || !freqs));
+}
+
+extern "C" int tfidf_search_phrase_batch(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                         uint32_t n_p, uint32_t *doc_ids, float *scores, uint32_t *freqs, uint64_t cap,
+                                         uint64_t *hit_offsets, uint64_t *n_out) {
+  if (phrase_null_args(ix, p_utf8, p_offsets, n_p, doc_ids, scores, freqs, cap, hit_offsets, n_out))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::shared_ptr<StatsView> view;
+  const std::shared_ptr<Snapshot> snap = current(ix, &view);
+  if (!snap) return fail(TFIDF_E_STATE, "phrase search before commit");
+  return phrase_batch_on(ix, *snap, *view, p_utf8, p_offsets, n_p, doc_ids, scores, freqs, cap, hit_offsets, n_out);
+}
+
+extern "C" int tfidf_reader_search_phrase_batch(tfidf_reader *rd, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                                uint32_t n_p, uint32_t *doc_ids, float *scores, uint32_t *freqs,
+                                                uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out) {
+  if (phrase_null_args(rd, p_utf8, p_offsets, n_p, doc_ids, scores, freqs, cap, hit_offsets, n_out))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  return phrase_batch_on(rd->ix, *rd->S, *rd->V, p_utf8, p_offsets, n_p, doc_ids, scores, freqs, cap, hit_offsets,
+                         n_out);
+}
+
+// the single forms: the batch of one phrase
+extern "C" int tfidf_search_phrase(tfidf_index *ix, const uint8_t *p, uint64_t p_len, uint32_t *doc_ids, float *scores,
+                                   uint32_t *freqs, uint64_t cap, uint64_t *n_out) {
+  if (!n_out || (!p && p_len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t offs[2] = {0, p_len};
+  uint64_t ho[2];
+  return tfidf_search_phrase_batch(ix, p, offs, 1, doc_ids, scores, freqs, cap, ho, n_out);
+}
+
+extern "C" int tfidf_reader_search_phrase(tfidf_reader *rd, const uint8_t *p, uint64_t p_len, uint32_t *doc_ids,
+                                          float *scores, uint32_t *freqs, uint64_t cap, uint64_t *n_out) {
+  if (!n_out || (!p && p_len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t offs[2] = {0, p_len};
+  uint64_t ho[2];
+  return tfidf_reader_search_phrase_batch(rd, p, offs, 1, doc_ids, scores, freqs, cap, ho, n_out);
+}
+
+extern "C" int tfidf_last_phrase_stats(const tfidf_index *ix, uint64_t *candidates, uint64_t *row_chunks) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->ms_mu);
+  if (candidates) *candidates = ix->last_ph_candidates;
+  if (row_chunks) *row_chunks = ix->last_ph_row_chunks;
+  return TFIDF_OK;
 }
 
 // Concurrent single searches (the reference's Worker.processDocuments runs on

@@ -2274,6 +2274,75 @@ extern "C" int tfidf_node_fuzzy_terms_batch(tfidf_node *n, const uint8_t *t_utf8
   return TFIDF_OK;
 }
 
+// ---------------------------------------------------------------------------
+// exact phrase search over the node: every shard's ordered hits, merged per
+// phrase by (score descending, global id ascending)
+
+extern "C" int tfidf_node_search_phrase_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                              uint32_t n_p, uint64_t *doc_ids, float *scores, uint32_t *freqs,
+                                              uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out) {
+  if (!n || !hit_offsets || !n_out || (n_p && (!p_offsets || (!p_utf8 && p_offsets[n_p]))) ||
+      (cap && (!doc_ids || !scores || !freqs)))
+    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lk(n->mu);
+  if (!n->committed) return errf(TFIDF_E_STATE, "phrase search before tfidf_node_commit");
+  struct ShardHits {
+    std::vector<uint32_t> docs, freqs;
+    std::vector<float> scores;
+    std::vector<uint64_t> off;
+    bool ran = false;
+  };
+  const size_t G = n->shards.size();
+  std::vector<ShardHits> sh(G);
+  // one shard's batch: once with a guessed payload size, once more with the size it reports
+  if (int rc = n->pool->run([&](uint32_t g) {
+        tfidf_index *ix = n->shards[g];
+        ShardHits &b = sh[g];
+        if (!index_committed(ix) || index_num_docs(ix) == 0) return (int)TFIDF_OK;
+        b.off.assign((size_t)n_p + 1, 0);
+        uint64_t total = 0, guess = std::min<uint64_t>(64ull * n_p + 4096, 1ull << 24);
+        int rc = TFIDF_OK;
+        for (int attempt = 0; attempt < 2; attempt++) {
+          b.docs.resize(guess);
+          b.scores.resize(guess);
+          b.freqs.resize(guess);
+          rc = tfidf_search_phrase_batch(ix, p_utf8, p_offsets, n_p, b.docs.data(), b.scores.data(), b.freqs.data(),
+                                         guess, b.off.data(), &total);
+          if (rc != TFIDF_E_BUFFER) break;
+          guess = total;
+        }
+        b.ran = rc == TFIDF_OK;
+        return rc;
+      }))
+    return rc;
+  uint64_t total = 0;
+  hit_offsets[0] = 0;
+  for (uint32_t i = 0; i < n_p; i++) {
+    for (size_t g = 0; g < G; g++)
+      if (sh[g].ran) total += sh[g].off[i + 1] - sh[g].off[i];
+    hit_offsets[i + 1] = total;
+  }
+  *n_out = total;
+  if (total > cap) return errf(TFIDF_E_BUFFER, "need %llu result slots", (unsigned long long)total);
+  // the shards' lists of a phrase are ordered, and ascending shard = ascending global id among equal scores
+  std::vector<uint64_t> at(G);
+  for (uint32_t i = 0; i < n_p; i++) {
+    for (size_t g = 0; g < G; g++) at[g] = sh[g].ran ? sh[g].off[i] : 0;
+    for (uint64_t o = hit_offsets[i]; o < hit_offsets[i + 1]; o++) {
+      size_t best = G;
+      for (size_t g = 0; g < G; g++) {
+        if (!sh[g].ran || at[g] >= sh[g].off[i + 1]) continue;
+        if (best == G || sh[g].scores[at[g]] > sh[best].scores[at[best]]) best = g;
+      }
+      const uint64_t j = at[best]++;
+      doc_ids[o] = n->doc_base[best] + sh[best].docs[j];
+      scores[o] = sh[best].scores[j];
+      freqs[o] = sh[best].freqs[j];
+    }
+  }
+  return TFIDF_OK;
+}
+
 extern "C" int tfidf_node_stats_get(const tfidf_node *n, tfidf_node_stats *out) {
   if (!n || !out) return errf(TFIDF_E_INVALID_ARG, "NULL argument");
   out->n_shards = n->shards.size();

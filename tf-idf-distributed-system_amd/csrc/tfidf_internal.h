@@ -475,6 +475,26 @@ hipError_t launch_fz_select(const uint64_t *keys, const uint32_t *seg, uint32_t 
 hipError_t launch_fz_gather(const uint64_t *keys, const uint32_t *slots, const uint32_t *seg, const uint32_t *out_off,
                             uint32_t n_terms, uint64_t *o_keys, uint32_t *o_slots, hipStream_t s);
 
+// --- exact phrase search (kernels_phrase.hip; rules in phrase_plan.h) ---
+hipError_t launch_ph_scan(bool fill, const uint8_t *text, const uint64_t *ext, const HlItem *items, uint32_t i0,
+                          uint32_t ni, const HlKey *keys, const uint32_t *key_off, const uint32_t *row_q,
+                          uint64_t seed, const uint64_t *first, uint64_t *all, uint64_t *listed, uint64_t m_base,
+                          uint32_t *o_pos, uint32_t *o_ord, hipStream_t s);
+hipError_t launch_ph_freq(const uint64_t *row_off, uint64_t m_base, const uint32_t *pos, const uint32_t *ord,
+                          const uint32_t *row_q, const uint32_t *seq, const uint32_t *seq_off, uint64_t n,
+                          uint32_t *freq, hipStream_t s);
+hipError_t launch_ph_score(const uint32_t *freq, const uint32_t *docs, const uint32_t *row_q, const float *w,
+                           const float *cache, const uint8_t *norm, uint64_t n, uint64_t *key, uint64_t *flag,
+                           hipStream_t s);
+hipError_t launch_ph_compact(const uint64_t *key, const uint32_t *freq, const uint64_t *at, uint64_t n,
+                             uint64_t *o_key, uint32_t *o_row, hipStream_t s);
+hipError_t ph_sort_bytes(size_t *tmp_bytes, uint32_t n);
+hipError_t ph_sort(void *tmp, size_t tmp_bytes, const uint64_t *key_in, uint64_t *key_a, uint32_t *row_in,
+                   uint32_t *row_a, uint32_t *q_a, uint32_t *q_b, const uint32_t *row_q, uint32_t q0, uint32_t n_q,
+                   uint32_t n, const uint32_t **rows_out, hipStream_t s);
+hipError_t launch_ph_emit(const uint32_t *rows, const uint64_t *key, const uint32_t *freq, uint64_t n, uint32_t *o_doc,
+                          float *o_score, uint32_t *o_freq, hipStream_t s);
+
 // --- index internals the node-level orchestration reads (tfidf_capi.hip) ---
 }  // namespace tfidf
 struct tfidf_index;

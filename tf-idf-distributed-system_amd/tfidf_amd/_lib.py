@@ -128,6 +128,15 @@ SIGNATURES = {
     "tfidf_fuzzy_terms": _FUZZY_SINGLE_SIG,
     "tfidf_reader_fuzzy_terms": _FUZZY_SINGLE_SIG,
     "tfidf_last_fuzzy_chunks": (C.c_int, [VP, U64P, U64P]),
+    "tfidf_search_phrase_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U32P, F32P, U32P, C.c_uint64, U64P,
+                                            U64P]),
+    "tfidf_reader_search_phrase_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U32P, F32P, U32P, C.c_uint64,
+                                                   U64P, U64P]),
+    "tfidf_search_phrase": (C.c_int, [VP, C.c_char_p, C.c_uint64, U32P, F32P, U32P, C.c_uint64, U64P]),
+    "tfidf_reader_search_phrase": (C.c_int, [VP, C.c_char_p, C.c_uint64, U32P, F32P, U32P, C.c_uint64, U64P]),
+    "tfidf_node_search_phrase_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U64P, F32P, U32P, C.c_uint64,
+                                                 U64P, U64P]),
+    "tfidf_last_phrase_stats": (C.c_int, [VP, U64P, U64P]),
     "tfidf_query_positive_terms": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, U64P, U64P]),
     "tfidf_set_hash_attempt": (C.c_int, [VP, C.c_uint32]),
     "tfidf_get_commit_timing": (C.c_int, [VP, C.POINTER(CommitTiming)]),

@@ -485,6 +485,14 @@ class Node:
         return E._fuzzy_lists(E._fuzzy_batch_arrays(L.load().tfidf_node_fuzzy_terms_batch, self._h, terms, max_edits,
                                                     prefix_len, max_out, df_dtype=np.uint64))
 
+    def search_phrase_batch(self, phrases):
+        """ShardIndex.search_phrase_batch over the node: [[(global doc, score,
+        freq)]], every shard's hits merged per phrase by (score desc, global id
+        asc) (tfidf_node_search_phrase_batch)."""
+        from . import engine as E
+        return E._phrase_lists(*E._phrase_batch_arrays(L.load().tfidf_node_search_phrase_batch, self._h, phrases,
+                                                       dtype=np.uint64))
+
 
 class NodeStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("n_shards", "num_docs", "doc_count", "sum_ttf", "num_terms", "transport")]

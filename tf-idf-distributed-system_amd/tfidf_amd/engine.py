@@ -288,6 +288,53 @@ def _hit_lists(docs, scores, offs):
     return [list(zip(d[o[i]:o[i + 1]], s[o[i]:o[i + 1]])) for i in range(len(o) - 1)]
 
 
+def _phrase_batch_arrays(fn, handle, phrases, cap=None, dtype=np.uint32):
+    """tfidf_[reader_|node_]search_phrase_batch: one call for the sizes (or with
+    ``cap`` result slots), one more for the payload when that was too small.
+    -> (docs dtype[], scores float32[], freqs uint32[], offsets uint64[n_p + 1])."""
+    n_p = len(phrases)
+    blob, offs = _key_arrays(phrases)
+    hit_offs = np.zeros(n_p + 1, np.uint64)
+    n = C.c_uint64()
+    ct = C.c_uint32 if dtype == np.uint32 else C.c_uint64
+    cap = 0 if cap is None else cap
+    for _ in range(2):
+        docs = np.empty(max(cap, 1), dtype)
+        scores = np.empty(max(cap, 1), np.float32)
+        freqs = np.empty(max(cap, 1), np.uint32)
+        rc = fn(handle, blob, L.ptr(offs, C.c_uint64), n_p, L.ptr(docs, ct) if cap else None,
+                L.ptr(scores, C.c_float) if cap else None, L.ptr(freqs, C.c_uint32) if cap else None, cap,
+                L.ptr(hit_offs, C.c_uint64), C.byref(n))
+        if rc != L.E_BUFFER:
+            break
+        cap = n.value
+    L.check(rc)
+    return docs[:n.value], scores[:n.value], freqs[:n.value], hit_offs
+
+
+def _phrase_lists(docs, scores, freqs, offs):
+    d, s, f, o = docs.tolist(), scores.tolist(), freqs.tolist(), offs.tolist()
+    return [list(zip(d[o[i]:o[i + 1]], s[o[i]:o[i + 1]], f[o[i]:o[i + 1]])) for i in range(len(o) - 1)]
+
+
+def _phrase_single(fn, handle, phrase):
+    """tfidf_[reader_]search_phrase -> [(doc, score, freq)]."""
+    n = C.c_uint64()
+    cap = 0
+    for _ in range(2):
+        docs = np.empty(max(cap, 1), np.uint32)
+        scores = np.empty(max(cap, 1), np.float32)
+        freqs = np.empty(max(cap, 1), np.uint32)
+        rc = fn(handle, phrase, len(phrase), L.ptr(docs, C.c_uint32) if cap else None,
+                L.ptr(scores, C.c_float) if cap else None, L.ptr(freqs, C.c_uint32) if cap else None, cap, C.byref(n))
+        if rc != L.E_BUFFER:
+            break
+        cap = n.value
+    L.check(rc)
+    m = n.value
+    return list(zip(docs[:m].tolist(), scores[:m].tolist(), freqs[:m].tolist()))
+
+
 class ShardIndex:
     def __init__(self, device=0, k1=1.2, b=0.75, vocab_capacity_log2=18, stats_mode=L.STATS_SHARD,
                  inversion=L.INVERSION_AUTO):
@@ -443,6 +490,31 @@ class ShardIndex:
         this index or one of its readers (tfidf_last_fuzzy_chunks)."""
         a, b = C.c_uint64(), C.c_uint64()
         L.check(L.load().tfidf_last_fuzzy_chunks(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def search_phrase(self, phrase: bytes):
+        """[(doc, score, freq)] of the documents that hold the analysed terms
+        of ``phrase`` next to each other in order (tfidf_search_phrase): freq
+        counts every start position, score is BM25 over freq with the summed
+        idf of the positions; (score desc, doc asc).  The bytes are text, not
+        a query: operators and quotes are analysed away."""
+        return _phrase_single(L.load().tfidf_search_phrase, self._h, phrase)
+
+    def search_phrase_batch_arrays(self, phrases, cap=None):
+        """(docs uint32[], scores float32[], freqs uint32[], offsets uint64[n_p + 1])
+        of tfidf_search_phrase_batch; phrase i's hits are [offsets[i], offsets[i + 1])."""
+        return _phrase_batch_arrays(L.load().tfidf_search_phrase_batch, self._h, phrases, cap)
+
+    def search_phrase_batch(self, phrases):
+        """[search_phrase(p) for p in phrases] in one pass; a phrase that is
+        not UTF-8 has no hits."""
+        return _phrase_lists(*self.search_phrase_batch_arrays(phrases))
+
+    def last_phrase_stats(self):
+        """(candidate rows scanned, row chunks) of the last phrase search on
+        this index or one of its readers (tfidf_last_phrase_stats)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        L.check(L.load().tfidf_last_phrase_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def set_hash_attempt(self, attempt):
@@ -808,6 +880,18 @@ class Reader:
     def fuzzy_terms_batch(self, terms, max_edits=2, prefix_len=0, max_out=10):
         """ShardIndex.fuzzy_terms_batch on this reader's snapshot."""
         return _fuzzy_lists(self.fuzzy_terms_batch_arrays(terms, max_edits, prefix_len, max_out))
+
+    def search_phrase(self, phrase: bytes):
+        """ShardIndex.search_phrase on this reader's snapshot."""
+        return _phrase_single(L.load().tfidf_reader_search_phrase, self._h, phrase)
+
+    def search_phrase_batch_arrays(self, phrases, cap=None):
+        """ShardIndex.search_phrase_batch_arrays on this reader's snapshot."""
+        return _phrase_batch_arrays(L.load().tfidf_reader_search_phrase_batch, self._h, phrases, cap)
+
+    def search_phrase_batch(self, phrases):
+        """ShardIndex.search_phrase_batch on this reader's snapshot."""
+        return _phrase_lists(*self.search_phrase_batch_arrays(phrases))
 
     def doc_keys(self):
         lib = L.load()

@@ -147,6 +147,20 @@ class Worker:
             hits = rd.search(query.encode(), 0)
             return [document_score_info(rd.doc_key(d).decode(), s) for d, s in hits]
 
+    # No reference counterpart (QueryParser.escape neutralises the quotes,
+    # Worker.java:225-227): the documents that hold the analysed words of
+    # ``query`` next to each other in order, every hit, in the order and shape
+    # of search_index; DocumentScoreInfo JSON extended with "freq" (the
+    # phrase's occurrences in the document).
+    def search_phrase(self, query: str):
+        with self.index.reader() as rd:
+            out = []
+            for d, s, f in rd.search_phrase(query.encode()):
+                info = document_score_info(rd.doc_key(d).decode(), s)
+                info["freq"] = f
+                out.append(info)
+            return out
+
     # No reference counterpart ("contents" is stored with Store.NO,
     # Worker.java:216): the top-k hits with the passage that shows why each
     # matched, search and snippets on one reader.  DocumentScoreInfo JSON
