@@ -533,6 +533,71 @@ int tfidf_reader_search_phrase(tfidf_reader *rd, const uint8_t *p, uint64_t p_le
  * document) rows that were scanned and the row chunks they ran in (test and
  * bench instruments). */
 int tfidf_last_phrase_stats(const tfidf_index *ix, uint64_t *candidates, uint64_t *row_chunks);
+/* ---- more-like-this: documents similar to a seed document (Lucene 9.8
+ * MoreLikeThis restated on the index's own forward rows; the reference stores
+ * no term vectors and cannot offer it; DESIGN.md section 2, "More like this") ----
+ * A seed is a committed doc id of the snapshot.  Its candidate terms are the
+ * terms t of its indexed row with tf >= min_tf, df(t) >= min_df and, when
+ * max_df != 0, df(t) <= max_df, where df is the shard's own df of that snapshot
+ * (tfidf_set_global_* does not change the selection).  A candidate's score is
+ * (float)tf * idf with idf = (float)(log((num_docs + 1) / (double)(df + 1)) +
+ * 1.0) (ClassicSimilarity.idf; num_docs = the snapshot's live documents).  The
+ * interesting terms are the first max_terms candidates by score bits
+ * descending, then lower-cased term bytes ascending (unsigned).
+ * tfidf_mlt_params_init sets Lucene's defaults: min_tf 2, min_df 5, max_df 0 (no
+ * upper bound), max_terms 25; params == NULL means those.  min_tf 0 is read as
+ * 1; max_terms outside 1..1024 is TFIDF_E_INVALID_ARG.
+ * Seeds may repeat and come in any order; n == 0 is legal; n > 65536 or a seed
+ * >= num_docs is TFIDF_E_INVALID_ARG with nothing written; TFIDF_E_STATE before
+ * the first commit.  A seed that is empty, or was indexed empty (malformed
+ * UTF-8), has no terms and no hits.
+ *
+ * tfidf_mlt_terms_batch (MoreLikeThis.retrieveInterestingTerms): CSR output.
+ * term_offsets[n + 1], n_candidates[n] (the candidates before truncation),
+ * *n_terms and *n_term_bytes are always written; then, in selection order,
+ * blob_offsets[*n_terms + 1] into the term blob `terms`, tf, df and score per
+ * term when *n_terms <= term_cap and *n_term_bytes <= terms_cap, else
+ * TFIDF_E_BUFFER (caps 0 with NULL payload pointers ask for the sizes).
+ *
+ * tfidf_more_like_this_batch: per seed the top k (1..1024) of the disjunction
+ * of its interesting terms, one SHOULD TermQuery each in selection order,
+ * scored exactly as tfidf_search scores that disjunction on the snapshot (BM25
+ * with the statistics in force, GLOBAL ones when set); score descending, doc
+ * ascending; layout of tfidf_search_batch: doc_ids[n * k], scores[n * k],
+ * counts[n].  flags & TFIDF_MLT_EXCLUDE_SEED removes the seed from its own
+ * list: the list is then the top k of the other documents (k <= 1023).
+ * The device reads only the seeds' rows and hands the host each seed's first
+ * max_terms candidates and their score ties; no row's full term list and no
+ * part of the vocabulary crosses to the host. */
+typedef struct tfidf_mlt_params {
+  uint32_t min_tf, min_df, max_df, max_terms;
+} tfidf_mlt_params;
+#define TFIDF_MLT_EXCLUDE_SEED 1u
+int tfidf_mlt_params_init(tfidf_mlt_params *params);
+int tfidf_mlt_terms_batch(tfidf_index *ix, const uint32_t *seeds, uint32_t n, const tfidf_mlt_params *params,
+                          uint64_t *term_offsets, uint64_t *n_candidates, uint64_t *blob_offsets, uint8_t *terms,
+                          uint64_t terms_cap, uint32_t *tf, uint32_t *df, float *score, uint64_t term_cap,
+                          uint64_t *n_terms, uint64_t *n_term_bytes);
+int tfidf_reader_mlt_terms_batch(tfidf_reader *rd, const uint32_t *seeds, uint32_t n, const tfidf_mlt_params *params,
+                                 uint64_t *term_offsets, uint64_t *n_candidates, uint64_t *blob_offsets,
+                                 uint8_t *terms, uint64_t terms_cap, uint32_t *tf, uint32_t *df, float *score,
+                                 uint64_t term_cap, uint64_t *n_terms, uint64_t *n_term_bytes);
+int tfidf_more_like_this_batch(tfidf_index *ix, const uint32_t *seeds, uint32_t n, const tfidf_mlt_params *params,
+                               uint32_t k, uint32_t flags, uint32_t *doc_ids, float *scores, uint32_t *counts);
+int tfidf_reader_more_like_this_batch(tfidf_reader *rd, const uint32_t *seeds, uint32_t n,
+                                      const tfidf_mlt_params *params, uint32_t k, uint32_t flags, uint32_t *doc_ids,
+                                      float *scores, uint32_t *counts);
+/* The batch of one seed: doc_ids[k], scores[k], *count. */
+int tfidf_more_like_this(tfidf_index *ix, uint32_t seed, const tfidf_mlt_params *params, uint32_t k, uint32_t flags,
+                         uint32_t *doc_ids, float *scores, uint32_t *count);
+int tfidf_reader_more_like_this(tfidf_reader *rd, uint32_t seed, const tfidf_mlt_params *params, uint32_t k,
+                                uint32_t flags, uint32_t *doc_ids, float *scores, uint32_t *count);
+/* Of the last more-like-this call that ran on this index (any form): the
+ * forward-row entries the device scanned (the seeds' distinct terms, a repeated
+ * seed counted again) and the candidate chunks filled and sorted (test and
+ * bench instruments).  tfidf_last_search_ms then holds the last scoring chunk
+ * and, as the total, the whole call's device time. */
+int tfidf_last_mlt_stats(const tfidf_index *ix, uint64_t *row_entries_scanned, uint64_t *cand_chunks);
 /* Per-query device time of the last search call on this index (HIP events on the search's stream);
  * after a phrase search: the last conjunction chunk's scoring, and the whole call as the total. */
 int tfidf_last_search_ms(const tfidf_index *ix, float *ms_scoring, float *ms_total);
@@ -912,6 +977,20 @@ int tfidf_node_fuzzy_terms_batch(tfidf_node *n, const uint8_t *t_utf8, const uin
 int tfidf_node_search_phrase_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
                                    uint64_t *doc_ids, float *scores, uint32_t *freqs, uint64_t cap,
                                    uint64_t *hit_offsets, uint64_t *n_out);
+/* tfidf_more_like_this_batch over the node, after tfidf_node_commit, in both
+ * statistics modes.  Seeds are global ids, routed by doc_base as
+ * tfidf_node_doc_key routes them; one >= the node's num_docs is
+ * TFIDF_E_INVALID_ARG with nothing written.  The shard that owns a seed selects
+ * its interesting terms by its own df and num_docs; the term strings go to every
+ * shard with documents, which looks them up in its own dictionary (a term it
+ * lacks has no scorer), scores the disjunction with its statistics in force
+ * and returns its top k (k + 1 when excluding); the host merges per seed by
+ * (score descending, global id ascending), drops the seed when asked and
+ * truncates to k.  doc_ids[n * k], scores[n * k], counts[n].  A shard's failure
+ * fails the call with that shard's code. */
+int tfidf_node_more_like_this_batch(tfidf_node *n, const uint64_t *seeds, uint32_t n_seeds,
+                                    const tfidf_mlt_params *params, uint32_t k, uint32_t flags, uint64_t *doc_ids,
+                                    float *scores, uint32_t *counts);
 typedef struct tfidf_node_stats {
   uint64_t n_shards;
   uint64_t num_docs;      /* all shards */

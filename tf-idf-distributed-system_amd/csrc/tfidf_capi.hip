@@ -26,6 +26,7 @@
 #include "analysis.h"
 #include "compact_plan.h"
 #include "fuzzy_plan.h"
+#include "mlt_plan.h"
 #include "phrase_plan.h"
 #include "snippet_plan.h"
 #include "tfidf_common.h"
@@ -313,9 +314,14 @@ struct Snapshot {
   std::shared_ptr<StatsView> stats;    // replaced under tfidf_index::snap_mu
   std::unordered_map<uint32_t, std::string> term_cache;   // hashed slots' term strings (slot_term)
   std::mutex term_mu;
+  // more-like-this: ClassicSimilarity idf of every df 0 .. n_docs (mlt_idf_table), built and uploaded on first use
+  DevMem mlt_idf;
+  std::vector<float> h_mlt_idf;
+  bool mlt_ready = false;
+  std::mutex mlt_mu;
   explicit Snapshot(int d)
       : dev(d), dict(d), csr(d), csr_esc(d), post_esc(d), doc_len(d), doc_nuniq(d), doc_norm(d), rsplit(d), blk(d),
-        bbase(d), post(d), row_off(d), toff(d), tdf(d), crank(d), sdf(d) {}
+        bbase(d), post(d), row_off(d), toff(d), tdf(d), crank(d), sdf(d), mlt_idf(d) {}
   const uint32_t *df_dev() const { return term_major ? tdf.as<uint32_t>() : sdf.as<uint32_t>(); }   // per slot
   // what the scorers index a term's postings by: its column (block-major) or
   // its dictionary slot (term-major); the scorers' C is the matching count
@@ -344,6 +350,7 @@ struct SearchCtx {
   DevMem hl_in, hl_cnt, hl_m, hl_s, hl_o;   // hit highlighting: plan, slice counts, matches, per-row ranges, packed output
   DevMem fz_in, fz_hs, fz_c, fz_tmp;        // fuzzy lookup: staged terms + counters, hashed slots, candidates, sort scratch
   DevMem ph_in, ph_s, ph_o, ph_tmp;         // phrase search: phrases' keys / sequences / weights, per-row arrays, ordered hits, sort scratch
+  DevMem ml_in, ml_c, ml_tmp;               // more-like-this: staged seeds + row extents + counters, candidates, sort scratch
   PinnedVec<uint32_t> q_host, q_res, q_cand_h;   // q_cand_h: fused single query's block candidates (host merge)
   std::vector<uint64_t> q_merge;
   std::vector<uint32_t> q_units;            // batch scoring units {q, b0, b1, 0} (run_scoring)
@@ -352,7 +359,7 @@ struct SearchCtx {
   explicit SearchCtx(int d)
       : dev(d), q_in(d), q_out(d), cand(d), cand_n(d), out_doc(d), out_score(d), hits(d), hits_n(d), hits_c(d),
         hits_s(d), hits_P(d), ovf(d), hl_in(d), hl_cnt(d), hl_m(d), hl_s(d), hl_o(d), fz_in(d), fz_hs(d), fz_c(d),
-        fz_tmp(d), ph_in(d), ph_s(d), ph_o(d), ph_tmp(d) {}
+        fz_tmp(d), ph_in(d), ph_s(d), ph_o(d), ph_tmp(d), ml_in(d), ml_c(d), ml_tmp(d) {}
   int init() {
     DeviceGuard g(dev);
     if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess ||
@@ -401,6 +408,7 @@ struct tfidf_index {
   uint64_t last_hl_item_chunks = 0, last_hl_row_chunks = 0;   // of the last batched highlighting call (ms_mu)
   uint64_t last_fz_scan_chunks = 0, last_fz_cand_chunks = 0;  // of the last fuzzy term lookup (ms_mu)
   uint64_t last_ph_candidates = 0, last_ph_row_chunks = 0;    // of the last phrase search (ms_mu)
+  uint64_t last_mlt_entries = 0, last_mlt_chunks = 0;         // of the last more-like-this call (ms_mu)
 
   // staged corpus (builder)
   std::shared_ptr<DevMem> text, offsets;   // offsets: u64[n_staged + 1]
@@ -1747,6 +1755,10 @@ static int commit_once(tfidf_index *ix, Snapshot &S) {
   {
     std::lock_guard<std::mutex> tl(S.term_mu);
     S.term_cache.clear();
+  }
+  {
+    std::lock_guard<std::mutex> ml(S.mlt_mu);
+    S.mlt_ready = false;
   }
   // statistics in force: the shard's own (a GLOBAL exchange publishes another view)
   if (!S.stats || S.stats.use_count() > 1) S.stats = std::make_shared<StatsView>(ix->cfg.device);
@@ -3977,6 +3989,459 @@ extern "C" int tfidf_last_phrase_stats(const tfidf_index *ix, uint64_t *candidat
   std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->ms_mu);
   if (candidates) *candidates = ix->last_ph_candidates;
   if (row_chunks) *row_chunks = ix->last_ph_row_chunks;
+  return TFIDF_OK;
+}
+
+// ---------------------------------------------------------------------------
+// more-like-this ("More like this"; rules in mlt_plan.h).
+// The seeds' forward rows are scanned on the device (kernels_mlt.hip): count
+// the candidates per seed, fill (key, value) pairs by candidate chunks, sort,
+// select each seed's first max_terms and their score ties.  Only those (slot,
+// tf) pairs come to the host, where the strings are materialised (exact keys
+// from the mirror, hashed ones from their reference occurrence) and the bytes
+// break the ties.  The seeds' queries are built from the slots and go through
+// the batched top-k scorer like any search batch.
+
+// the snapshot's idf table on the device, built and uploaded by the first call that needs it
+static int mlt_table(Snapshot &S, hipStream_t s, const float **d_idf) {
+  std::lock_guard<std::mutex> lk(S.mlt_mu);
+  if (!S.mlt_ready) {
+    mlt_idf_table(S.n_docs, &S.h_mlt_idf);
+    HIP_TRY(S.mlt_idf.reserve(S.h_mlt_idf.size() * 4));
+    HIP_TRY(hipMemcpyAsync(S.mlt_idf.p, S.h_mlt_idf.data(), S.h_mlt_idf.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    S.mlt_ready = true;
+  }
+  *d_idf = S.mlt_idf.as<float>();
+  return TFIDF_OK;
+}
+
+static int mlt_rules(const tfidf_mlt_params *p, MltRules *r) {
+  tfidf_mlt_params d;
+  tfidf_mlt_params_init(&d);
+  if (p) d = *p;
+  if (d.max_terms < 1 || d.max_terms > kMltMaxTerms)
+    return fail(TFIDF_E_INVALID_ARG, "max_terms %u outside 1..%u", d.max_terms, kMltMaxTerms);
+  *r = MltRules{d.min_tf ? d.min_tf : 1u, d.min_df, d.max_df, d.max_terms};
+  return TFIDF_OK;
+}
+
+static int mlt_check_seeds(const Snapshot &S, const uint32_t *seeds, uint32_t n) {
+  if (n > kMltMaxSeeds) return fail(TFIDF_E_INVALID_ARG, "more than %u seeds in one call", kMltMaxSeeds);
+  if (n && !seeds) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  for (uint32_t i = 0; i < n; i++)
+    if (seeds[i] >= S.n_docs)
+      return fail(TFIDF_E_INVALID_ARG, "seed %u (doc %u) out of range: %llu documents", i, seeds[i],
+                  (unsigned long long)S.n_docs);
+  return TFIDF_OK;
+}
+
+// interesting terms of checked seeds, on the caller's search context
+static int mlt_terms_on(tfidf_index *ix, Snapshot &S, SearchCtx &X, hipStream_t s, const uint32_t *seeds, uint32_t n,
+                        const MltRules &R, MltLists *out) {
+  out->terms.assign(n, {});
+  out->n_cand.assign(n, 0);
+  uint64_t n_entries = 0, n_fill = 0;
+  auto publish = [&]() {
+    std::lock_guard<std::mutex> lk(ix->ms_mu);
+    ix->last_mlt_entries = n_entries;
+    ix->last_mlt_chunks = n_fill;
+  };
+  if (n == 0 || S.n_docs == 0) { publish(); return TFIDF_OK; }
+  const float *d_idf = nullptr;
+  if (int rc = mlt_table(S, s, &d_idf)) return rc;
+  const uint64_t budget = std::min<uint64_t>(hl_budget("TFIDF_MLT_CAND_BUDGET", kMltCandBudget), 1ull << 30);
+  const int max_grid = ix->num_cus * 8;
+
+  // staged seeds and counters: row_base u64[n], row_off u64[n + 1], then u32: doc[n], staged[n], counts[n],
+  // seg and out_off [n + 1] each, take[n], the fill cursor
+  const size_t in_off = (size_t)n * 8, in_doc = in_off + ((size_t)n + 1) * 8, in_st = in_doc + (size_t)n * 4,
+               in_cnt = in_st + (size_t)n * 4, in_seg = in_cnt + (size_t)n * 4, in_oo = in_seg + ((size_t)n + 1) * 4,
+               in_take = in_oo + ((size_t)n + 1) * 4, in_cur = in_take + (size_t)n * 4, in_end = in_cur + 8;
+  HIP_TRY(X.ml_in.reserve(in_end));
+  uint8_t *ib = X.ml_in.as<uint8_t>();
+  uint64_t *d_base = reinterpret_cast<uint64_t *>(ib), *d_off = reinterpret_cast<uint64_t *>(ib + in_off);
+  uint32_t *d_doc = reinterpret_cast<uint32_t *>(ib + in_doc), *d_st = reinterpret_cast<uint32_t *>(ib + in_st),
+           *d_cnt = reinterpret_cast<uint32_t *>(ib + in_cnt), *d_seg = reinterpret_cast<uint32_t *>(ib + in_seg),
+           *d_oo = reinterpret_cast<uint32_t *>(ib + in_oo), *d_take = reinterpret_cast<uint32_t *>(ib + in_take),
+           *d_cur = reinterpret_cast<uint32_t *>(ib + in_cur);
+  std::vector<uint32_t> h_in((size_t)2 * n);
+  for (uint32_t i = 0; i < n; i++) {
+    h_in[i] = seeds[i];
+    h_in[(size_t)n + i] = (uint32_t)S.staged_of(seeds[i]);
+  }
+  HIP_TRY(hipMemcpyAsync(d_doc, h_in.data(), (size_t)2 * n * 4, hipMemcpyHostToDevice, s));   // doc[n] | staged[n]
+  HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)n * 4, s));
+  HIP_TRY(launch_mlt_extents(S.offsets->as<uint64_t>(), S.doc_nuniq.as<uint32_t>(), d_doc, d_st, n, d_base, d_off, s));
+  HIP_TRY(exclusive_scan_u64(d_off, d_off, n, s));
+
+  MltScan a{};
+  a.csr = S.csr.as<uint32_t>();
+  a.csr_words = S.csr.bytes / 4;
+  a.rsplit = S.rsplit.as<uint32_t>();
+  a.R = S.R;
+  a.range_shift = S.range_shift;
+  a.C = S.C;
+  a.csr_esc = S.csr_esc.as<uint64_t>();
+  a.n_esc = S.h_esc.size();
+  a.df = S.df_dev();
+  a.idf = d_idf;
+  a.n_docs = S.n_docs;
+  a.seed_doc = d_doc;
+  a.row_base = d_base;
+  a.row_off = d_off;
+  a.s0 = 0;
+  a.s1 = n;
+  a.min_tf = R.min_tf;
+  a.min_df = R.min_df;
+  a.max_df = R.max_df;
+  a.counts = d_cnt;
+  a.cursor = d_cur;
+  // the rows' lengths are not known here yet: a grid for ~1024 entries per seed, the kernel strides over the rest
+  HIP_TRY(launch_mlt_scan(false, a, std::max<uint64_t>((uint64_t)n * 1024, 16384), max_grid, s));
+  std::vector<uint32_t> counts(n), seg, take, oo;
+  std::vector<uint64_t> h_off((size_t)n + 1), cuts, h_keys, h_vals;
+  HIP_TRY(hipMemcpyAsync(counts.data(), d_cnt, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(h_off.data(), d_off, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  n_entries = h_off[n];
+  for (uint32_t i = 0; i < n; i++) out->n_cand[i] = counts[i];
+
+  mlt_plan_chunks(counts.data(), 0, n, budget, &cuts);
+  std::string ts;
+  for (size_t ci = 0; ci + 1 < cuts.size(); ci++) {
+    const uint64_t a0 = cuts[ci], na = cuts[ci + 1] - a0;
+    seg.assign(na + 1, 0);
+    uint64_t T = 0;
+    for (uint64_t t = 0; t < na; t++) {
+      T += counts[a0 + t];
+      if (T >= (1ull << 31)) return fail(TFIDF_E_INVALID_ARG, "more than 2^31 candidates for one seed range");
+      seg[t + 1] = (uint32_t)T;
+    }
+    if (T == 0) continue;
+    n_fill++;
+    // candidates: keys [T] x 2 (sort in / out), values [T] x 2
+    HIP_TRY(X.ml_c.reserve((size_t)T * 32));
+    uint64_t *k_in = X.ml_c.as<uint64_t>(), *k_out = k_in + T, *v_in = k_out + T, *v_out = v_in + T;
+    HIP_TRY(hipMemsetAsync(d_cur, 0, 4, s));
+    MltScan f = a;
+    f.s0 = (uint32_t)a0;
+    f.s1 = (uint32_t)(a0 + na);
+    f.keys = k_in;
+    f.vals = v_in;
+    f.cap = (uint32_t)T;
+    HIP_TRY(launch_mlt_scan(true, f, h_off[a0 + na] - h_off[a0], max_grid, s));
+    const int end_bit = mlt_key_bits((uint32_t)na);
+    size_t tmp_bytes = 0;
+    HIP_TRY(mlt_sort(nullptr, &tmp_bytes, k_in, k_out, v_in, v_out, (uint32_t)T, end_bit, s));
+    HIP_TRY(X.ml_tmp.reserve(tmp_bytes));
+    tmp_bytes = X.ml_tmp.bytes;
+    HIP_TRY(mlt_sort(X.ml_tmp.p, &tmp_bytes, k_in, k_out, v_in, v_out, (uint32_t)T, end_bit, s));
+    // what the host orders: the selection, packed into the sort's input buffers
+    take.resize(na);
+    HIP_TRY(hipMemcpyAsync(d_seg, seg.data(), (na + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_mlt_select(k_out, d_seg, (uint32_t)na, R.max_terms, d_take, s));
+    HIP_TRY(hipMemcpyAsync(take.data(), d_take, na * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    oo.assign(na + 1, 0);
+    uint64_t n_take = 0;
+    for (uint64_t t = 0; t < na; t++) {
+      if (take[t] > seg[t + 1] - seg[t]) return fail(TFIDF_E_STATE, "more-like-this selection past its segment");
+      oo[t] = (uint32_t)n_take;
+      n_take += take[t];
+    }
+    oo[na] = (uint32_t)n_take;
+    HIP_TRY(hipMemcpyAsync(d_oo, oo.data(), (na + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_mlt_gather(k_out, v_out, d_seg, d_oo, (uint32_t)na, k_in, v_in, s));
+    h_keys.resize(n_take);
+    h_vals.resize(n_take);
+    HIP_TRY(hipMemcpyAsync(h_keys.data(), k_in, n_take * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h_vals.data(), v_in, n_take * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint64_t t = 0; t < na; t++) {
+      std::vector<MltTerm> &L = out->terms[a0 + t];
+      L.reserve(oo[t + 1] - oo[t]);
+      for (uint32_t i = oo[t]; i < oo[t + 1]; i++) {
+        const uint32_t slot = mlt_val_slot(h_vals[i]), tf = mlt_val_tf(h_vals[i]);
+        if (mlt_key_seed(h_keys[i]) != t || slot >= S.C)
+          return fail(TFIDF_E_STATE, "more-like-this candidate %u of seed %llu is out of place", i,
+                      (unsigned long long)(a0 + t));
+        const uint32_t df = S.h_df[slot];
+        const float score = mlt_score(tf, S.h_mlt_idf[std::min<uint64_t>(df, S.n_docs)]);
+        if (mlt_float_bits(score) != mlt_key_score_bits(h_keys[i]))
+          return fail(TFIDF_E_STATE, "more-like-this score of slot %u differs between device and host", slot);
+        if (int rc = slot_term(S, slot, &ts)) return rc;
+        L.push_back(MltTerm{ts, slot, tf, df, score});
+      }
+      std::sort(L.begin(), L.end(), [](const MltTerm &x, const MltTerm &y) {
+        const uint32_t bx = mlt_float_bits(x.score), by = mlt_float_bits(y.score);
+        if (bx != by) return bx > by;
+        return x.term < y.term;
+      });
+      if (L.size() > R.max_terms) L.resize(R.max_terms);
+    }
+  }
+  publish();
+  return TFIDF_OK;
+}
+
+// Top kk of each prepared query on the caller's search context, in chunks
+// whose candidate buffers stay near 1 GiB: docs / scores [n * kk], counts [n].
+static int score_prepared(tfidf_index *ix, Snapshot &S, StatsView &V, SearchCtx &X, hipStream_t s,
+                          const std::vector<PreparedQuery> &pqs, uint32_t kk, uint32_t *docs, float *scores,
+                          uint32_t *counts, bool *any_out) {
+  const uint32_t n = (uint32_t)pqs.size();
+  *any_out = false;
+  memset(counts, 0, (size_t)n * 4);
+  if (n == 0 || S.n_docs == 0) return TFIDF_OK;
+  const uint64_t per_q = (uint64_t)std::max(1u, S.n_blocks) * kk * 8;
+  const uint32_t chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, (1ull << 30) / per_q));
+  HIP_TRY(X.q_res.resize((size_t)2 * n * kk + n));
+  std::vector<uint8_t> ran((n + chunk - 1) / chunk, 0);
+  for (uint32_t c0 = 0, ci = 0; c0 < n; c0 += chunk, ci++) {
+    const uint32_t nc = std::min(chunk, n - c0);
+    QueryBatch qb;
+    for (uint32_t i = 0; i < nc; i++) qb.add(pqs[c0 + i]);
+    if (qb.slot.empty()) continue;
+    X.q_rec_start = true;
+    if (int rc = run_scoring(ix, S, V, X, s, qb, nc, kk)) return rc;
+    uint32_t *hres = X.q_res.data() + (size_t)2 * c0 * kk + c0;
+    HIP_TRY(hipMemcpyAsync(hres, X.res_doc, ((size_t)2 * nc * kk + nc) * 4, hipMemcpyDeviceToHost, s));
+    ran[ci] = 1;
+    *any_out = true;
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  X.q_in_pending = false;
+  for (uint32_t c0 = 0, ci = 0; c0 < n; c0 += chunk, ci++) {
+    if (!ran[ci]) continue;
+    const uint32_t nc = std::min(chunk, n - c0);
+    const uint32_t *hres = X.q_res.data() + (size_t)2 * c0 * kk + c0;
+    memcpy(docs + (size_t)c0 * kk, hres, (size_t)nc * kk * 4);
+    memcpy(scores + (size_t)c0 * kk, hres + (size_t)nc * kk, (size_t)nc * kk * 4);
+    memcpy(counts + c0, hres + (size_t)2 * nc * kk, (size_t)nc * 4);
+  }
+  return TFIDF_OK;
+}
+
+// one SHOULD clause of boost 1 for dictionary slot `slot` (prepare_query's weights)
+static void add_should(const Snapshot &S, const StatsView &V, uint32_t slot, PreparedQuery *pq) {
+  const uint64_t df = V.global ? V.gdf[slot] : S.h_df[slot];
+  volatile float w = 1.0f * bm25_idf(df, V.doc_count);
+  pq->slot.push_back(S.col_of(slot));
+  pq->ldf.push_back(S.h_df[slot]);
+  const float wv = w;
+  pq->w.push_back(wv);
+  pq->role.push_back(kRoleShould << 24);
+}
+
+static int mlt_terms_call(tfidf_index *ix, Snapshot &S, const uint32_t *seeds, uint32_t n, const MltRules &R,
+                          MltLists *out) {
+  if (int rc = mlt_check_seeds(S, seeds, n)) return rc;
+  CtxLease lease(ix);
+  if (lease.rc) return lease.rc;
+  SearchCtx &X = *lease.c;
+  const hipStream_t s = lease.stream();
+  DeviceGuard g(ix->cfg.device);
+  if (X.q_timing) HIP_TRY(hipEventRecord(X.ev[QEV_P0], s));
+  if (int rc = mlt_terms_on(ix, S, X, s, seeds, n, R, out)) return rc;
+  if (X.q_timing) HIP_TRY(hipEventRecord(X.ev[QEV_P1], s));
+  HIP_TRY(hipStreamSynchronize(s));
+  set_last_ms(ix, 0.0f, qev_ms(X, QEV_P0, QEV_P1));
+  return TFIDF_OK;
+}
+
+int tfidf::index_mlt_terms(tfidf_index *ix, const uint32_t *seeds, uint32_t n, const MltRules &rules, MltLists *out) {
+  if (!ix || !out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "more-like-this before commit");
+  return mlt_terms_call(ix, *snap, seeds, n, rules, out);
+}
+
+int tfidf::index_search_term_lists(tfidf_index *ix, const std::vector<std::vector<std::string>> &lists, uint32_t k,
+                                   uint32_t *doc_ids, float *scores, uint32_t *counts) {
+  if (!ix || (lists.size() && (!doc_ids || !scores || !counts))) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (k == 0 || k > 1024) return fail(TFIDF_E_INVALID_ARG, "term-list search needs 1 <= k <= 1024");
+  std::shared_ptr<StatsView> view;
+  const std::shared_ptr<Snapshot> snap = current(ix, &view);
+  if (!snap) return fail(TFIDF_E_STATE, "search before commit");
+  Snapshot &S = *snap;
+  StatsView &V = *view;
+  CtxLease lease(ix);
+  if (lease.rc) return lease.rc;
+  DeviceGuard g(ix->cfg.device);
+  if (int e = V.wait_gdf()) return e;
+  std::vector<PreparedQuery> pqs(lists.size());
+  if (V.doc_count)
+    for (size_t i = 0; i < lists.size(); i++)
+      for (const std::string &t : lists[i]) {
+        const uint32_t slot = lookup_term(S, t);
+        if (slot != kInvalidSlot) add_should(S, V, slot, &pqs[i]);   // absent: no scorer
+      }
+  bool any = false;
+  if (int rc = score_prepared(ix, S, V, *lease.c, lease.stream(), pqs, k, doc_ids, scores, counts, &any)) return rc;
+  set_last_ms(ix, any ? qev_ms(*lease.c, QEV_0, QEV_1) : 0.0f, any ? qev_ms(*lease.c, QEV_0, QEV_2) : 0.0f);
+  return TFIDF_OK;
+}
+
+static int mlt_terms_batch_on(tfidf_index *ix, Snapshot &S, const uint32_t *seeds, uint32_t n, const MltRules &R,
+                              uint64_t *term_offsets, uint64_t *n_candidates,
+                              uint64_t *blob_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *tf, uint32_t *df,
+                              float *score, uint64_t term_cap, uint64_t *n_terms, uint64_t *n_term_bytes) {
+  if (!term_offsets || (n && !n_candidates) || !n_terms || !n_term_bytes)
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  MltLists ml;
+  if (int rc = mlt_terms_call(ix, S, seeds, n, R, &ml)) return rc;
+  uint64_t nt = 0, nb = 0;
+  term_offsets[0] = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    n_candidates[i] = ml.n_cand[i];
+    nt += ml.terms[i].size();
+    for (const MltTerm &t : ml.terms[i]) nb += t.term.size();
+    term_offsets[i + 1] = nt;
+  }
+  *n_terms = nt;
+  *n_term_bytes = nb;
+  if (nt > term_cap || nb > terms_cap || (nt && (!blob_offsets || !tf || !df || !score)) || (nb && !terms))
+    return fail(TFIDF_E_BUFFER, "need %llu term slots and %llu term bytes", (unsigned long long)nt,
+                (unsigned long long)nb);
+  uint64_t at = 0, b = 0;
+  if (blob_offsets) blob_offsets[0] = 0;
+  for (uint32_t i = 0; i < n; i++)
+    for (const MltTerm &t : ml.terms[i]) {
+      memcpy(terms + b, t.term.data(), t.term.size());
+      b += t.term.size();
+      tf[at] = t.tf;
+      df[at] = t.df;
+      score[at] = t.score;
+      blob_offsets[++at] = b;
+    }
+  return TFIDF_OK;
+}
+
+static int mlt_search_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint32_t *seeds, uint32_t n,
+                         const MltRules &R, uint32_t k, uint32_t flags, uint32_t *doc_ids, float *scores,
+                         uint32_t *counts) {
+  const bool excl = (flags & TFIDF_MLT_EXCLUDE_SEED) != 0;
+  if (flags & ~TFIDF_MLT_EXCLUDE_SEED) return fail(TFIDF_E_INVALID_ARG, "unknown flags 0x%x", flags);
+  if (k == 0 || k > (excl ? 1023u : 1024u))
+    return fail(TFIDF_E_INVALID_ARG, "more-like-this needs 1 <= k <= %u", excl ? 1023u : 1024u);
+  if (n && (!doc_ids || !scores || !counts)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (int rc = mlt_check_seeds(S, seeds, n)) return rc;
+  CtxLease lease(ix);
+  if (lease.rc) return lease.rc;
+  SearchCtx &X = *lease.c;
+  const hipStream_t s = lease.stream();
+  DeviceGuard g(ix->cfg.device);
+  if (X.q_timing) HIP_TRY(hipEventRecord(X.ev[QEV_P0], s));
+  MltLists ml;
+  if (int rc = mlt_terms_on(ix, S, X, s, seeds, n, R, &ml)) return rc;
+  if (int e = V.wait_gdf()) return e;
+  std::vector<PreparedQuery> pqs(n);
+  if (V.doc_count)
+    for (uint32_t i = 0; i < n; i++)
+      for (const MltTerm &t : ml.terms[i]) add_should(S, V, t.slot, &pqs[i]);
+  const uint32_t kk = excl ? k + 1 : k;
+  std::vector<uint32_t> t_docs, t_cnt;
+  std::vector<float> t_scores;
+  uint32_t *pd = doc_ids, *pc = counts;
+  float *ps = scores;
+  if (excl) {
+    t_docs.resize((size_t)n * kk);
+    t_scores.resize((size_t)n * kk);
+    t_cnt.resize(n);
+    pd = t_docs.data();
+    ps = t_scores.data();
+    pc = t_cnt.data();
+  }
+  bool any = false;
+  if (int rc = score_prepared(ix, S, V, X, s, pqs, kk, pd, ps, pc, &any)) return rc;
+  if (X.q_timing) HIP_TRY(hipEventRecord(X.ev[QEV_P1], s));
+  HIP_TRY(hipStreamSynchronize(s));
+  set_last_ms(ix, any ? qev_ms(X, QEV_0, QEV_2) : 0.0f, qev_ms(X, QEV_P0, QEV_P1));
+  if (excl)
+    for (uint32_t i = 0; i < n; i++) {   // the top k of the others: the seed dropped from the top k + 1
+      uint32_t m = 0;
+      for (uint32_t j = 0; j < pc[i] && m < k; j++) {
+        if (pd[(size_t)i * kk + j] == seeds[i]) continue;
+        doc_ids[(size_t)i * k + m] = pd[(size_t)i * kk + j];
+        scores[(size_t)i * k + m] = ps[(size_t)i * kk + j];
+        m++;
+      }
+      counts[i] = m;
+    }
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_mlt_params_init(tfidf_mlt_params *params) {
+  if (!params) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  *params = tfidf_mlt_params{2, 5, 0, 25};   // MoreLikeThis.DEFAULT_MIN_TERM_FREQ / _MIN_DOC_FREQ / _MAX_DOC_FREQ / _MAX_QUERY_TERMS
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_mlt_terms_batch(tfidf_index *ix, const uint32_t *seeds, uint32_t n, const tfidf_mlt_params *params,
+                                     uint64_t *term_offsets, uint64_t *n_candidates, uint64_t *blob_offsets,
+                                     uint8_t *terms, uint64_t terms_cap, uint32_t *tf, uint32_t *df, float *score,
+                                     uint64_t term_cap, uint64_t *n_terms, uint64_t *n_term_bytes) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  MltRules R;
+  if (int rc = mlt_rules(params, &R)) return rc;
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "more-like-this before commit");
+  return mlt_terms_batch_on(ix, *snap, seeds, n, R, term_offsets, n_candidates, blob_offsets, terms, terms_cap, tf,
+                            df, score, term_cap, n_terms, n_term_bytes);
+}
+
+extern "C" int tfidf_reader_mlt_terms_batch(tfidf_reader *rd, const uint32_t *seeds, uint32_t n,
+                                            const tfidf_mlt_params *params, uint64_t *term_offsets,
+                                            uint64_t *n_candidates, uint64_t *blob_offsets, uint8_t *terms,
+                                            uint64_t terms_cap, uint32_t *tf, uint32_t *df, float *score,
+                                            uint64_t term_cap, uint64_t *n_terms, uint64_t *n_term_bytes) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  MltRules R;
+  if (int rc = mlt_rules(params, &R)) return rc;
+  return mlt_terms_batch_on(rd->ix, *rd->S, seeds, n, R, term_offsets, n_candidates, blob_offsets, terms, terms_cap,
+                            tf, df, score, term_cap, n_terms, n_term_bytes);
+}
+
+extern "C" int tfidf_more_like_this_batch(tfidf_index *ix, const uint32_t *seeds, uint32_t n,
+                                          const tfidf_mlt_params *params, uint32_t k, uint32_t flags, uint32_t *doc_ids,
+                                          float *scores, uint32_t *counts) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  MltRules R;
+  if (int rc = mlt_rules(params, &R)) return rc;
+  std::shared_ptr<StatsView> view;
+  const std::shared_ptr<Snapshot> snap = current(ix, &view);
+  if (!snap) return fail(TFIDF_E_STATE, "more-like-this before commit");
+  return mlt_search_on(ix, *snap, *view, seeds, n, R, k, flags, doc_ids, scores, counts);
+}
+
+extern "C" int tfidf_reader_more_like_this_batch(tfidf_reader *rd, const uint32_t *seeds, uint32_t n,
+                                                 const tfidf_mlt_params *params, uint32_t k, uint32_t flags,
+                                                 uint32_t *doc_ids, float *scores, uint32_t *counts) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  MltRules R;
+  if (int rc = mlt_rules(params, &R)) return rc;
+  return mlt_search_on(rd->ix, *rd->S, *rd->V, seeds, n, R, k, flags, doc_ids, scores, counts);
+}
+
+// the single forms: the batch of one seed
+extern "C" int tfidf_more_like_this(tfidf_index *ix, uint32_t seed, const tfidf_mlt_params *params, uint32_t k,
+                                    uint32_t flags, uint32_t *doc_ids, float *scores, uint32_t *count) {
+  if (!count) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  return tfidf_more_like_this_batch(ix, &seed, 1, params, k, flags, doc_ids, scores, count);
+}
+
+extern "C" int tfidf_reader_more_like_this(tfidf_reader *rd, uint32_t seed, const tfidf_mlt_params *params, uint32_t k,
+                                           uint32_t flags, uint32_t *doc_ids, float *scores, uint32_t *count) {
+  if (!count) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  return tfidf_reader_more_like_this_batch(rd, &seed, 1, params, k, flags, doc_ids, scores, count);
+}
+
+extern "C" int tfidf_last_mlt_stats(const tfidf_index *ix, uint64_t *row_entries_scanned, uint64_t *cand_chunks) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->ms_mu);
+  if (row_entries_scanned) *row_entries_scanned = ix->last_mlt_entries;
+  if (cand_chunks) *cand_chunks = ix->last_mlt_chunks;
   return TFIDF_OK;
 }
 

@@ -38,6 +38,7 @@
 
 #include "../../include/tfidf.h"
 #include "analysis.h"
+#include "mlt_plan.h"
 #include "tfidf_common.h"
 #include "tfidf_internal.h"
 
@@ -2339,6 +2340,102 @@ extern "C" int tfidf_node_search_phrase_batch(tfidf_node *n, const uint8_t *p_ut
       scores[o] = sh[best].scores[j];
       freqs[o] = sh[best].freqs[j];
     }
+  }
+  return TFIDF_OK;
+}
+
+// ---------------------------------------------------------------------------
+// more-like-this over the node: the owning shard selects a seed's terms, every
+// shard with documents scores the term strings on its own dictionary and
+// statistics, the host merges per seed by (score descending, global id ascending)
+
+extern "C" int tfidf_node_more_like_this_batch(tfidf_node *n, const uint64_t *seeds, uint32_t n_seeds,
+                                               const tfidf_mlt_params *params, uint32_t k, uint32_t flags,
+                                               uint64_t *doc_ids, float *scores, uint32_t *counts) {
+  if (!n || (n_seeds && (!seeds || !doc_ids || !scores || !counts))) return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  tfidf_mlt_params p;
+  tfidf_mlt_params_init(&p);
+  if (params) p = *params;
+  if (p.max_terms < 1 || p.max_terms > kMltMaxTerms)
+    return errf(TFIDF_E_INVALID_ARG, "max_terms %u outside 1..%u", p.max_terms, kMltMaxTerms);
+  const MltRules R{p.min_tf ? p.min_tf : 1u, p.min_df, p.max_df, p.max_terms};
+  const bool excl = (flags & TFIDF_MLT_EXCLUDE_SEED) != 0;
+  if (flags & ~TFIDF_MLT_EXCLUDE_SEED) return errf(TFIDF_E_INVALID_ARG, "unknown flags 0x%x", flags);
+  if (k == 0 || k > (excl ? 1023u : 1024u))
+    return errf(TFIDF_E_INVALID_ARG, "more-like-this needs 1 <= k <= %u", excl ? 1023u : 1024u);
+  if (n_seeds > kMltMaxSeeds) return errf(TFIDF_E_INVALID_ARG, "more than %u seeds in one call", kMltMaxSeeds);
+  std::lock_guard<std::mutex> lk(n->mu);
+  if (!n->committed) return errf(TFIDF_E_STATE, "more-like-this before tfidf_node_commit");
+  for (uint32_t i = 0; i < n_seeds; i++)
+    if (seeds[i] >= n->num_docs)
+      return errf(TFIDF_E_INVALID_ARG, "seed %u (doc %llu) out of range: %llu documents", i,
+                  (unsigned long long)seeds[i], (unsigned long long)n->num_docs);
+  const size_t G = n->shards.size();
+  // seeds to their shards (tfidf_node_doc_key's rule)
+  struct Owned {
+    std::vector<uint32_t> local, at;
+    MltLists ml;
+  };
+  std::vector<Owned> own(G);
+  for (uint32_t i = 0; i < n_seeds; i++) {
+    size_t g = G - 1;
+    while (n->doc_base[g] > seeds[i]) g--;
+    own[g].local.push_back((uint32_t)(seeds[i] - n->doc_base[g]));
+    own[g].at.push_back(i);
+  }
+  if (int rc = n->pool->run([&](uint32_t g) {
+        if (own[g].local.empty()) return (int)TFIDF_OK;
+        return index_mlt_terms(n->shards[g], own[g].local.data(), (uint32_t)own[g].local.size(), R, &own[g].ml);
+      }))
+    return rc;
+  std::vector<std::vector<std::string>> lists(n_seeds);
+  for (size_t g = 0; g < G; g++)
+    for (size_t j = 0; j < own[g].at.size(); j++)
+      for (const MltTerm &t : own[g].ml.terms[j]) lists[own[g].at[j]].push_back(t.term);
+  const uint32_t kk = excl ? k + 1 : k;
+  struct ShardTop {
+    std::vector<uint32_t> docs, cnt;
+    std::vector<float> scores;
+    bool ran = false;
+  };
+  std::vector<ShardTop> sh(G);
+  if (int rc = n->pool->run([&](uint32_t g) {
+        tfidf_index *ix = n->shards[g];
+        if (n_seeds == 0 || !index_committed(ix) || index_num_docs(ix) == 0) return (int)TFIDF_OK;
+        ShardTop &b = sh[g];
+        b.docs.resize((size_t)n_seeds * kk);
+        b.scores.resize((size_t)n_seeds * kk);
+        b.cnt.assign(n_seeds, 0);
+        const int rc = index_search_term_lists(ix, lists, kk, b.docs.data(), b.scores.data(), b.cnt.data());
+        b.ran = rc == TFIDF_OK;
+        return rc;
+      }))
+    return rc;
+  struct Hit {
+    float score;
+    uint64_t doc;
+  };
+  std::vector<Hit> all;
+  for (uint32_t i = 0; i < n_seeds; i++) {
+    all.clear();
+    for (size_t g = 0; g < G; g++) {
+      if (!sh[g].ran) continue;
+      for (uint32_t j = 0; j < sh[g].cnt[i]; j++) {
+        const uint64_t d = n->doc_base[g] + sh[g].docs[(size_t)i * kk + j];
+        if (excl && d == seeds[i]) continue;
+        all.push_back(Hit{sh[g].scores[(size_t)i * kk + j], d});
+      }
+    }
+    std::sort(all.begin(), all.end(), [](const Hit &x, const Hit &y) {
+      if (x.score != y.score) return x.score > y.score;
+      return x.doc < y.doc;
+    });
+    const uint32_t m = (uint32_t)std::min<size_t>(k, all.size());
+    for (uint32_t j = 0; j < m; j++) {
+      doc_ids[(size_t)i * k + j] = all[j].doc;
+      scores[(size_t)i * k + j] = all[j].score;
+    }
+    counts[i] = m;
   }
   return TFIDF_OK;
 }

@@ -495,6 +495,41 @@ hipError_t ph_sort(void *tmp, size_t tmp_bytes, const uint64_t *key_in, uint64_t
 hipError_t launch_ph_emit(const uint32_t *rows, const uint64_t *key, const uint32_t *freq, uint64_t n, uint32_t *o_doc,
                           float *o_score, uint32_t *o_freq, hipStream_t s);
 
+// --- more-like-this (kernels_mlt.hip; rules in mlt_plan.h) ---
+// One pass over the forward rows of seeds [s0, s1) of a staged batch: the
+// flattened entries row_off[s0] .. row_off[s1] (row_off: exclusive scan of the
+// rows' lengths over all n_seeds seeds, n_seeds + 1 words).
+struct MltScan {
+  const uint32_t *csr;        // packed CSR entries (csr_pack) and the words the buffer holds
+  uint64_t csr_words;
+  const uint32_t *rsplit;     // [n_docs][R] row range segments
+  uint32_t R, range_shift, C;
+  const uint64_t *csr_esc;    // sorted tf escapes
+  uint64_t n_esc;
+  const uint32_t *df;         // per slot (Snapshot::df_dev)
+  const float *idf;           // mlt_idf_table: [n_docs + 1]
+  uint64_t n_docs;
+  const uint32_t *seed_doc;   // [n_seeds] committed ids
+  const uint64_t *row_base;   // [n_seeds] first CSR entry of each seed's row
+  const uint64_t *row_off;    // [n_seeds + 1]
+  uint32_t s0, s1;
+  uint32_t min_tf, min_df, max_df;
+  uint32_t *counts;           // count pass: survivors per seed (zeroed before)
+  uint64_t *keys, *vals;      // fill pass: mlt_key (seed relative to s0) / mlt_val per survivor, the
+  uint32_t *cursor;           // append cursor (zeroed before) and the capacity the counts gave
+  uint32_t cap;
+};
+hipError_t launch_mlt_extents(const uint64_t *offsets, const uint32_t *doc_nuniq, const uint32_t *seed_doc,
+                              const uint32_t *seed_staged, uint32_t n, uint64_t *row_base, uint64_t *row_len,
+                              hipStream_t s);
+hipError_t launch_mlt_scan(bool fill, const MltScan &a, uint64_t n_entries, int max_grid, hipStream_t s);
+hipError_t mlt_sort(void *tmp, size_t *tmp_bytes, const uint64_t *keys_in, uint64_t *keys_out, const uint64_t *vals_in,
+                    uint64_t *vals_out, uint32_t n, int end_bit, hipStream_t s);
+hipError_t launch_mlt_select(const uint64_t *keys, const uint32_t *seg, uint32_t n_seeds, uint32_t max_terms,
+                             uint32_t *take, hipStream_t s);
+hipError_t launch_mlt_gather(const uint64_t *keys, const uint64_t *vals, const uint32_t *seg, const uint32_t *out_off,
+                             uint32_t n_seeds, uint64_t *o_keys, uint64_t *o_vals, hipStream_t s);
+
 // --- index internals the node-level orchestration reads (tfidf_capi.hip) ---
 }  // namespace tfidf
 struct tfidf_index;
@@ -520,6 +555,23 @@ struct FuzzyLists {
 };
 int index_fuzzy_terms(tfidf_index *ix, const uint8_t *t_utf8, const uint64_t *t_offsets, uint32_t n_terms,
                       uint32_t max_edits, uint32_t prefix_len, uint32_t max_out, FuzzyLists *out);
+// more-like-this on the snapshot published now: per seed (a committed doc id)
+// its interesting terms in selection order and the candidates before truncation
+struct MltRules;
+struct MltTerm {
+  std::string term;
+  uint32_t slot, tf, df;
+  float score;
+};
+struct MltLists {
+  std::vector<std::vector<MltTerm>> terms;
+  std::vector<uint64_t> n_cand;
+};
+int index_mlt_terms(tfidf_index *ix, const uint32_t *seeds, uint32_t n, const MltRules &rules, MltLists *out);
+// top k of one disjunction per term list (SHOULD clauses in list order, boost
+// 1; a term this shard lacks has no scorer) in the layout of tfidf_search_batch
+int index_search_term_lists(tfidf_index *ix, const std::vector<std::vector<std::string>> &lists, uint32_t k,
+                            uint32_t *doc_ids, float *scores, uint32_t *counts);
 // device-key searches on a reader's pinned snapshot (tfidf_reader_open)
 int reader_batch_keys_device(tfidf_reader *rd, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
                              uint32_t k, uint64_t doc_base, void *d_keys);

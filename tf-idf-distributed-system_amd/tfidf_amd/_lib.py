@@ -88,6 +88,18 @@ def _fuzzy_batch_sig(df):
 _FUZZY_SINGLE_SIG = (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, U64P, U64P, VP,
                                C.c_uint64, U32P, U8P, C.c_uint64, U64P, U64P, F32P])
 
+class MltParams(C.Structure):
+    _fields_ = [("min_tf", C.c_uint32), ("min_df", C.c_uint32), ("max_df", C.c_uint32), ("max_terms", C.c_uint32)]
+
+
+MLT_EXCLUDE_SEED = 1
+MLTP = C.POINTER(MltParams)
+# tfidf_[reader_]mlt_terms_batch / tfidf_[reader_]more_like_this_batch / the single forms
+_MLT_TERMS_SIG = (C.c_int, [VP, U32P, C.c_uint32, MLTP, U64P, U64P, U64P, VP, C.c_uint64, U32P, U32P, F32P, C.c_uint64,
+                            U64P, U64P])
+_MLT_BATCH_SIG = (C.c_int, [VP, U32P, C.c_uint32, MLTP, C.c_uint32, C.c_uint32, U32P, F32P, U32P])
+_MLT_SINGLE_SIG = (C.c_int, [VP, C.c_uint32, MLTP, C.c_uint32, C.c_uint32, U32P, F32P, U32P])
+
 SIGNATURES = {
     "tfidf_version": (C.c_char_p, []),
     "tfidf_last_error": (C.c_char_p, []),
@@ -137,6 +149,14 @@ SIGNATURES = {
     "tfidf_node_search_phrase_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U64P, F32P, U32P, C.c_uint64,
                                                  U64P, U64P]),
     "tfidf_last_phrase_stats": (C.c_int, [VP, U64P, U64P]),
+    "tfidf_mlt_params_init": (C.c_int, [MLTP]),
+    "tfidf_mlt_terms_batch": _MLT_TERMS_SIG,
+    "tfidf_reader_mlt_terms_batch": _MLT_TERMS_SIG,
+    "tfidf_more_like_this_batch": _MLT_BATCH_SIG,
+    "tfidf_reader_more_like_this_batch": _MLT_BATCH_SIG,
+    "tfidf_more_like_this": _MLT_SINGLE_SIG,
+    "tfidf_reader_more_like_this": _MLT_SINGLE_SIG,
+    "tfidf_last_mlt_stats": (C.c_int, [VP, U64P, U64P]),
     "tfidf_query_positive_terms": (C.c_int, [C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, U64P, U64P]),
     "tfidf_set_hash_attempt": (C.c_int, [VP, C.c_uint32]),
     "tfidf_get_commit_timing": (C.c_int, [VP, C.POINTER(CommitTiming)]),
@@ -224,6 +244,7 @@ SIGNATURES = {
     "tfidf_node_snippets_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U64P, U64P, C.c_uint32, VP, C.c_uint64,
                                             U64P, U64P, U64P, U32P, U32P, C.c_uint64, U64P, U64P, U64P, F32P]),
     "tfidf_node_fuzzy_terms_batch": _fuzzy_batch_sig(U64P),
+    "tfidf_node_more_like_this_batch": (C.c_int, [VP, U64P, C.c_uint32, MLTP, C.c_uint32, C.c_uint32, U64P, F32P, U32P]),
     "tfidf_node_last_failed": (C.c_int, [VP, U64P]),
     "tfidf_node_stats_get": (C.c_int, [VP, VP]),
     "tfidf_device_free": (C.c_int, [C.c_int, VP]),

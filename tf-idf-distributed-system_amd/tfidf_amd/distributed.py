@@ -493,6 +493,24 @@ class Node:
         return E._phrase_lists(*E._phrase_batch_arrays(L.load().tfidf_node_search_phrase_batch, self._h, phrases,
                                                        dtype=np.uint64))
 
+    def more_like_this_batch(self, docs, k=10, exclude_seed=True, **params):
+        """ShardIndex.more_like_this_batch over the node: ``docs`` are global
+        ids; the owning shard picks a seed's interesting terms, every shard
+        scores them on its own dictionary and statistics, and the lists are
+        merged per seed by (score desc, global id asc)
+        (tfidf_node_more_like_this_batch).  -> [[(global doc, score)]]."""
+        from . import engine as E
+        seeds = np.ascontiguousarray(docs, np.uint64)
+        n = len(seeds)
+        out_d = np.zeros((max(n, 1), k), np.uint64)
+        out_s = np.zeros((max(n, 1), k), np.float32)
+        cnt = np.zeros(max(n, 1), np.uint32)
+        L.check(L.load().tfidf_node_more_like_this_batch(
+            self._h, L.ptr(seeds, C.c_uint64), n, C.byref(E.mlt_params(**params)), k,
+            L.MLT_EXCLUDE_SEED if exclude_seed else 0, L.ptr(out_d, C.c_uint64), L.ptr(out_s, C.c_float),
+            L.ptr(cnt, C.c_uint32)))
+        return E._topk_lists(out_d[:n], out_s[:n], cnt[:n])
+
 
 class NodeStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("n_shards", "num_docs", "doc_count", "sum_ttf", "num_terms", "transport")]

@@ -335,6 +335,82 @@ def _phrase_single(fn, handle, phrase):
     return list(zip(docs[:m].tolist(), scores[:m].tolist(), freqs[:m].tolist()))
 
 
+def mlt_params(min_tf=None, min_df=None, max_df=None, max_terms=None):
+    """tfidf_mlt_params with Lucene's MoreLikeThis defaults (min_tf 2, min_df 5,
+    max_df 0 = no upper bound, max_terms 25) where an argument is None."""
+    p = L.MltParams()
+    L.check(L.load().tfidf_mlt_params_init(C.byref(p)))
+    for name, v in (("min_tf", min_tf), ("min_df", min_df), ("max_df", max_df), ("max_terms", max_terms)):
+        if v is not None:
+            setattr(p, name, v)
+    return p
+
+
+def _mlt_terms_arrays(fn, handle, docs, params, term_cap=None, bytes_cap=None):
+    """tfidf_[reader_]mlt_terms_batch: one call for the sizes (or with the given
+    caps), one more for the payload when that was too small.  -> (term offsets
+    uint64[n + 1], n_candidates uint64[n], blob offsets uint64[m + 1], term blob
+    bytes, tf uint32[m], df uint32[m], score float32[m])."""
+    seeds = np.ascontiguousarray(docs, np.uint32)
+    n = len(seeds)
+    t_offs = np.zeros(n + 1, np.uint64)
+    cand = np.zeros(max(n, 1), np.uint64)
+    nt, nb = C.c_uint64(), C.c_uint64()
+    t_cap = 0 if term_cap is None else term_cap
+    b_cap = 0 if bytes_cap is None else bytes_cap
+    for _ in range(2):
+        b_offs = np.zeros(t_cap + 1, np.uint64)
+        blob = np.empty(max(b_cap, 1), np.uint8)
+        tf = np.zeros(max(t_cap, 1), np.uint32)
+        df = np.zeros(max(t_cap, 1), np.uint32)
+        score = np.zeros(max(t_cap, 1), np.float32)
+        rc = fn(handle, L.ptr(seeds, C.c_uint32), n, C.byref(params), L.ptr(t_offs, C.c_uint64),
+                L.ptr(cand, C.c_uint64), L.ptr(b_offs, C.c_uint64) if t_cap else None,
+                blob.ctypes.data_as(C.c_void_p) if b_cap else None, b_cap, L.ptr(tf, C.c_uint32) if t_cap else None,
+                L.ptr(df, C.c_uint32) if t_cap else None, L.ptr(score, C.c_float) if t_cap else None, t_cap,
+                C.byref(nt), C.byref(nb))
+        if rc != L.E_BUFFER or term_cap is not None or bytes_cap is not None:
+            break
+        t_cap, b_cap = nt.value, nb.value
+    L.check(rc)
+    m = nt.value
+    return t_offs, cand[:n], b_offs[:m + 1], blob[:nb.value].tobytes(), tf[:m], df[:m], score[:m]
+
+
+def _mlt_terms_lists(arrays):
+    """-> per seed ([(term bytes, tf, df, score)], n_candidates)."""
+    t_offs, cand, b_offs, blob, tf, df, score = arrays
+    o, b, f, d, s = t_offs.tolist(), b_offs.tolist(), tf.tolist(), df.tolist(), score.tolist()
+    terms = [(blob[b[j]:b[j + 1]], f[j], d[j], s[j]) for j in range(len(b) - 1)]
+    return [(terms[o[i]:o[i + 1]], int(cand[i])) for i in range(len(o) - 1)]
+
+
+def _mlt_batch_arrays(fn, handle, docs, k, exclude_seed, params):
+    """tfidf_[reader_]more_like_this_batch -> (docs uint32[n, k], scores float32[n, k], counts uint32[n])."""
+    seeds = np.ascontiguousarray(docs, np.uint32)
+    n = len(seeds)
+    out_d = np.zeros((max(n, 1), max(k, 1)), np.uint32)
+    out_s = np.zeros((max(n, 1), max(k, 1)), np.float32)
+    cnt = np.zeros(max(n, 1), np.uint32)
+    L.check(fn(handle, L.ptr(seeds, C.c_uint32), n, C.byref(params), k, L.MLT_EXCLUDE_SEED if exclude_seed else 0,
+               L.ptr(out_d, C.c_uint32), L.ptr(out_s, C.c_float), L.ptr(cnt, C.c_uint32)))
+    return out_d[:n], out_s[:n], cnt[:n]
+
+
+def _mlt_single(fn, handle, doc, k, exclude_seed, params):
+    """tfidf_[reader_]more_like_this -> [(doc, score)]."""
+    out_d = np.zeros(max(k, 1), np.uint32)
+    out_s = np.zeros(max(k, 1), np.float32)
+    cnt = C.c_uint32()
+    L.check(fn(handle, doc, C.byref(params), k, L.MLT_EXCLUDE_SEED if exclude_seed else 0, L.ptr(out_d, C.c_uint32),
+               L.ptr(out_s, C.c_float), C.byref(cnt)))
+    return list(zip(out_d[:cnt.value].tolist(), out_s[:cnt.value].tolist()))
+
+
+def _topk_lists(docs, scores, counts):
+    return [list(zip(docs[i, :c].tolist(), scores[i, :c].tolist())) for i, c in enumerate(counts.tolist())]
+
+
 class ShardIndex:
     def __init__(self, device=0, k1=1.2, b=0.75, vocab_capacity_log2=18, stats_mode=L.STATS_SHARD,
                  inversion=L.INVERSION_AUTO):
@@ -515,6 +591,50 @@ class ShardIndex:
         this index or one of its readers (tfidf_last_phrase_stats)."""
         a, b = C.c_uint64(), C.c_uint64()
         L.check(L.load().tfidf_last_phrase_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def more_like_this(self, doc, k=10, exclude_seed=True, **params):
+        """[(doc, score)]: the top ``k`` of the disjunction of document
+        ``doc``'s interesting terms (Lucene's MoreLikeThis on the index's own
+        row of the seed; tfidf_more_like_this), scored as ``search`` scores
+        it; without the seed itself unless ``exclude_seed`` is False.
+        ``params``: min_tf, min_df, max_df, max_terms (mlt_params)."""
+        return _mlt_single(L.load().tfidf_more_like_this, self._h, doc, k, exclude_seed, mlt_params(**params))
+
+    def more_like_this_batch_arrays(self, docs, k=10, exclude_seed=True, **params):
+        """(docs uint32[n, k], scores float32[n, k], counts uint32[n]) of tfidf_more_like_this_batch."""
+        return _mlt_batch_arrays(L.load().tfidf_more_like_this_batch, self._h, docs, k, exclude_seed,
+                                 mlt_params(**params))
+
+    def more_like_this_batch(self, docs, k=10, exclude_seed=True, **params):
+        """[more_like_this(d, ...) for d in docs] from one device pass over the seeds' rows and one scoring batch."""
+        return _topk_lists(*self.more_like_this_batch_arrays(docs, k, exclude_seed, **params))
+
+    def mlt_terms_batch_arrays(self, docs, term_cap=None, bytes_cap=None, **params):
+        """(term offsets uint64[n + 1], n_candidates uint64[n], blob offsets
+        uint64[m + 1], term blob, tf uint32[m], df uint32[m], score float32[m])
+        of tfidf_mlt_terms_batch; seed i's terms are [offsets[i], offsets[i + 1])."""
+        return _mlt_terms_arrays(L.load().tfidf_mlt_terms_batch, self._h, docs, mlt_params(**params), term_cap,
+                                 bytes_cap)
+
+    def mlt_terms_batch(self, docs, **params):
+        """Per seed ([(term bytes, tf, df, score)], n_candidates): its
+        interesting terms in selection order (score descending, then bytes)
+        and the candidates there were before the cut to max_terms."""
+        return _mlt_terms_lists(self.mlt_terms_batch_arrays(docs, **params))
+
+    def mlt_terms_arrays(self, doc, **params):
+        return self.mlt_terms_batch_arrays([doc], **params)
+
+    def mlt_terms(self, doc, **params):
+        """mlt_terms_batch([doc])[0]."""
+        return self.mlt_terms_batch([doc], **params)[0]
+
+    def last_mlt_stats(self):
+        """(forward-row entries scanned, candidate chunks) of the last
+        more-like-this call on this index or one of its readers (tfidf_last_mlt_stats)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        L.check(L.load().tfidf_last_mlt_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
     def set_hash_attempt(self, attempt):
@@ -892,6 +1012,35 @@ class Reader:
     def search_phrase_batch(self, phrases):
         """ShardIndex.search_phrase_batch on this reader's snapshot."""
         return _phrase_lists(*self.search_phrase_batch_arrays(phrases))
+
+    def more_like_this(self, doc, k=10, exclude_seed=True, **params):
+        """ShardIndex.more_like_this on this reader's snapshot."""
+        return _mlt_single(L.load().tfidf_reader_more_like_this, self._h, doc, k, exclude_seed, mlt_params(**params))
+
+    def more_like_this_batch_arrays(self, docs, k=10, exclude_seed=True, **params):
+        """ShardIndex.more_like_this_batch_arrays on this reader's snapshot."""
+        return _mlt_batch_arrays(L.load().tfidf_reader_more_like_this_batch, self._h, docs, k, exclude_seed,
+                                 mlt_params(**params))
+
+    def more_like_this_batch(self, docs, k=10, exclude_seed=True, **params):
+        """ShardIndex.more_like_this_batch on this reader's snapshot."""
+        return _topk_lists(*self.more_like_this_batch_arrays(docs, k, exclude_seed, **params))
+
+    def mlt_terms_batch_arrays(self, docs, term_cap=None, bytes_cap=None, **params):
+        """ShardIndex.mlt_terms_batch_arrays on this reader's snapshot."""
+        return _mlt_terms_arrays(L.load().tfidf_reader_mlt_terms_batch, self._h, docs, mlt_params(**params), term_cap,
+                                 bytes_cap)
+
+    def mlt_terms_batch(self, docs, **params):
+        """ShardIndex.mlt_terms_batch on this reader's snapshot."""
+        return _mlt_terms_lists(self.mlt_terms_batch_arrays(docs, **params))
+
+    def mlt_terms_arrays(self, doc, **params):
+        return self.mlt_terms_batch_arrays([doc], **params)
+
+    def mlt_terms(self, doc, **params):
+        """ShardIndex.mlt_terms on this reader's snapshot."""
+        return self.mlt_terms_batch([doc], **params)[0]
 
     def doc_keys(self):
         lib = L.load()

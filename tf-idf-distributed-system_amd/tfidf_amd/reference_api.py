@@ -161,6 +161,20 @@ class Worker:
                 out.append(info)
             return out
 
+    # No reference counterpart ("contents" has no term vectors, so Lucene's
+    # MoreLikeThis.like(docNum) would find no terms there): the ``k``
+    # documents most like the document whose key is ``name``, without that
+    # document, in the shape of search_index; [] for a name the index lacks.
+    # Key and hits are resolved on one reader.
+    def search_similar(self, name: str, k=10):
+        with self.index.reader() as rd:
+            blob, offs = rd.doc_keys()
+            raw, o, key = blob.tobytes(), offs.tolist(), name.encode()
+            doc = next((d for d in range(rd.num_docs) if raw[o[d]:o[d + 1]] == key), None)
+            if doc is None:
+                return []
+            return [document_score_info(rd.doc_key(d).decode(), s) for d, s in rd.more_like_this(doc, k)]
+
     # No reference counterpart ("contents" is stored with Store.NO,
     # Worker.java:216): the top-k hits with the passage that shows why each
     # matched, search and snippets on one reader.  DocumentScoreInfo JSON
