@@ -499,6 +499,76 @@ int tfidf_reader_fuzzy_terms(tfidf_reader *rd, const uint8_t *term, uint64_t len
  * chunks filled and sorted (1, 1 when everything fitted; 0, 0 when no input
  * term could have candidates). */
 int tfidf_last_fuzzy_chunks(const tfidf_index *ix, uint64_t *scan_chunks, uint64_t *cand_chunks);
+/* ---- wildcard and prefix search (Lucene's WildcardQuery / PrefixQuery; the
+ * reference has no counterpart: QueryParser.escape neutralises '*' and '?';
+ * DESIGN.md section 2, "Wildcard search") ----
+ * Pattern: a byte string, not tokenised and not parsed as a query, decoded as
+ *   strict UTF-8 into elements.  '*' matches any run of code points, the empty
+ *   one included; '?' matches exactly one code point (not a byte, not a UTF-16
+ *   unit); '\x' is the literal x and a trailing lone '\' a literal backslash;
+ *   everything else is a literal, lower-cased per code point as the fuzzy
+ *   lookup lower-cases its input.  Runs of '*' collapse to one.  An empty
+ *   pattern, one that is not strict UTF-8 and one of more than 255 elements
+ *   after collapsing match nothing, without failing the call.
+ * Match: the whole vocabulary term (the vocabulary of the fuzzy lookup: local
+ *   df >= 1, lower-cased UTF-8) matches the pattern, anchored at both ends.
+ *   "abc*" is the prefix query, a pattern without '*' or '?' the exact term,
+ *   "*" every term.  Leading wildcards are legal.
+ * tfidf_wildcard_terms_batch (type-ahead): pattern i's matching terms in (df
+ *   descending, term bytes ascending, unsigned) order, the first max_out
+ *   (1..1024); n_matched[i] counts them before truncation.  df is the shard's
+ *   own.  The CSR layout, the TFIDF_E_BUFFER / size-query protocol, the n_p
+ *   limits (0 legal, > 65536 invalid) and TFIDF_E_STATE before the first commit
+ *   are those of tfidf_fuzzy_terms_batch, without the dist array.
+ * tfidf_search_wildcard_batch (the query): pattern i's hits are the live
+ *   documents holding at least one matching term, doc id ascending, at
+ *   doc_ids[hit_offsets[i] .. hit_offsets[i + 1]).  Every hit scores 1.0f
+ *   (Lucene's constant-score rewrite of a multi-term query, boost 1), so no
+ *   score array is returned.  There is no clause limit: a pattern matching the
+ *   whole vocabulary returns every document that has a token.  hit_offsets[n_p
+ *   + 1], n_matched[n_p] (matching terms) and *n_out are always written;
+ *   doc_ids when *n_out <= cap, else TFIDF_E_BUFFER; cap 0 with NULL doc_ids
+ *   asks for the sizes.  Doc ids are positions among the live documents.
+ * Both run on a search context beside readers, tfidf_add_docs and
+ *   tfidf_commit; the reader forms see their own snapshot.  Scratch is bounded:
+ *   patterns are scanned in chunks that fit the kernels' staging, a chunk whose
+ *   matches exceed 2^22 is filled by ranges of its patterns, and the union runs
+ *   over ranges of patterns whose document bitmaps stay within 2^27 bits (one
+ *   pattern at least); the output does not depend on the chunking.
+ *   *ms_device (may be NULL): HIP-event time of the call's device work, also
+ *   the total of tfidf_last_search_ms.
+ * tfidf_wildcard_terms / tfidf_search_wildcard and their reader forms: the
+ *   batch of one, without the offsets arrays one pattern does not need. */
+int tfidf_wildcard_terms_batch(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                               uint32_t max_out, uint64_t *cand_offsets, uint64_t *n_matched, uint64_t *term_offsets,
+                               uint8_t *terms, uint64_t terms_cap, uint32_t *df, uint64_t cand_cap, uint64_t *n_cands,
+                               uint64_t *n_term_bytes, float *ms_device);
+int tfidf_reader_wildcard_terms_batch(tfidf_reader *rd, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                                      uint32_t max_out, uint64_t *cand_offsets, uint64_t *n_matched,
+                                      uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *df,
+                                      uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device);
+int tfidf_wildcard_terms(tfidf_index *ix, const uint8_t *pattern, uint64_t len, uint32_t max_out, uint64_t *n_matched,
+                         uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *df, uint64_t cand_cap,
+                         uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device);
+int tfidf_reader_wildcard_terms(tfidf_reader *rd, const uint8_t *pattern, uint64_t len, uint32_t max_out,
+                                uint64_t *n_matched, uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap,
+                                uint32_t *df, uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes,
+                                float *ms_device);
+int tfidf_search_wildcard_batch(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                                uint32_t *doc_ids, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_matched,
+                                uint64_t *n_out, float *ms_device);
+int tfidf_reader_search_wildcard_batch(tfidf_reader *rd, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                                       uint32_t *doc_ids, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_matched,
+                                       uint64_t *n_out, float *ms_device);
+int tfidf_search_wildcard(tfidf_index *ix, const uint8_t *pattern, uint64_t len, uint32_t *doc_ids, uint64_t cap,
+                          uint64_t *n_matched, uint64_t *n_out, float *ms_device);
+int tfidf_reader_search_wildcard(tfidf_reader *rd, const uint8_t *pattern, uint64_t len, uint32_t *doc_ids,
+                                 uint64_t cap, uint64_t *n_matched, uint64_t *n_out, float *ms_device);
+/* Of the last wildcard call that ran on this index (any form): the scans of
+ * the dictionary (one per staged chunk of patterns), the (pattern, term)
+ * matches found and the union chunks (0 for the term calls). */
+int tfidf_last_wildcard_stats(const tfidf_index *ix, uint64_t *scan_chunks, uint64_t *matches,
+                              uint64_t *union_chunks);
 /* ---- exact phrase search (no reference counterpart: Worker.java:225-227
  * escapes the quotes away; DESIGN.md section 2, "Phrase search") ----
  * The phrase bytes are analysed as a whole the way a document is (they are not
@@ -968,6 +1038,22 @@ int tfidf_node_fuzzy_terms_batch(tfidf_node *n, const uint8_t *t_utf8, const uin
                                  uint64_t *n_within, uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap,
                                  uint64_t *df, uint8_t *dist, uint64_t cand_cap, uint64_t *n_cands,
                                  uint64_t *n_term_bytes, float *ms_device);
+/* The wildcard calls over the node, after tfidf_node_commit, in both
+ * statistics modes: every shard with documents runs the batch at once on its
+ * own device.  Terms are merged as tfidf_node_fuzzy_terms_batch merges them
+ * (df summed over the shards, u64 here; n_matched counts the distinct terms;
+ * the order and max_out apply to the merged lists).  Hit ids become global by
+ * the shard's doc_base; shards are contiguous, so a pattern's list is the
+ * shards' lists in shard order (u64 ids), and n_matched counts the distinct
+ * matching terms.  A shard's failure fails the call with that shard's code.
+ * *ms_device is the largest of the shards' device times. */
+int tfidf_node_wildcard_terms_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                                    uint32_t max_out, uint64_t *cand_offsets, uint64_t *n_matched,
+                                    uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint64_t *df,
+                                    uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device);
+int tfidf_node_search_wildcard_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                                     uint64_t *doc_ids, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_matched,
+                                     uint64_t *n_out, float *ms_device);
 /* tfidf_search_phrase_batch over the node, after tfidf_node_commit, in both
  * statistics modes: every shard with documents runs the batch at once on its
  * own device, doc_ids become global by the shard's doc_base, and the host

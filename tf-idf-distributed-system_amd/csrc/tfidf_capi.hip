@@ -26,6 +26,7 @@
 #include "analysis.h"
 #include "compact_plan.h"
 #include "fuzzy_plan.h"
+#include "wildcard_plan.h"
 #include "mlt_plan.h"
 #include "phrase_plan.h"
 #include "snippet_plan.h"
@@ -351,6 +352,7 @@ struct SearchCtx {
   DevMem fz_in, fz_hs, fz_c, fz_tmp;        // fuzzy lookup: staged terms + counters, hashed slots, candidates, sort scratch
   DevMem ph_in, ph_s, ph_o, ph_tmp;         // phrase search: phrases' keys / sequences / weights, per-row arrays, ordered hits, sort scratch
   DevMem ml_in, ml_c, ml_tmp;               // more-like-this: staged seeds + row extents + counters, candidates, sort scratch
+  DevMem wc_bits, wc_cnt, wc_out, wc_len;   // wildcard union: pattern bitmaps, (pattern, block) counts, doc ids, matched rows' lengths
   PinnedVec<uint32_t> q_host, q_res, q_cand_h;   // q_cand_h: fused single query's block candidates (host merge)
   std::vector<uint64_t> q_merge;
   std::vector<uint32_t> q_units;            // batch scoring units {q, b0, b1, 0} (run_scoring)
@@ -359,7 +361,8 @@ struct SearchCtx {
   explicit SearchCtx(int d)
       : dev(d), q_in(d), q_out(d), cand(d), cand_n(d), out_doc(d), out_score(d), hits(d), hits_n(d), hits_c(d),
         hits_s(d), hits_P(d), ovf(d), hl_in(d), hl_cnt(d), hl_m(d), hl_s(d), hl_o(d), fz_in(d), fz_hs(d), fz_c(d),
-        fz_tmp(d), ph_in(d), ph_s(d), ph_o(d), ph_tmp(d), ml_in(d), ml_c(d), ml_tmp(d) {}
+        fz_tmp(d), ph_in(d), ph_s(d), ph_o(d), ph_tmp(d), ml_in(d), ml_c(d), ml_tmp(d), wc_bits(d),
+        wc_cnt(d), wc_out(d), wc_len(d) {}
   int init() {
     DeviceGuard g(dev);
     if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess ||
@@ -409,6 +412,7 @@ struct tfidf_index {
   uint64_t last_fz_scan_chunks = 0, last_fz_cand_chunks = 0;  // of the last fuzzy term lookup (ms_mu)
   uint64_t last_ph_candidates = 0, last_ph_row_chunks = 0;    // of the last phrase search (ms_mu)
   uint64_t last_mlt_entries = 0, last_mlt_chunks = 0;         // of the last more-like-this call (ms_mu)
+  uint64_t last_wc_scan_chunks = 0, last_wc_matches = 0, last_wc_union_chunks = 0;   // of the last wildcard call (ms_mu)
 
   // staged corpus (builder)
   std::shared_ptr<DevMem> text, offsets;   // offsets: u64[n_staged + 1]
@@ -3326,6 +3330,462 @@ extern "C" int tfidf_last_fuzzy_chunks(const tfidf_index *ix, uint64_t *scan_chu
   std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->ms_mu);
   if (scan_chunks) *scan_chunks = ix->last_fz_scan_chunks;
   if (cand_chunks) *cand_chunks = ix->last_fz_cand_chunks;
+  return TFIDF_OK;
+}
+
+// ---------------------------------------------------------------------------
+// wildcard and prefix search (wildcard_plan.h, kernels_wildcard.hip).  Per scan
+// chunk of patterns: one counting pass over the dictionary (n_matched and the
+// scratch sizes), then per match chunk a filling pass and the (pattern, df)
+// sort, which also groups the matched slots by pattern.  The terms route then
+// selects what the host orders, exactly as the fuzzy lookup does; the document
+// route unions the matched terms' postings per union chunk of patterns:
+// bitmaps, counts per (pattern, block), one prefix sum, ascending doc ids.
+// Every hit of the document route scores 1.0 (Lucene's constant-score rewrite
+// of a multi-term query, boost 1), so no score is returned, and no clause
+// limit applies: the matched terms never become scorer clauses.
+
+constexpr uint64_t kWcMatchBudget = 1ull << 22;  // (pattern, term) matches per fill, as kFzCandBudget
+constexpr uint64_t kWcHitBudget = 1ull << 27;    // bitmap bits per union chunk: 16 MiB of bitmaps, <= 512 MiB of doc ids
+static_assert(kWcChunkPatterns <= kFzChunkTerms && kWcChunkElems <= kFzChunkCps, "the staging area of the fuzzy scan holds a pattern chunk");
+
+static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                       bool want_docs, uint32_t max_out, WildcardLists *out) {
+  out->ms_device = 0.0f;
+  out->terms.assign(want_docs ? 0 : n_p, {});
+  out->n_matched.assign(n_p, 0);
+  out->docs.clear();
+  out->hit_off.assign((size_t)n_p + 1, 0);
+  std::vector<std::vector<uint32_t>> els(n_p);
+  std::vector<uint32_t> n_el(n_p, 0);
+  uint32_t buf[kWcMaxElems];
+  bool any = false;
+  for (uint32_t i = 0; i < n_p; i++) {
+    const uint64_t len = p_offsets[i + 1] - p_offsets[i];
+    if (len == 0) continue;
+    n_el[i] = wc_parse(p_utf8 + p_offsets[i], len, buf);
+    els[i].assign(buf, buf + n_el[i]);
+    any = any || n_el[i];
+  }
+  uint64_t n_scan = 0, n_match = 0, n_union = 0;
+  auto publish = [&](float ms) {
+    std::lock_guard<std::mutex> lk(ix->ms_mu);
+    ix->last_wc_scan_chunks = n_scan;
+    ix->last_wc_matches = n_match;
+    ix->last_wc_union_chunks = n_union;
+    ix->last_ms_scoring = 0.0f;
+    ix->last_ms_total = ms;
+  };
+  if (!any || S.n_docs == 0 || S.C == 0) { publish(0.0f); return TFIDF_OK; }
+  std::vector<uint64_t> cuts;
+  wc_plan_scan_chunks(n_el.data(), n_p, &cuts);
+  const uint64_t budget = std::min<uint64_t>(hl_budget("TFIDF_WILDCARD_MATCH_BUDGET", kWcMatchBudget), 1ull << 30);
+  const uint64_t hit_budget = hl_budget("TFIDF_WILDCARD_HIT_BUDGET", kWcHitBudget);
+  const uint32_t nb = (uint32_t)((S.n_docs + kBlockDocs - 1) / kBlockDocs);
+  if (!S.term_major && nb != S.n_blocks) return fail(TFIDF_E_STATE, "block count of the snapshot is off");
+
+  CtxLease lease(ix);
+  if (lease.rc) return lease.rc;
+  SearchCtx &X = *lease.c;
+  const hipStream_t s = lease.stream();
+  DeviceGuard g(ix->cfg.device);
+  const int max_grid = ix->num_cus * 8;
+  HIP_TRY(hipEventRecord(X.ev[QEV_0], s));
+
+  // the staging area of the fuzzy scan (fuzzy_on): offsets, elements, counts, seg, out_off, take, cursor, hashed count
+  const size_t in_cps = (kFzChunkTerms + 1) * 4, in_cnt = in_cps + kFzChunkCps * 4, in_seg = in_cnt + kFzChunkTerms * 4,
+               in_oo = in_seg + (kFzChunkTerms + 1) * 4, in_take = in_oo + (kFzChunkTerms + 1) * 4,
+               in_cur = in_take + kFzChunkTerms * 4, in_end = in_cur + 8;
+  HIP_TRY(X.fz_in.reserve(in_end));
+  uint8_t *ib = X.fz_in.as<uint8_t>();
+  uint32_t *d_off = reinterpret_cast<uint32_t *>(ib), *d_cps = reinterpret_cast<uint32_t *>(ib + in_cps),
+           *d_cnt = reinterpret_cast<uint32_t *>(ib + in_cnt), *d_seg = reinterpret_cast<uint32_t *>(ib + in_seg),
+           *d_oo = reinterpret_cast<uint32_t *>(ib + in_oo), *d_take = reinterpret_cast<uint32_t *>(ib + in_take),
+           *d_cur = reinterpret_cast<uint32_t *>(ib + in_cur), *d_hsn = d_cur + 1;
+
+  FzScan a{};
+  a.dict = S.dict.as<uint64_t>();
+  a.df = S.df_dev();
+  a.C = S.C;
+  a.t_off = d_off;
+  a.t_cps = d_cps;
+  a.counts = d_cnt;
+  a.cursor = d_cur;
+  const uint8_t *d_text = S.text->as<uint8_t>();
+  bool listed = false;                     // the hashed slots are listed by the first counting scan
+  uint32_t hs_n = 0;
+
+  WcUnion u{};
+  u.C = S.C;
+  u.n_blocks = nb;
+  u.NC = S.NC;
+  u.n_docs = S.n_docs;
+  u.post_words = S.nnz;
+  if (S.term_major) {
+    u.toff = S.toff.as<uint64_t>();
+    u.post = S.post.as<uint64_t>();
+  } else {
+    u.crank = S.crank.as<uint2>();
+    u.blk = S.blk.as<uint32_t>();
+    u.bbase = S.bbase.as<uint64_t>();
+    u.post32 = S.post.as<uint32_t>();
+  }
+
+  FzStage st;
+  std::vector<uint32_t> counts, seg, take, oo, h_slots;
+  std::vector<uint64_t> sub, usub, h_keys, h_cnt;
+  std::string ts;
+  for (size_t ci = 0; ci + 1 < cuts.size(); ci++) {
+    const uint64_t t0 = cuts[ci], nt = cuts[ci + 1] - t0;
+    fz_stage_terms(els, t0, t0 + nt, &st);
+    if (st.cps.empty()) continue;                                   // only patterns that match nothing
+    if (nt > kWcChunkPatterns || st.cps.size() > kWcChunkElems)
+      return fail(TFIDF_E_STATE, "wildcard scan chunk over its limits");
+    n_scan++;
+    HIP_TRY(hipMemcpyAsync(d_off, st.off.data(), (nt + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_cps, st.cps.data(), st.cps.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_cnt, 0, nt * 4, s));
+    a.n_terms = (uint32_t)nt;
+    a.t_off = d_off;
+    a.keys = nullptr;
+    a.slots = nullptr;
+    a.cap = 0;
+    a.hs_list = nullptr;
+    a.hs_cap = 0;
+    if (!listed) {
+      HIP_TRY(X.fz_hs.reserve((size_t)kFzHashedInit * 4));
+      HIP_TRY(hipMemsetAsync(d_hsn, 0, 4, s));
+      a.hs_list = X.fz_hs.as<uint32_t>();
+      a.hs_count = d_hsn;
+      a.hs_cap = (uint32_t)(X.fz_hs.bytes / 4);
+    }
+    HIP_TRY(launch_wc_scan(false, a, max_grid, s));
+    if (!listed) {
+      HIP_TRY(hipMemcpyAsync(&hs_n, d_hsn, 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      if (hs_n > a.hs_cap) {                                        // more hashed slots than the list held: list them again
+        HIP_TRY(X.fz_hs.reserve((size_t)hs_n * 4));
+        HIP_TRY(hipMemsetAsync(d_hsn, 0, 4, s));
+        FzScan l = a;
+        l.n_terms = 0;
+        l.hs_list = X.fz_hs.as<uint32_t>();
+        l.hs_cap = hs_n;
+        HIP_TRY(launch_wc_scan(false, l, max_grid, s));
+      }
+      listed = true;
+    }
+    a.hs_list = X.fz_hs.as<uint32_t>();
+    a.hs_count = nullptr;
+    a.hs_n = hs_n;
+    HIP_TRY(launch_wc_hashed(false, a, d_text, S.text_bytes, max_grid, s));
+    counts.resize(nt);
+    HIP_TRY(hipMemcpyAsync(counts.data(), d_cnt, nt * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (uint64_t t = 0; t < nt; t++) {
+      out->n_matched[t0 + t] = counts[t];
+      n_match += counts[t];
+    }
+
+    sub.clear();
+    wc_plan_match_chunks(counts.data(), 0, nt, budget, &sub);
+    for (size_t si = 0; si + 1 < sub.size(); si++) {
+      const uint64_t a0 = sub[si], na = sub[si + 1] - a0;
+      seg.assign(na + 1, 0);
+      uint64_t T = 0;
+      for (uint64_t t = 0; t < na; t++) {
+        T += counts[a0 + t];
+        if (T >= (1ull << 31)) return fail(TFIDF_E_INVALID_ARG, "more than 2^31 matches for one pattern range");
+        seg[t + 1] = (uint32_t)T;
+      }
+      if (T == 0) continue;
+      // matches: keys [T] x 2 (sort in / out), slots [T] x 2
+      const size_t Tp = (T + 1) & ~(size_t)1;
+      HIP_TRY(X.fz_c.reserve(Tp * 24));
+      uint64_t *k_in = X.fz_c.as<uint64_t>(), *k_out = k_in + Tp;
+      uint32_t *s_in = reinterpret_cast<uint32_t *>(k_out + Tp), *s_out = s_in + Tp;
+      HIP_TRY(hipMemsetAsync(d_cur, 0, 4, s));
+      HIP_TRY(hipMemsetAsync(s_in, 0xFF, T * 4, s));                 // a slot the fill does not write is out of range
+      FzScan f = a;
+      f.t_off = d_off + a0;                 // the range's patterns: offsets into the chunk's elements
+      f.n_terms = (uint32_t)na;
+      f.keys = k_in;
+      f.slots = s_in;
+      f.cap = (uint32_t)T;
+      HIP_TRY(launch_wc_scan(true, f, max_grid, s));
+      HIP_TRY(launch_wc_hashed(true, f, d_text, S.text_bytes, max_grid, s));
+      size_t tmp_bytes = 0;
+      HIP_TRY(fz_sort(nullptr, &tmp_bytes, k_in, k_out, s_in, s_out, (uint32_t)T, s));
+      HIP_TRY(X.fz_tmp.reserve(tmp_bytes));
+      tmp_bytes = X.fz_tmp.bytes;
+      HIP_TRY(fz_sort(X.fz_tmp.p, &tmp_bytes, k_in, k_out, s_in, s_out, (uint32_t)T, s));
+      HIP_TRY(hipMemcpyAsync(d_seg, seg.data(), (na + 1) * 4, hipMemcpyHostToDevice, s));
+
+      if (want_docs) {
+        usub.clear();
+        wc_plan_union_chunks(0, na, (uint64_t)nb * kBlockDocs, hit_budget, &usub);
+        for (size_t ui = 0; ui + 1 < usub.size(); ui++) {
+          const uint64_t u0 = usub[ui], np = usub[ui + 1] - u0;
+          const uint32_t M = seg[u0 + np] - seg[u0];
+          if (M == 0) continue;                                     // no pattern of the chunk has a term
+          n_union++;
+          const uint64_t n_pb = np * nb;
+          HIP_TRY(X.wc_bits.reserve(n_pb * (kBlockDocs / 8)));
+          HIP_TRY(X.wc_cnt.reserve((n_pb + 1) * 8));
+          u.slots = s_out;
+          u.seg = d_seg + u0;
+          u.n_pat = (uint32_t)np;
+          u.bits = X.wc_bits.as<uint32_t>();
+          u.cnt = X.wc_cnt.as<uint64_t>();
+          u.out = nullptr;
+          u.out_cap = 0;
+          if (S.term_major) {
+            HIP_TRY(hipMemsetAsync(u.bits, 0, n_pb * (kBlockDocs / 8), s));
+            HIP_TRY(X.wc_len.reserve(((size_t)M + 1) * 8));
+            u.row_off = X.wc_len.as<uint64_t>();
+            HIP_TRY(launch_wc_rows(u, M, s));
+            HIP_TRY(exclusive_scan_u64(u.row_off, u.row_off, M, s));
+            HIP_TRY(launch_wc_union_term(u, M, S.nnz, max_grid, s));
+          } else {
+            HIP_TRY(launch_wc_union_block(u, s));
+          }
+          HIP_TRY(launch_wc_count(u, s));
+          HIP_TRY(exclusive_scan_u64(u.cnt, u.cnt, n_pb, s));
+          h_cnt.resize(n_pb + 1);
+          HIP_TRY(hipMemcpyAsync(h_cnt.data(), u.cnt, (n_pb + 1) * 8, hipMemcpyDeviceToHost, s));
+          HIP_TRY(hipStreamSynchronize(s));
+          const uint64_t H = h_cnt[n_pb];
+          if (H > np * S.n_docs) return fail(TFIDF_E_STATE, "wildcard union counted more hits than documents");
+          for (uint64_t t = 0; t < np; t++)
+            out->hit_off[t0 + a0 + u0 + t + 1] = h_cnt[(t + 1) * nb] - h_cnt[t * nb];
+          if (H == 0) continue;
+          HIP_TRY(X.wc_out.reserve(H * 4));
+          u.out = X.wc_out.as<uint32_t>();
+          u.out_cap = H;
+          HIP_TRY(launch_wc_expand(u, s));
+          const size_t at = out->docs.size();
+          out->docs.resize(at + H);
+          HIP_TRY(hipMemcpyAsync(out->docs.data() + at, u.out, H * 4, hipMemcpyDeviceToHost, s));
+          HIP_TRY(hipStreamSynchronize(s));
+        }
+        continue;
+      }
+
+      // what the host orders: everything (max_out == 0), or the selection packed into the sort's input buffers
+      uint64_t n_take = T;
+      oo = seg;
+      const uint64_t *src_k = k_out;
+      const uint32_t *src_s = s_out;
+      if (max_out) {
+        take.resize(na);
+        HIP_TRY(launch_fz_select(k_out, d_seg, (uint32_t)na, max_out, d_take, s));
+        HIP_TRY(hipMemcpyAsync(take.data(), d_take, na * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        n_take = 0;
+        for (uint64_t t = 0; t < na; t++) {
+          if (take[t] > seg[t + 1] - seg[t]) return fail(TFIDF_E_STATE, "wildcard selection past its segment");
+          oo[t] = (uint32_t)n_take;
+          n_take += take[t];
+        }
+        oo[na] = (uint32_t)n_take;
+        HIP_TRY(hipMemcpyAsync(d_oo, oo.data(), (na + 1) * 4, hipMemcpyHostToDevice, s));
+        HIP_TRY(launch_fz_gather(k_out, s_out, d_seg, d_oo, (uint32_t)na, k_in, s_in, s));
+        src_k = k_in;
+        src_s = s_in;
+      }
+      h_keys.resize(n_take);
+      h_slots.resize(n_take);
+      HIP_TRY(hipMemcpyAsync(h_keys.data(), src_k, n_take * 8, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(h_slots.data(), src_s, n_take * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+      for (uint64_t t = 0; t < na; t++) {
+        std::vector<FuzzyCand> &L = out->terms[t0 + a0 + t];
+        L.reserve(oo[t + 1] - oo[t]);
+        for (uint32_t i = oo[t]; i < oo[t + 1]; i++) {
+          if (fz_key_term(h_keys[i]) != t || h_slots[i] >= S.C)
+            return fail(TFIDF_E_STATE, "wildcard match %u of pattern %llu is out of place", i, (unsigned long long)t);
+          if (int rc = slot_term(S, h_slots[i], &ts)) return rc;
+          L.push_back(FuzzyCand{ts, fz_key_df(h_keys[i]), 0});
+        }
+        std::sort(L.begin(), L.end(), [](const FuzzyCand &x, const FuzzyCand &y) {
+          if (x.df != y.df) return x.df > y.df;
+          return x.term < y.term;
+        });
+        if (max_out && L.size() > max_out) L.resize(max_out);
+      }
+    }
+  }
+  for (uint32_t i = 0; i < n_p; i++) out->hit_off[i + 1] += out->hit_off[i];
+  if (want_docs && out->hit_off[n_p] != out->docs.size()) return fail(TFIDF_E_STATE, "wildcard hit lists are out of step");
+  HIP_TRY(hipEventRecord(X.ev[QEV_1], s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(hipEventElapsedTime(&out->ms_device, X.ev[QEV_0], X.ev[QEV_1]));
+  publish(out->ms_device);
+  return TFIDF_OK;
+}
+
+static int wildcard_check_args(const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p) {
+  if (n_p > kWcMaxPatterns) return fail(TFIDF_E_INVALID_ARG, "more than %u patterns in one call", kWcMaxPatterns);
+  if (n_p && (!p_offsets || (!p_utf8 && p_offsets[n_p] != p_offsets[0])))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  for (uint32_t i = 0; i < n_p; i++)
+    if (p_offsets[i + 1] < p_offsets[i]) return fail(TFIDF_E_INVALID_ARG, "p_offsets decrease at pattern %u", i);
+  return TFIDF_OK;
+}
+
+int tfidf::index_wildcard(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p, bool docs,
+                          uint32_t max_out, WildcardLists *out) {
+  if (!ix || !out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (int rc = wildcard_check_args(p_utf8, p_offsets, n_p)) return rc;
+  if (max_out > kWcMaxOut) return fail(TFIDF_E_INVALID_ARG, "max_out %u above %u", max_out, kWcMaxOut);
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "wildcard search before commit");
+  return wildcard_on(ix, *snap, p_utf8, p_offsets, n_p, docs, max_out, out);
+}
+
+// the CSR output of the term calls: offsets, n_matched and the totals always, the payload when it fits
+static int wildcard_terms_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                             uint32_t n_p, uint32_t max_out, uint64_t *cand_offsets, uint64_t *n_matched,
+                             uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *df,
+                             uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device) {
+  if (int rc = wildcard_check_args(p_utf8, p_offsets, n_p)) return rc;
+  if (max_out < 1 || max_out > kWcMaxOut) return fail(TFIDF_E_INVALID_ARG, "max_out %u outside 1..%u", max_out, kWcMaxOut);
+  if (!cand_offsets || (n_p && !n_matched) || !n_cands || !n_term_bytes) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (ms_device) *ms_device = 0.0f;
+  WildcardLists wl;
+  if (int rc = wildcard_on(ix, S, p_utf8, p_offsets, n_p, false, max_out, &wl)) return rc;
+  if (ms_device) *ms_device = wl.ms_device;
+  uint64_t nc = 0, nbytes = 0;
+  cand_offsets[0] = 0;
+  for (uint32_t i = 0; i < n_p; i++) {
+    n_matched[i] = wl.n_matched[i];
+    nc += wl.terms[i].size();
+    for (const FuzzyCand &c : wl.terms[i]) nbytes += c.term.size();
+    cand_offsets[i + 1] = nc;
+  }
+  *n_cands = nc;
+  *n_term_bytes = nbytes;
+  if (nc > cand_cap || nbytes > terms_cap || (nc && (!term_offsets || !df)) || (nbytes && !terms))
+    return fail(TFIDF_E_BUFFER, "need %llu term slots and %llu term bytes", (unsigned long long)nc,
+                (unsigned long long)nbytes);
+  uint64_t at = 0, b = 0;
+  if (term_offsets) term_offsets[0] = 0;
+  for (uint32_t i = 0; i < n_p; i++)
+    for (const FuzzyCand &c : wl.terms[i]) {
+      memcpy(terms + b, c.term.data(), c.term.size());
+      b += c.term.size();
+      df[at] = (uint32_t)c.df;
+      term_offsets[++at] = b;
+    }
+  return TFIDF_OK;
+}
+
+// the output of the document calls: hit_offsets, n_matched and *n_out always, the doc ids when they fit
+static int wildcard_docs_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                            uint32_t n_p, uint32_t *doc_ids, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_matched,
+                            uint64_t *n_out, float *ms_device) {
+  if (int rc = wildcard_check_args(p_utf8, p_offsets, n_p)) return rc;
+  if (!hit_offsets || (n_p && !n_matched) || !n_out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (ms_device) *ms_device = 0.0f;
+  WildcardLists wl;
+  if (int rc = wildcard_on(ix, S, p_utf8, p_offsets, n_p, true, 0, &wl)) return rc;
+  if (ms_device) *ms_device = wl.ms_device;
+  for (uint32_t i = 0; i < n_p; i++) n_matched[i] = wl.n_matched[i];
+  memcpy(hit_offsets, wl.hit_off.data(), ((size_t)n_p + 1) * 8);
+  *n_out = wl.docs.size();
+  if (wl.docs.size() > cap || (!wl.docs.empty() && !doc_ids))
+    return fail(TFIDF_E_BUFFER, "need %llu hit slots", (unsigned long long)wl.docs.size());
+  if (!wl.docs.empty()) memcpy(doc_ids, wl.docs.data(), wl.docs.size() * 4);
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_reader_wildcard_terms_batch(tfidf_reader *rd, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                                 uint32_t n_p, uint32_t max_out, uint64_t *cand_offsets,
+                                                 uint64_t *n_matched, uint64_t *term_offsets, uint8_t *terms,
+                                                 uint64_t terms_cap, uint32_t *df, uint64_t cand_cap,
+                                                 uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  return wildcard_terms_on(rd->ix, *rd->S, p_utf8, p_offsets, n_p, max_out, cand_offsets, n_matched, term_offsets,
+                           terms, terms_cap, df, cand_cap, n_cands, n_term_bytes, ms_device);
+}
+
+extern "C" int tfidf_wildcard_terms_batch(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                          uint32_t n_p, uint32_t max_out, uint64_t *cand_offsets, uint64_t *n_matched,
+                                          uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *df,
+                                          uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes,
+                                          float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  if (int rc = wildcard_check_args(p_utf8, p_offsets, n_p)) return rc;
+  if (max_out < 1 || max_out > kWcMaxOut) return fail(TFIDF_E_INVALID_ARG, "max_out %u outside 1..%u", max_out, kWcMaxOut);
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "wildcard lookup before commit");
+  return wildcard_terms_on(ix, *snap, p_utf8, p_offsets, n_p, max_out, cand_offsets, n_matched, term_offsets, terms,
+                           terms_cap, df, cand_cap, n_cands, n_term_bytes, ms_device);
+}
+
+extern "C" int tfidf_reader_search_wildcard_batch(tfidf_reader *rd, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                                  uint32_t n_p, uint32_t *doc_ids, uint64_t cap, uint64_t *hit_offsets,
+                                                  uint64_t *n_matched, uint64_t *n_out, float *ms_device) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  return wildcard_docs_on(rd->ix, *rd->S, p_utf8, p_offsets, n_p, doc_ids, cap, hit_offsets, n_matched, n_out,
+                          ms_device);
+}
+
+extern "C" int tfidf_search_wildcard_batch(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                           uint32_t n_p, uint32_t *doc_ids, uint64_t cap, uint64_t *hit_offsets,
+                                           uint64_t *n_matched, uint64_t *n_out, float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  if (int rc = wildcard_check_args(p_utf8, p_offsets, n_p)) return rc;
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "wildcard search before commit");
+  return wildcard_docs_on(ix, *snap, p_utf8, p_offsets, n_p, doc_ids, cap, hit_offsets, n_matched, n_out, ms_device);
+}
+
+// the batch of one, without the offsets arrays of the input and of the patterns' lists
+extern "C" int tfidf_reader_wildcard_terms(tfidf_reader *rd, const uint8_t *pattern, uint64_t len, uint32_t max_out,
+                                           uint64_t *n_matched, uint64_t *term_offsets, uint8_t *terms,
+                                           uint64_t terms_cap, uint32_t *df, uint64_t cand_cap, uint64_t *n_cands,
+                                           uint64_t *n_term_bytes, float *ms_device) {
+  if (!n_matched || (!pattern && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t p_off[2] = {0, len};
+  uint64_t c_off[2];
+  return tfidf_reader_wildcard_terms_batch(rd, pattern, p_off, 1, max_out, c_off, n_matched, term_offsets, terms,
+                                           terms_cap, df, cand_cap, n_cands, n_term_bytes, ms_device);
+}
+
+extern "C" int tfidf_wildcard_terms(tfidf_index *ix, const uint8_t *pattern, uint64_t len, uint32_t max_out,
+                                    uint64_t *n_matched, uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap,
+                                    uint32_t *df, uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes,
+                                    float *ms_device) {
+  if (!n_matched || (!pattern && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t p_off[2] = {0, len};
+  uint64_t c_off[2];
+  return tfidf_wildcard_terms_batch(ix, pattern, p_off, 1, max_out, c_off, n_matched, term_offsets, terms, terms_cap,
+                                    df, cand_cap, n_cands, n_term_bytes, ms_device);
+}
+
+extern "C" int tfidf_reader_search_wildcard(tfidf_reader *rd, const uint8_t *pattern, uint64_t len, uint32_t *doc_ids,
+                                            uint64_t cap, uint64_t *n_matched, uint64_t *n_out, float *ms_device) {
+  if (!n_matched || (!pattern && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t p_off[2] = {0, len};
+  uint64_t h_off[2];
+  return tfidf_reader_search_wildcard_batch(rd, pattern, p_off, 1, doc_ids, cap, h_off, n_matched, n_out, ms_device);
+}
+
+extern "C" int tfidf_search_wildcard(tfidf_index *ix, const uint8_t *pattern, uint64_t len, uint32_t *doc_ids,
+                                     uint64_t cap, uint64_t *n_matched, uint64_t *n_out, float *ms_device) {
+  if (!n_matched || (!pattern && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t p_off[2] = {0, len};
+  uint64_t h_off[2];
+  return tfidf_search_wildcard_batch(ix, pattern, p_off, 1, doc_ids, cap, h_off, n_matched, n_out, ms_device);
+}
+
+extern "C" int tfidf_last_wildcard_stats(const tfidf_index *ix, uint64_t *scan_chunks, uint64_t *matches,
+                                         uint64_t *union_chunks) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->ms_mu);
+  if (scan_chunks) *scan_chunks = ix->last_wc_scan_chunks;
+  if (matches) *matches = ix->last_wc_matches;
+  if (union_chunks) *union_chunks = ix->last_wc_union_chunks;
   return TFIDF_OK;
 }
 

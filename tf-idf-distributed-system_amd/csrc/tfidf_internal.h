@@ -475,6 +475,39 @@ hipError_t launch_fz_select(const uint64_t *keys, const uint32_t *seg, uint32_t 
 hipError_t launch_fz_gather(const uint64_t *keys, const uint32_t *slots, const uint32_t *seg, const uint32_t *out_off,
                             uint32_t n_terms, uint64_t *o_keys, uint32_t *o_slots, hipStream_t s);
 
+// --- wildcard and prefix search (kernels_wildcard.hip; rules in wildcard_plan.h) ---
+// The scan takes an FzScan: t_cps holds pattern elements (wc_parse), n_terms <=
+// kWcChunkPatterns patterns of t_off[n_terms] - t_off[0] <= kWcChunkElems
+// elements; max_edits and prefix_len are not read.
+hipError_t launch_wc_scan(bool fill, const FzScan &a, int max_grid, hipStream_t s);
+hipError_t launch_wc_hashed(bool fill, const FzScan &a, const uint8_t *text, uint64_t text_bytes, int max_grid,
+                            hipStream_t s);
+// The union of the matched terms' postings for n_pat patterns: pattern p's
+// matched slots are slots[seg[p]] .. slots[seg[p + 1]].  bits: n_pat bitmaps of
+// n_blocks * kBlockDocs bits; cnt: n_pat * n_blocks + 1 words (bits per
+// (pattern, block), then scanned in place); out: the ascending doc ids.
+struct WcUnion {
+  const uint32_t *slots, *seg;
+  uint32_t n_pat, C;          // C: dictionary slots
+  uint32_t n_blocks, NC;
+  uint64_t n_docs, post_words;  // post_words: postings the layout's buffer holds
+  const uint2 *crank;         // block-major (toff == nullptr): col_rank, blk, bbase, post_word postings
+  const uint32_t *blk;
+  const uint64_t *bbase;
+  const uint32_t *post32;
+  const uint64_t *toff, *post;  // term-major
+  uint64_t *row_off;          // term-major: [M + 1] the matched rows' lengths, then scanned in place
+  uint32_t *bits;
+  uint64_t *cnt;
+  uint32_t *out;
+  uint64_t out_cap;
+};
+hipError_t launch_wc_union_block(const WcUnion &a, hipStream_t s);
+hipError_t launch_wc_rows(const WcUnion &a, uint32_t M, hipStream_t s);
+hipError_t launch_wc_union_term(const WcUnion &a, uint32_t M, uint64_t n_post_bound, int max_grid, hipStream_t s);
+hipError_t launch_wc_count(const WcUnion &a, hipStream_t s);
+hipError_t launch_wc_expand(const WcUnion &a, hipStream_t s);
+
 // --- exact phrase search (kernels_phrase.hip; rules in phrase_plan.h) ---
 hipError_t launch_ph_scan(bool fill, const uint8_t *text, const uint64_t *ext, const HlItem *items, uint32_t i0,
                           uint32_t ni, const HlKey *keys, const uint32_t *key_off, const uint32_t *row_q,
@@ -555,6 +588,19 @@ struct FuzzyLists {
 };
 int index_fuzzy_terms(tfidf_index *ix, const uint8_t *t_utf8, const uint64_t *t_offsets, uint32_t n_terms,
                       uint32_t max_edits, uint32_t prefix_len, uint32_t max_out, FuzzyLists *out);
+// wildcard search on the snapshot published now.  docs == false: per pattern its
+// matching terms in (df descending, bytes) order (at most max_out; 0 = all of
+// them; dist is 0).  docs == true: the patterns' ascending hit lists, one after
+// the other (hit_off: n_p + 1).  n_matched: matching terms before truncation.
+struct WildcardLists {
+  std::vector<std::vector<FuzzyCand>> terms;
+  std::vector<uint64_t> n_matched;
+  std::vector<uint32_t> docs;
+  std::vector<uint64_t> hit_off;
+  float ms_device = 0.0f;
+};
+int index_wildcard(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p, bool docs,
+                   uint32_t max_out, WildcardLists *out);
 // more-like-this on the snapshot published now: per seed (a committed doc id)
 // its interesting terms in selection order and the candidates before truncation
 struct MltRules;

@@ -88,6 +88,23 @@ def _fuzzy_batch_sig(df):
 _FUZZY_SINGLE_SIG = (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, U64P, U64P, VP,
                                C.c_uint64, U32P, U8P, C.c_uint64, U64P, U64P, F32P])
 
+
+def _wildcard_terms_sig(df):
+    """tfidf_[reader_|node_]wildcard_terms_batch; df is u32 per shard, u64 over a node."""
+    return (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, C.c_uint32, U64P, U64P, U64P, VP, C.c_uint64, df, C.c_uint64,
+                      U64P, U64P, F32P])
+
+
+def _wildcard_docs_sig(doc):
+    """tfidf_[reader_|node_]search_wildcard_batch; doc ids are u32 per shard, u64 over a node."""
+    return (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, doc, C.c_uint64, U64P, U64P, U64P, F32P])
+
+
+_WILDCARD_TERMS_SINGLE_SIG = (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, U64P, U64P, VP, C.c_uint64, U32P,
+                                        C.c_uint64, U64P, U64P, F32P])
+_WILDCARD_DOCS_SINGLE_SIG = (C.c_int, [VP, C.c_char_p, C.c_uint64, U32P, C.c_uint64, U64P, U64P, F32P])
+
+
 class MltParams(C.Structure):
     _fields_ = [("min_tf", C.c_uint32), ("min_df", C.c_uint32), ("max_df", C.c_uint32), ("max_terms", C.c_uint32)]
 
@@ -140,6 +157,17 @@ SIGNATURES = {
     "tfidf_fuzzy_terms": _FUZZY_SINGLE_SIG,
     "tfidf_reader_fuzzy_terms": _FUZZY_SINGLE_SIG,
     "tfidf_last_fuzzy_chunks": (C.c_int, [VP, U64P, U64P]),
+    "tfidf_wildcard_terms_batch": _wildcard_terms_sig(U32P),
+    "tfidf_reader_wildcard_terms_batch": _wildcard_terms_sig(U32P),
+    "tfidf_node_wildcard_terms_batch": _wildcard_terms_sig(U64P),
+    "tfidf_wildcard_terms": _WILDCARD_TERMS_SINGLE_SIG,
+    "tfidf_reader_wildcard_terms": _WILDCARD_TERMS_SINGLE_SIG,
+    "tfidf_search_wildcard_batch": _wildcard_docs_sig(U32P),
+    "tfidf_reader_search_wildcard_batch": _wildcard_docs_sig(U32P),
+    "tfidf_node_search_wildcard_batch": _wildcard_docs_sig(U64P),
+    "tfidf_search_wildcard": _WILDCARD_DOCS_SINGLE_SIG,
+    "tfidf_reader_search_wildcard": _WILDCARD_DOCS_SINGLE_SIG,
+    "tfidf_last_wildcard_stats": (C.c_int, [VP, U64P, U64P, U64P]),
     "tfidf_search_phrase_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U32P, F32P, U32P, C.c_uint64, U64P,
                                             U64P]),
     "tfidf_reader_search_phrase_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U32P, F32P, U32P, C.c_uint64,

@@ -485,6 +485,21 @@ class Node:
         return E._fuzzy_lists(E._fuzzy_batch_arrays(L.load().tfidf_node_fuzzy_terms_batch, self._h, terms, max_edits,
                                                     prefix_len, max_out, df_dtype=np.uint64))
 
+    def wildcard_terms_batch(self, patterns, max_out=10):
+        """ShardIndex.wildcard_terms_batch over the node's vocabulary: df is
+        summed over the shards and n_matched counts distinct terms
+        (tfidf_node_wildcard_terms_batch)."""
+        from . import engine as E
+        return E._wildcard_term_lists(E._wildcard_terms_arrays(L.load().tfidf_node_wildcard_terms_batch, self._h,
+                                                               patterns, max_out, df_dtype=np.uint64))
+
+    def search_wildcard_batch(self, patterns):
+        """ShardIndex.search_wildcard_batch over the node: [(ascending global
+        doc ids, distinct matching terms)] (tfidf_node_search_wildcard_batch)."""
+        from . import engine as E
+        return E._wildcard_doc_lists(E._wildcard_docs_arrays(L.load().tfidf_node_search_wildcard_batch, self._h,
+                                                             patterns, dtype=np.uint64))
+
     def search_phrase_batch(self, phrases):
         """ShardIndex.search_phrase_batch over the node: [[(global doc, score,
         freq)]], every shard's hits merged per phrase by (score desc, global id

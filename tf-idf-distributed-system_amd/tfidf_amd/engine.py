@@ -278,6 +278,107 @@ def _fuzzy_single(fn, handle, term, max_edits, prefix_len, max_out):
     return [(raw[t[j]:t[j + 1]], int(df[j]), int(dist[j])) for j in range(nc.value)], within.value
 
 
+def _wildcard_terms_arrays(fn, handle, patterns, max_out, df_dtype=np.uint32):
+    """tfidf_[reader_|node_]wildcard_terms_batch, sized as _fuzzy_batch_arrays
+    sizes the fuzzy batch.  -> (cand offsets uint64[n + 1], n_matched
+    uint64[n], term offsets uint64[m + 1], term blob bytes, df[m], ms_device)."""
+    patterns = list(patterns)
+    blob, p_offs = _key_arrays(patterns)
+    n = len(patterns)
+    c_offs = np.zeros(n + 1, np.uint64)
+    matched = np.zeros(max(n, 1), np.uint64)
+    nc, nb, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+    dfc = np.ctypeslib.as_ctypes_type(df_dtype)
+    m_cap = min(n * max(int(max_out), 0), 1 << 20)
+    b_cap = 32 * m_cap
+    for _ in range(2):
+        t_out = np.zeros(m_cap + 1, np.uint64)
+        text = np.empty(max(b_cap, 1), np.uint8)
+        df = np.zeros(max(m_cap, 1), df_dtype)
+        rc = fn(handle, blob, L.ptr(p_offs, C.c_uint64), n, max_out, L.ptr(c_offs, C.c_uint64),
+                L.ptr(matched, C.c_uint64), L.ptr(t_out, C.c_uint64), text.ctypes.data_as(C.c_void_p), b_cap,
+                L.ptr(df, dfc), m_cap, C.byref(nc), C.byref(nb), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        m_cap, b_cap = nc.value, nb.value
+    L.check(rc)
+    m, b = nc.value, nb.value
+    return c_offs, matched[:n], t_out[:m + 1], text[:b].tobytes(), df[:m], ms.value
+
+
+def _wildcard_term_lists(arrays):
+    """-> per pattern ([(term bytes, df)], n_matched)."""
+    c_offs, matched, t_out, text, df, _ = arrays
+    c, t, f = c_offs.tolist(), t_out.tolist(), df.tolist()
+    cands = [(text[t[j]:t[j + 1]], f[j]) for j in range(len(t) - 1)]
+    return [(cands[c[i]:c[i + 1]], int(matched[i])) for i in range(len(c) - 1)]
+
+
+def _wildcard_terms_single(fn, handle, pattern, max_out):
+    """tfidf_wildcard_terms / tfidf_reader_wildcard_terms -> ([(term bytes, df)], n_matched)."""
+    matched, nc, nb, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+    m_cap = min(max(int(max_out), 0), 1 << 20)
+    b_cap = 32 * m_cap
+    for _ in range(2):
+        t_out = np.zeros(m_cap + 1, np.uint64)
+        text = np.empty(max(b_cap, 1), np.uint8)
+        df = np.zeros(max(m_cap, 1), np.uint32)
+        rc = fn(handle, pattern, len(pattern), max_out, C.byref(matched), L.ptr(t_out, C.c_uint64),
+                text.ctypes.data_as(C.c_void_p), b_cap, L.ptr(df, C.c_uint32), m_cap, C.byref(nc), C.byref(nb),
+                C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        m_cap, b_cap = nc.value, nb.value
+    L.check(rc)
+    raw, t = text[:nb.value].tobytes(), t_out.tolist()
+    return [(raw[t[j]:t[j + 1]], int(df[j])) for j in range(nc.value)], matched.value
+
+
+def _wildcard_docs_arrays(fn, handle, patterns, cap=None, dtype=np.uint32):
+    """tfidf_[reader_|node_]search_wildcard_batch: one call for the sizes (or
+    with ``cap`` hit slots), then again with the size reported while that was too small.
+    -> (doc ids dtype[], hit offsets uint64[n + 1], n_matched uint64[n], ms_device)."""
+    patterns = list(patterns)
+    blob, p_offs = _key_arrays(patterns)
+    n = len(patterns)
+    h_offs = np.zeros(n + 1, np.uint64)
+    matched = np.zeros(max(n, 1), np.uint64)
+    total, ms = C.c_uint64(), C.c_float()
+    dc = np.ctypeslib.as_ctypes_type(dtype)
+    cap = 0 if cap is None else int(cap)
+    for _ in range(8):                      # beside commits the index may have grown between two calls: ask again
+        docs = np.empty(max(cap, 1), dtype)
+        rc = fn(handle, blob, L.ptr(p_offs, C.c_uint64), n, L.ptr(docs, dc) if cap else None, cap,
+                L.ptr(h_offs, C.c_uint64), L.ptr(matched, C.c_uint64), C.byref(total), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        cap = total.value
+    L.check(rc)
+    return docs[:total.value], h_offs, matched[:n], ms.value
+
+
+def _wildcard_doc_lists(arrays):
+    """-> per pattern (ascending doc ids, n_matched)."""
+    docs, h_offs, matched, _ = arrays
+    d, o = docs.tolist(), h_offs.tolist()
+    return [(d[o[i]:o[i + 1]], int(matched[i])) for i in range(len(o) - 1)]
+
+
+def _wildcard_docs_single(fn, handle, pattern):
+    """tfidf_search_wildcard / tfidf_reader_search_wildcard -> (ascending doc ids, n_matched)."""
+    matched, total, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+    cap = 0
+    for _ in range(8):                      # as _wildcard_docs_arrays
+        docs = np.empty(max(cap, 1), np.uint32)
+        rc = fn(handle, pattern, len(pattern), L.ptr(docs, C.c_uint32) if cap else None, cap, C.byref(matched),
+                C.byref(total), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        cap = total.value
+    L.check(rc)
+    return docs[:total.value].tolist(), matched.value
+
+
 def _per_query(rows, d_offs):
     f = d_offs.tolist()
     return [rows[f[i]:f[i + 1]] for i in range(len(f) - 1)]
@@ -321,7 +422,7 @@ def _phrase_single(fn, handle, phrase):
     """tfidf_[reader_]search_phrase -> [(doc, score, freq)]."""
     n = C.c_uint64()
     cap = 0
-    for _ in range(2):
+    for _ in range(8):                      # as _wildcard_docs_arrays
         docs = np.empty(max(cap, 1), np.uint32)
         scores = np.empty(max(cap, 1), np.float32)
         freqs = np.empty(max(cap, 1), np.uint32)
@@ -560,6 +661,41 @@ class ShardIndex:
         empty, not UTF-8 or longer than 255 UTF-16 units gives ([], 0)."""
         return _fuzzy_lists(_fuzzy_batch_arrays(L.load().tfidf_fuzzy_terms_batch, self._h, terms, max_edits,
                                                 prefix_len, max_out))
+
+    def wildcard_terms(self, pattern: bytes, max_out=10):
+        """([(term bytes, df)], n_matched): the vocabulary terms matching the
+        wildcard pattern (``*`` any run of code points, ``?`` one code point,
+        ``\\x`` the literal x), df descending then bytes; at most max_out
+        (1..1024) of the n_matched there are (tfidf_wildcard_terms)."""
+        return _wildcard_terms_single(L.load().tfidf_wildcard_terms, self._h, pattern, max_out)
+
+    def wildcard_terms_batch(self, patterns, max_out=10):
+        """[wildcard_terms(p, max_out) for p in patterns] from one pass over
+        the dictionary per chunk of patterns (tfidf_wildcard_terms_batch)."""
+        return _wildcard_term_lists(_wildcard_terms_arrays(L.load().tfidf_wildcard_terms_batch, self._h, patterns,
+                                                           max_out))
+
+    def search_wildcard(self, pattern: bytes):
+        """(ascending doc ids, n_matched): the live documents holding a term
+        that matches the pattern; every hit scores 1.0, and no clause limit
+        applies (tfidf_search_wildcard)."""
+        return _wildcard_docs_single(L.load().tfidf_search_wildcard, self._h, pattern)
+
+    def search_wildcard_batch_arrays(self, patterns, cap=None):
+        """(doc ids uint32[], hit offsets uint64[n + 1], n_matched uint64[n], ms_device) of tfidf_search_wildcard_batch."""
+        return _wildcard_docs_arrays(L.load().tfidf_search_wildcard_batch, self._h, patterns, cap)
+
+    def search_wildcard_batch(self, patterns):
+        """[search_wildcard(p) for p in patterns] (tfidf_search_wildcard_batch)."""
+        return _wildcard_doc_lists(self.search_wildcard_batch_arrays(patterns))
+
+    def last_wildcard_stats(self):
+        """(dictionary scans, (pattern, term) matches, union chunks) of the
+        last wildcard call on this index or one of its readers
+        (tfidf_last_wildcard_stats)."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        L.check(L.load().tfidf_last_wildcard_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def last_fuzzy_chunks(self):
         """(dictionary scans, candidate chunks) of the last fuzzy lookup on
@@ -991,6 +1127,27 @@ class Reader:
     def fuzzy_terms(self, term: bytes, max_edits=2, prefix_len=0, max_out=10):
         """ShardIndex.fuzzy_terms on this reader's snapshot."""
         return _fuzzy_single(L.load().tfidf_reader_fuzzy_terms, self._h, term, max_edits, prefix_len, max_out)
+
+    def wildcard_terms(self, pattern: bytes, max_out=10):
+        """ShardIndex.wildcard_terms on this reader's snapshot."""
+        return _wildcard_terms_single(L.load().tfidf_reader_wildcard_terms, self._h, pattern, max_out)
+
+    def wildcard_terms_batch(self, patterns, max_out=10):
+        """ShardIndex.wildcard_terms_batch on this reader's snapshot."""
+        return _wildcard_term_lists(_wildcard_terms_arrays(L.load().tfidf_reader_wildcard_terms_batch, self._h,
+                                                           patterns, max_out))
+
+    def search_wildcard(self, pattern: bytes):
+        """ShardIndex.search_wildcard on this reader's snapshot."""
+        return _wildcard_docs_single(L.load().tfidf_reader_search_wildcard, self._h, pattern)
+
+    def search_wildcard_batch_arrays(self, patterns, cap=None):
+        """(doc ids uint32[], hit offsets uint64[n + 1], n_matched uint64[n], ms_device) of tfidf_reader_search_wildcard_batch."""
+        return _wildcard_docs_arrays(L.load().tfidf_reader_search_wildcard_batch, self._h, patterns, cap)
+
+    def search_wildcard_batch(self, patterns):
+        """ShardIndex.search_wildcard_batch on this reader's snapshot."""
+        return _wildcard_doc_lists(self.search_wildcard_batch_arrays(patterns))
 
     def fuzzy_terms_batch_arrays(self, terms, max_edits=2, prefix_len=0, max_out=10):
         """(cand offsets, n_within, term offsets, term blob, df, dist, ms_device) of tfidf_reader_fuzzy_terms_batch."""

@@ -242,6 +242,24 @@ class Worker:
             out = [document_score_info(rd.doc_key(d).decode(), s) for d, s in hits]
         return (corrected if changed else None), out
 
+    # No reference counterpart (QueryParser.escape neutralises '*' and '?'):
+    # the documents holding a term that starts with ``text`` (lower-cased, not
+    # tokenised; its own '*', '?' and '\' are literals), every hit with the
+    # constant score 1.0 in doc id order, in the shape of search_index.
+    def search_prefix(self, text: str):
+        pattern = re.sub(r"([*?\\])", r"\\\1", text).encode() + b"*"
+        with self.index.reader() as rd:
+            docs, _ = rd.search_wildcard(pattern)
+            return [document_score_info(rd.doc_key(d).decode(), 1.0) for d in docs]
+
+    # The type-ahead call: the ``n`` most frequent vocabulary terms that start
+    # with ``prefix`` (df descending, then bytes) -> [(term, df)]
+    def suggest_terms(self, prefix: str, n=10):
+        pattern = re.sub(r"([*?\\])", r"\\\1", prefix).encode() + b"*"
+        with self.index.reader() as rd:
+            terms, _ = rd.wildcard_terms(pattern, n)
+            return [(t.decode("utf-8", errors="replace"), df) for t, df in terms]
+
     # Worker.java:175-186 /worker/process: any exception -> empty list
     def process_documents(self, search_query: str):
         try:
