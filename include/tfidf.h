@@ -599,6 +599,35 @@ int tfidf_search_phrase(tfidf_index *ix, const uint8_t *p, uint64_t p_len, uint3
                         uint32_t *freqs, uint64_t cap, uint64_t *n_out);
 int tfidf_reader_search_phrase(tfidf_reader *rd, const uint8_t *p, uint64_t p_len, uint32_t *doc_ids, float *scores,
                                uint32_t *freqs, uint64_t cap, uint64_t *n_out);
+/* ---- sloppy phrase search: PhraseQuery with slop > 0 (DESIGN.md section 2,
+ * "Sloppy phrases") ----
+ * tfidf_search_phrase_batch with a slop per phrase (slops[n_p]; values above
+ * INT32_MAX behave as INT32_MAX) and a float frequency.  Analysis, candidates,
+ * statistics, weight, order, limits and the output protocol are those of the
+ * exact calls.  slop = 0: the exact rule, repeated terms allowed; hits, order
+ * and score bits are tfidf_search_phrase_batch's, freq is the count as a float.
+ * One term, any slop: the hits and score bits of tfidf_search(term, k = 0),
+ * freq = tf.  slop > 0 and m >= 2: Lucene 9.8's SloppyPhraseMatcher for a
+ * phrase without a repeated term: freq is the float sum, in match order, of
+ * 1 / (1 + matchLength) over the matches of matchLength <= slop, the hits are
+ * the candidates with freq > 0, score = weight - weight / (1 + freq *
+ * cache[norm(d)]) in float.  Limits of this library: with slop > 0, a phrase
+ * that repeats a term (Lucene's repeat groups are not restated) or has more
+ * than 64 terms is TFIDF_E_UNSUPPORTED_QUERY with nothing written; at slop 0
+ * both are served.  A NULL slops with n_p > 0 is TFIDF_E_INVALID_ARG.
+ * tfidf_last_phrase_stats and tfidf_last_search_ms are set as by the exact
+ * calls. */
+int tfidf_search_phrase_slop_batch(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                   const uint32_t *slops, uint32_t n_p, uint32_t *doc_ids, float *scores, float *freqs,
+                                   uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out);
+int tfidf_reader_search_phrase_slop_batch(tfidf_reader *rd, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                          const uint32_t *slops, uint32_t n_p, uint32_t *doc_ids, float *scores,
+                                          float *freqs, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out);
+/* The batch of one phrase. */
+int tfidf_search_phrase_slop(tfidf_index *ix, const uint8_t *p, uint64_t p_len, uint32_t slop, uint32_t *doc_ids,
+                             float *scores, float *freqs, uint64_t cap, uint64_t *n_out);
+int tfidf_reader_search_phrase_slop(tfidf_reader *rd, const uint8_t *p, uint64_t p_len, uint32_t slop,
+                                    uint32_t *doc_ids, float *scores, float *freqs, uint64_t cap, uint64_t *n_out);
 /* Of the last phrase search that ran on this index (any form): the (phrase,
  * document) rows that were scanned and the row chunks they ran in (test and
  * bench instruments). */
@@ -1063,6 +1092,10 @@ int tfidf_node_search_wildcard_batch(tfidf_node *n, const uint8_t *p_utf8, const
 int tfidf_node_search_phrase_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
                                    uint64_t *doc_ids, float *scores, uint32_t *freqs, uint64_t cap,
                                    uint64_t *hit_offsets, uint64_t *n_out);
+/* tfidf_search_phrase_slop_batch over the node, as tfidf_node_search_phrase_batch. */
+int tfidf_node_search_phrase_slop_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                        const uint32_t *slops, uint32_t n_p, uint64_t *doc_ids, float *scores,
+                                        float *freqs, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out);
 /* tfidf_more_like_this_batch over the node, after tfidf_node_commit, in both
  * statistics modes.  Seeds are global ids, routed by doc_base as
  * tfidf_node_doc_key routes them; one >= the node's num_docs is

@@ -12,7 +12,11 @@
 //                  the counting pass reported for its slice
 //   k_ph_freq      one wave per row: the lanes take the row's listed tokens as
 //                  starts (ph_match_at), a wave reduction gives freq
-//   k_ph_score     row -> score, sort key, hit flag (freq >= 1)
+//   k_ph_sloppy_freq  (tfidf_search_phrase_slop*) one wave per row, freq as a
+//                  float: k_ph_freq's count for a row at slop 0 or of one term,
+//                  else the SloppyPhraseMatcher walk, one lane per cursor
+//   k_ph_score     row -> score, sort key, hit flag (freq >= 1); k_ph_score_f
+//                  for the float frequency
 //   k_ph_compact   the hits' keys and row indices, packed by the scanned flags
 //   k_ph_phrase_of sorted hit -> its phrase, the key of the second (stable) pass
 //   k_ph_emit      sorted hit -> (doc, score, freq)
@@ -90,6 +94,126 @@ __global__ void __launch_bounds__(64 * kPhFreqWaves) k_ph_freq(
   if (lane == 0) freq[row] = mine;
 }
 
+// --- sloppy phrases: the float frequency of SloppyPhraseMatcher (phrase_plan.h) ---
+
+__device__ __forceinline__ uint64_t ph_uniform(uint64_t v) {   // a value every lane holds, as a scalar
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v),
+                 hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+  return (uint64_t)hi << 32 | lo;
+}
+
+__device__ __forceinline__ uint64_t ph_wave_min(uint64_t v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
+    v = o < v ? o : v;
+  }
+  return ph_uniform(v);
+}
+
+// the first of a row's n list entries at or after from whose ordinal is j, n
+// when there is none: 64 entries per ballot (from, j wave-uniform)
+__device__ __forceinline__ uint64_t ph_wave_next(const uint32_t *__restrict__ ord, uint64_t n, uint32_t j,
+                                                 uint64_t from, uint32_t lane) {
+  for (; from < n; from += 64) {
+    const uint64_t i = from + lane;
+    const uint64_t b = __ballot(i < n && ord[i] == j);
+    if (b) return from + (uint64_t)(__ffsll((long long)b) - 1);
+  }
+  return n;
+}
+
+// rows [0, n) as k_ph_freq takes them, freq as a float.  A row whose phrase has
+// slop 0 or one term counts ph_match_at starts (the exact rule).  Any other row
+// (2 <= m <= 64 distinct terms, checked on the host) walks ph_sloppy_freq's
+// steps with lane j holding cursor j: the queue is the lanes' keys, pop-min and
+// top are wave minima with the popped lane masked out, end / next / matchLength
+// / freq are wave-uniform, and a cursor advances by a ballot over the 64 list
+// entries after it.
+__global__ void __launch_bounds__(64 * kPhFreqWaves) k_ph_sloppy_freq(
+    const uint64_t *__restrict__ row_off, uint64_t m_base, const uint32_t *__restrict__ pos,
+    const uint32_t *__restrict__ ord, const uint32_t *__restrict__ row_q, const uint32_t *__restrict__ seq,
+    const uint32_t *__restrict__ seq_off, const uint32_t *__restrict__ slop, uint64_t n, float *__restrict__ freq) {
+  const uint64_t row = (uint64_t)blockIdx.x * kPhFreqWaves + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63u;
+  if (row >= n) return;
+  const uint64_t m0 = row_off[row] - m_base, cnt = row_off[row + 1] - row_off[row];
+  const uint32_t q = row_q[row];
+  const uint32_t m = seq_off[q + 1] - seq_off[q];
+  const uint32_t *rp = pos + m0, *ro = ord + m0;
+  if (slop[q] == 0 || m < 2) {
+    const uint32_t *sq = seq + seq_off[q];
+    uint32_t mine = 0;
+    for (uint64_t i = lane; i < cnt; i += 64) mine += ph_match_at(rp, ro, cnt, i, sq, m) ? 1u : 0u;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) mine += (uint32_t)__shfl_xor((int)mine, d, 64);
+    if (lane == 0) freq[row] = (float)mine;
+    return;
+  }
+  if (m > kPhMaxSloppyTerms) {                       // never launched: the host refuses the phrase
+    if (lane == 0) freq[row] = 0.0f;
+    return;
+  }
+  const int64_t max_len = ph_slop(slop[q]);
+  const bool live = lane < m;
+  uint64_t at = cnt;
+  for (uint32_t j = 0; j < m; j++) {
+    const uint64_t f = ph_wave_next(ro, cnt, j, 0, lane);
+    if (lane == j) at = f;
+  }
+  if (__ballot(live && at == cnt)) {                 // a term without a listed token: no match
+    if (lane == 0) freq[row] = 0.0f;
+    return;
+  }
+  uint64_t key = live ? ph_cursor_key((int64_t)rp[at] - lane, lane) : ~0ull;
+  int64_t end = ph_key_position(~ph_wave_min(live ? ~key : ~0ull));   // the greatest live key holds the greatest position
+  uint64_t top = ph_wave_min(key);
+  uint32_t pp = (uint32_t)(top & 0xFFu);
+  int64_t next = ph_key_position(ph_wave_min(lane == pp ? ~0ull : key));
+  int64_t match_length = end - ph_key_position(top);
+  float f = 0.0f;
+  for (;;) {
+    const uint64_t cur = ph_uniform((uint64_t)__shfl((unsigned long long)at, (int)pp, 64));
+    const uint64_t nx = ph_wave_next(ro, cnt, pp, cur + 1, lane);
+    if (nx == cnt) break;
+    const int64_t p = (int64_t)rp[nx] - pp;
+    if (lane == pp) {
+      at = nx;
+      key = ph_cursor_key(p, pp);
+    }
+    if (p > end) end = p;
+    if (p > next) {
+      if (match_length <= max_len) f = ph_sloppy_add(f, match_length);
+      top = ph_wave_min(key);
+      pp = (uint32_t)(top & 0xFFu);
+      next = ph_key_position(ph_wave_min(lane == pp ? ~0ull : key));
+      match_length = end - ph_key_position(top);
+    } else {
+      const int64_t l = end - p;
+      if (l < match_length) match_length = l;
+    }
+  }
+  if (match_length <= max_len) f = ph_sloppy_add(f, match_length);
+  if (lane == 0) freq[row] = f;
+}
+
+// k_ph_score for a float frequency.  The frequency is never negative, so a row
+// is a hit when its 32-bit word is not 0: k_ph_compact and k_ph_emit carry
+// that word as they carry a count.
+__global__ void __launch_bounds__(256) k_ph_score_f(const float *__restrict__ freq, const uint32_t *__restrict__ docs,
+                                                    const uint32_t *__restrict__ row_q, const float *__restrict__ w,
+                                                    const float *__restrict__ cache, const uint8_t *__restrict__ norm,
+                                                    uint64_t n, uint64_t *__restrict__ key,
+                                                    uint64_t *__restrict__ flag) {
+  const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= n) return;
+  const float f = freq[r];
+  const uint32_t d = docs[r];
+  const float sc = f > 0.0f ? ph_score_f(w[row_q[r]], f, cache[norm[d]]) : 0.0f;
+  key[r] = ph_sort_key(__float_as_uint(sc), d);
+  flag[r] = f > 0.0f ? 1u : 0u;
+}
+
 __global__ void __launch_bounds__(256) k_ph_score(const uint32_t *__restrict__ freq, const uint32_t *__restrict__ docs,
                                                   const uint32_t *__restrict__ row_q, const float *__restrict__ w,
                                                   const float *__restrict__ cache, const uint8_t *__restrict__ norm,
@@ -156,6 +280,24 @@ hipError_t launch_ph_freq(const uint64_t *row_off, uint64_t m_base, const uint32
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_ph_freq, dim3(ph_grid(n, kPhFreqWaves)), dim3(64 * kPhFreqWaves), 0, s, row_off, m_base, pos,
                      ord, row_q, seq, seq_off, n, freq);
+  return hipGetLastError();
+}
+
+hipError_t launch_ph_sloppy_freq(const uint64_t *row_off, uint64_t m_base, const uint32_t *pos, const uint32_t *ord,
+                                 const uint32_t *row_q, const uint32_t *seq, const uint32_t *seq_off,
+                                 const uint32_t *slop, uint64_t n, float *freq, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_ph_sloppy_freq, dim3(ph_grid(n, kPhFreqWaves)), dim3(64 * kPhFreqWaves), 0, s, row_off, m_base,
+                     pos, ord, row_q, seq, seq_off, slop, n, freq);
+  return hipGetLastError();
+}
+
+hipError_t launch_ph_score_f(const float *freq, const uint32_t *docs, const uint32_t *row_q, const float *w,
+                             const float *cache, const uint8_t *norm, uint64_t n, uint64_t *key, uint64_t *flag,
+                             hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_ph_score_f, dim3(ph_grid(n, 256)), dim3(256), 0, s, freq, docs, row_q, w, cache, norm, n, key,
+                     flag);
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
-// phrase_plan.h — the logic of exact phrase search (tfidf_search_phrase*)
-// that the host and the device share: the scan of one slice that numbers every
+// phrase_plan.h — the logic of exact phrase search (tfidf_search_phrase*) and
+// of sloppy phrase search (tfidf_search_phrase_slop*; the last section) that
+// the host and the device share: the scan of one slice that numbers every
 // token and lists those of the phrase, the frequency rule over a row's listed
 // tokens, the score and the ordering key.  Plain C++ (TFIDF_HD; no HIP), so all
 // of it is tested on its own (tests/phrase_check.cpp); kernels_phrase.hip runs
@@ -27,6 +28,7 @@
 namespace tfidf {
 
 constexpr uint32_t kPhMaxTerms = 1024;   // analysed terms of one phrase (kMaxClauseCount)
+constexpr uint32_t kPhMaxSloppyTerms = 64;   // of a phrase searched with slop > 0: one lane of a wave each
 
 // hl_scan_slice that also numbers the tokens: emit(i, k, ordinal) for the i-th
 // listed token, the k-th token of the slice.  Returns the listed tokens, *n_all
@@ -77,6 +79,93 @@ TFIDF_HD bool ph_match_at(const uint32_t *pos, const uint32_t *ord, uint64_t n, 
 // BM25Scorer.score for tf = freq in Java float order (built without FMA contraction)
 TFIDF_HD float ph_score(float w, uint32_t freq, float norm_inverse) {
   const float t = (float)freq * norm_inverse;
+  const float u = 1.0f + t;
+  const float v = w / u;
+  return w - v;
+}
+
+// --- sloppy phrases (tfidf_search_phrase_slop*; Lucene's SloppyPhraseMatcher) ---
+// Only phrases without a repeated term are matched with slop > 0, so the
+// ordinal of a listed token is its phrase position j, and the cursor of j walks
+// the row's list entries of ordinal j with position = token position - j.
+
+// a term stands at two positions of seq[0, m) (ordinals are dense: 0 .. n-1)
+TFIDF_HD bool ph_has_repeat(const uint32_t *seq, uint32_t m) {
+  for (uint32_t j = 0; j < m; j++)
+    if (seq[j] != j) return true;
+  return false;
+}
+
+TFIDF_HD int32_t ph_slop(uint32_t slop) { return slop > 0x7FFFFFFFu ? 0x7FFFFFFF : (int32_t)slop; }
+
+// the queue order of PhraseQueue.lessThan as one ascending key: (position, j);
+// position >= -63 for j < 64
+TFIDF_HD uint64_t ph_cursor_key(int64_t position, uint32_t j) { return (uint64_t)(position + 64) << 8 | j; }
+TFIDF_HD int64_t ph_key_position(uint64_t key) { return (int64_t)(key >> 8) - 64; }
+
+// PhraseScorer's freq += sloppyWeight() for one match, in float
+TFIDF_HD float ph_sloppy_add(float freq, int64_t match_length) {
+  const float d = 1.0f + (float)match_length;
+  const float v = 1.0f / d;
+  return freq + v;
+}
+
+// SloppyPhraseMatcher over one row's listed tokens (n of them: pos ascending,
+// ord) for a phrase of 2 <= m <= 64 distinct terms: the float frequency, the sum
+// of 1 / (1 + matchLength) over the matches of matchLength <= slop in match
+// order.  0 when a term has no listed token.  One thread; k_ph_sloppy_freq
+// walks the same steps with one lane per cursor.
+TFIDF_HD float ph_sloppy_freq(const uint32_t *pos, const uint32_t *ord, uint64_t n, uint32_t m, uint32_t slop) {
+  if (m < 2 || m > kPhMaxSloppyTerms) return 0.0f;
+  const int64_t max_len = ph_slop(slop);
+  uint64_t at[kPhMaxSloppyTerms], key[kPhMaxSloppyTerms];          // per cursor: list index, queue key
+  auto next_of = [&](uint32_t j, uint64_t from) {
+    while (from < n && ord[from] != j) from++;
+    return from;
+  };
+  int64_t end = 0;
+  for (uint32_t j = 0; j < m; j++) {
+    at[j] = next_of(j, 0);
+    if (at[j] == n) return 0.0f;
+    const int64_t p = (int64_t)pos[at[j]] - j;
+    key[j] = ph_cursor_key(p, j);
+    if (j == 0 || p > end) end = p;
+  }
+  // least key of the cursors other than skip (m = none)
+  auto least = [&](uint32_t skip) {
+    uint64_t best = ~0ull;
+    for (uint32_t j = 0; j < m; j++)
+      if (j != skip && key[j] < best) best = key[j];
+    return best;
+  };
+  float freq = 0.0f;
+  uint64_t top = least(m);
+  uint32_t pp = (uint32_t)(top & 0xFFu);
+  int64_t match_length = end - ph_key_position(top), next = ph_key_position(least(pp));
+  for (;;) {
+    at[pp] = next_of(pp, at[pp] + 1);
+    if (at[pp] == n) break;
+    const int64_t p = (int64_t)pos[at[pp]] - pp;
+    key[pp] = ph_cursor_key(p, pp);
+    if (p > end) end = p;
+    if (p > next) {
+      if (match_length <= max_len) freq = ph_sloppy_add(freq, match_length);
+      top = least(m);
+      pp = (uint32_t)(top & 0xFFu);
+      next = ph_key_position(least(pp));
+      match_length = end - ph_key_position(top);
+    } else {
+      const int64_t l = end - p;
+      if (l < match_length) match_length = l;
+    }
+  }
+  if (match_length <= max_len) freq = ph_sloppy_add(freq, match_length);
+  return freq;
+}
+
+// ph_score for a float frequency (built without FMA contraction)
+TFIDF_HD float ph_score_f(float w, float freq, float norm_inverse) {
+  const float t = freq * norm_inverse;
   const float u = 1.0f + t;
   const float v = w / u;
   return w - v;

@@ -20,6 +20,7 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/tfidf.h"
@@ -4075,7 +4076,10 @@ extern "C" int tfidf_reader_search_batch_all(tfidf_reader *rd, const uint8_t *q_
 // ---------------------------------------------------------------------------
 // exact phrase search (phrase_plan.h, kernels_phrase.hip): the documents that
 // hold the phrase's terms next to each other in order, scored by BM25 over the
-// phrase frequency (Lucene's PhraseQuery with slop 0).
+// phrase frequency (Lucene's PhraseQuery with slop 0).  The sloppy calls
+// (tfidf_search_phrase_slop*) take the same path with a slop per phrase: they
+// differ in the frequency kernel (k_ph_sloppy_freq, a float frequency) and the
+// score kernel, nothing else.
 //
 // Per call: the phrases are analysed and looked up on the host, one upload
 // carries their key segments, ordinal sequences and weights.  Per all-hits chunk
@@ -4102,11 +4106,20 @@ struct PhrasePrep {
 
 // analysed, deduplicated and looked up; a phrase without work (no term, not
 // UTF-8, a term this snapshot lacks) keeps work == false
-static int phrase_prepare(Snapshot &S, StatsView &V, const uint8_t *p, uint64_t n, uint32_t index, PhrasePrep *pp) {
+// slop > 0: a phrase of several terms must have at most kPhMaxSloppyTerms, all different
+static int phrase_prepare(Snapshot &S, StatsView &V, const uint8_t *p, uint64_t n, uint32_t index, uint32_t slop,
+                          PhrasePrep *pp) {
   std::vector<std::string> toks;
   if (!analyze(p, n, &toks)) return TFIDF_OK;
   if (toks.size() > kPhMaxTerms)
     return fail(TFIDF_E_INVALID_ARG, "phrase %u has %zu terms (more than %u)", index, toks.size(), kPhMaxTerms);
+  if (slop > 0 && toks.size() > 1) {
+    if (toks.size() > kPhMaxSloppyTerms)
+      return fail(TFIDF_E_UNSUPPORTED_QUERY, "phrase %u has %zu terms (more than %u) and slop %u", index, toks.size(),
+                  kPhMaxSloppyTerms, slop);
+    if (std::unordered_set<std::string>(toks.begin(), toks.end()).size() != toks.size())
+      return fail(TFIDF_E_UNSUPPORTED_QUERY, "phrase %u repeats a term and has slop %u", index, slop);
+  }
   if (toks.empty() || V.doc_count == 0) return TFIDF_OK;
   std::unordered_map<std::string, uint32_t> ordinal;
   for (const std::string &t : toks) {
@@ -4134,9 +4147,11 @@ static int phrase_prepare(Snapshot &S, StatsView &V, const uint8_t *p, uint64_t 
   return TFIDF_OK;
 }
 
+// slops == nullptr: the exact calls, freqs holds counts; else one slop per
+// phrase and freqs holds float frequencies (4 bytes per hit either way)
 static int phrase_batch_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *p_utf8,
-                           const uint64_t *p_offsets, uint32_t n_p, uint32_t *doc_ids, float *scores, uint32_t *freqs,
-                           uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out) {
+                           const uint64_t *p_offsets, const uint32_t *slops, uint32_t n_p, uint32_t *doc_ids,
+                           float *scores, uint32_t *freqs, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out) {
   if (n_p && p_offsets[0] != 0) return fail(TFIDF_E_INVALID_ARG, "p_offsets[0] is not 0");
   for (uint32_t i = 0; i < n_p; i++)
     if (p_offsets[i + 1] < p_offsets[i]) return fail(TFIDF_E_INVALID_ARG, "p_offsets decrease at phrase %u", i);
@@ -4144,7 +4159,9 @@ static int phrase_batch_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uin
   DeviceGuard g(ix->cfg.device);                       // slot_term may read a reference occurrence
   std::vector<PhrasePrep> pp(n_p);
   for (uint32_t i = 0; i < n_p; i++)
-    if (int rc = phrase_prepare(S, V, p_utf8 + p_offsets[i], p_offsets[i + 1] - p_offsets[i], i, &pp[i])) return rc;
+    if (int rc = phrase_prepare(S, V, p_utf8 + p_offsets[i], p_offsets[i + 1] - p_offsets[i], i, slops ? slops[i] : 0,
+                                &pp[i]))
+      return rc;
   for (uint32_t i = 0; i <= n_p; i++) hit_offsets[i] = 0;
   *n_out = 0;
   uint64_t n_cand = 0, n_row_chunks = 0;
@@ -4194,22 +4211,25 @@ static int phrase_batch_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uin
   SearchCtx &X = *lease.c;
   const hipStream_t s = lease.stream();
 
-  // one upload: key segments, ordinal sequences, weights
+  // one upload: key segments, ordinal sequences, weights, slops
   const size_t in_soff = up16(((size_t)n_p + 1) * 4), in_w = up16(in_soff + ((size_t)n_p + 1) * 4),
                in_seq = up16(in_w + (size_t)n_p * 4), in_keys = up16(in_seq + seq.size() * 4),
-               in_end = up16(in_keys + keys.size() * sizeof(HlKey));
+               in_slop = up16(in_keys + keys.size() * sizeof(HlKey)),
+               in_end = up16(in_slop + (slops ? (size_t)n_p * 4 : 0));
   std::vector<uint8_t> h_in(in_end);
   memcpy(h_in.data(), key_off.data(), ((size_t)n_p + 1) * 4);
   memcpy(h_in.data() + in_soff, seq_off.data(), ((size_t)n_p + 1) * 4);
   memcpy(h_in.data() + in_w, w.data(), (size_t)n_p * 4);
   memcpy(h_in.data() + in_seq, seq.data(), seq.size() * 4);
   memcpy(h_in.data() + in_keys, keys.data(), keys.size() * sizeof(HlKey));
+  if (slops) memcpy(h_in.data() + in_slop, slops, (size_t)n_p * 4);
   HIP_TRY(X.ph_in.reserve(in_end));
   uint8_t *pb = X.ph_in.as<uint8_t>();
   if (X.q_timing) HIP_TRY(hipEventRecord(X.ev[QEV_P0], s));
   HIP_TRY(hipMemcpyAsync(pb, h_in.data(), in_end, hipMemcpyHostToDevice, s));
   const uint32_t *d_koff = reinterpret_cast<uint32_t *>(pb), *d_soff = reinterpret_cast<uint32_t *>(pb + in_soff),
-                 *d_seq = reinterpret_cast<uint32_t *>(pb + in_seq);
+                 *d_seq = reinterpret_cast<uint32_t *>(pb + in_seq),
+                 *d_slop = reinterpret_cast<uint32_t *>(pb + in_slop);
   const float *d_w = reinterpret_cast<float *>(pb + in_w);
   const HlKey *d_keys = reinterpret_cast<HlKey *>(pb + in_keys);
   const uint8_t *d_text = S.text->as<uint8_t>();
@@ -4317,9 +4337,17 @@ static int phrase_batch_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uin
         uint64_t *r_key = reinterpret_cast<uint64_t *>(sb), *r_flag = reinterpret_cast<uint64_t *>(sb + s_flag),
                  *c_key = reinterpret_cast<uint64_t *>(sb + s_ckey);
         uint32_t *r_freq = reinterpret_cast<uint32_t *>(sb + s_freq), *c_row = reinterpret_cast<uint32_t *>(sb + s_crow);
-        HIP_TRY(launch_ph_freq(d_row + s0, m_base, m_pos, m_ord, d_rowq + g0, d_seq, d_soff, ns, r_freq, s));
-        HIP_TRY(launch_ph_score(r_freq, d_docs + g0, d_rowq + g0, d_w, V.cache.as<float>(),
-                                S.doc_norm.as<uint8_t>(), ns, r_key, r_flag, s));
+        if (slops) {
+          float *r_freq_f = reinterpret_cast<float *>(r_freq);
+          HIP_TRY(launch_ph_sloppy_freq(d_row + s0, m_base, m_pos, m_ord, d_rowq + g0, d_seq, d_soff, d_slop, ns,
+                                        r_freq_f, s));
+          HIP_TRY(launch_ph_score_f(r_freq_f, d_docs + g0, d_rowq + g0, d_w, V.cache.as<float>(),
+                                    S.doc_norm.as<uint8_t>(), ns, r_key, r_flag, s));
+        } else {
+          HIP_TRY(launch_ph_freq(d_row + s0, m_base, m_pos, m_ord, d_rowq + g0, d_seq, d_soff, ns, r_freq, s));
+          HIP_TRY(launch_ph_score(r_freq, d_docs + g0, d_rowq + g0, d_w, V.cache.as<float>(),
+                                  S.doc_norm.as<uint8_t>(), ns, r_key, r_flag, s));
+        }
         HIP_TRY(exclusive_scan_u64(r_flag, r_flag, ns, s));
         HIP_TRY(launch_ph_compact(r_key, r_freq, r_flag, ns, c_key, c_row, s));
         h_at.resize(ns + 1);
@@ -4415,7 +4443,8 @@ extern "C" int tfidf_search_phrase_batch(tfidf_index *ix, const uint8_t *p_utf8,
   std::shared_ptr<StatsView> view;
   const std::shared_ptr<Snapshot> snap = current(ix, &view);
   if (!snap) return fail(TFIDF_E_STATE, "phrase search before commit");
-  return phrase_batch_on(ix, *snap, *view, p_utf8, p_offsets, n_p, doc_ids, scores, freqs, cap, hit_offsets, n_out);
+  return phrase_batch_on(ix, *snap, *view, p_utf8, p_offsets, nullptr, n_p, doc_ids, scores, freqs, cap, hit_offsets,
+                         n_out);
 }
 
 extern "C" int tfidf_reader_search_phrase_batch(tfidf_reader *rd, const uint8_t *p_utf8, const uint64_t *p_offsets,
@@ -4423,8 +4452,8 @@ extern "C" int tfidf_reader_search_phrase_batch(tfidf_reader *rd, const uint8_t 
                                                 uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out) {
   if (phrase_null_args(rd, p_utf8, p_offsets, n_p, doc_ids, scores, freqs, cap, hit_offsets, n_out))
     return fail(TFIDF_E_INVALID_ARG, "NULL argument");
-  return phrase_batch_on(rd->ix, *rd->S, *rd->V, p_utf8, p_offsets, n_p, doc_ids, scores, freqs, cap, hit_offsets,
-                         n_out);
+  return phrase_batch_on(rd->ix, *rd->S, *rd->V, p_utf8, p_offsets, nullptr, n_p, doc_ids, scores, freqs, cap,
+                         hit_offsets, n_out);
 }
 
 // the single forms: the batch of one phrase
@@ -4442,6 +4471,53 @@ extern "C" int tfidf_reader_search_phrase(tfidf_reader *rd, const uint8_t *p, ui
   const uint64_t offs[2] = {0, p_len};
   uint64_t ho[2];
   return tfidf_reader_search_phrase_batch(rd, p, offs, 1, doc_ids, scores, freqs, cap, ho, n_out);
+}
+
+// the sloppy calls: the exact path with a slop per phrase and float frequencies
+extern "C" int tfidf_search_phrase_slop_batch(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                              const uint32_t *slops, uint32_t n_p, uint32_t *doc_ids, float *scores,
+                                              float *freqs, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out) {
+  if (phrase_null_args(ix, p_utf8, p_offsets, n_p, doc_ids, scores, reinterpret_cast<uint32_t *>(freqs), cap,
+                       hit_offsets, n_out) ||
+      (n_p && !slops))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::shared_ptr<StatsView> view;
+  const std::shared_ptr<Snapshot> snap = current(ix, &view);
+  if (!snap) return fail(TFIDF_E_STATE, "phrase search before commit");
+  const uint32_t none = 0;                             // n_p == 0: slops may be NULL
+  return phrase_batch_on(ix, *snap, *view, p_utf8, p_offsets, slops ? slops : &none, n_p, doc_ids, scores,
+                         reinterpret_cast<uint32_t *>(freqs), cap, hit_offsets, n_out);
+}
+
+extern "C" int tfidf_reader_search_phrase_slop_batch(tfidf_reader *rd, const uint8_t *p_utf8,
+                                                     const uint64_t *p_offsets, const uint32_t *slops, uint32_t n_p,
+                                                     uint32_t *doc_ids, float *scores, float *freqs, uint64_t cap,
+                                                     uint64_t *hit_offsets, uint64_t *n_out) {
+  if (phrase_null_args(rd, p_utf8, p_offsets, n_p, doc_ids, scores, reinterpret_cast<uint32_t *>(freqs), cap,
+                       hit_offsets, n_out) ||
+      (n_p && !slops))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint32_t none = 0;
+  return phrase_batch_on(rd->ix, *rd->S, *rd->V, p_utf8, p_offsets, slops ? slops : &none, n_p, doc_ids, scores,
+                         reinterpret_cast<uint32_t *>(freqs), cap, hit_offsets, n_out);
+}
+
+extern "C" int tfidf_search_phrase_slop(tfidf_index *ix, const uint8_t *p, uint64_t p_len, uint32_t slop,
+                                        uint32_t *doc_ids, float *scores, float *freqs, uint64_t cap,
+                                        uint64_t *n_out) {
+  if (!n_out || (!p && p_len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t offs[2] = {0, p_len};
+  uint64_t ho[2];
+  return tfidf_search_phrase_slop_batch(ix, p, offs, &slop, 1, doc_ids, scores, freqs, cap, ho, n_out);
+}
+
+extern "C" int tfidf_reader_search_phrase_slop(tfidf_reader *rd, const uint8_t *p, uint64_t p_len, uint32_t slop,
+                                               uint32_t *doc_ids, float *scores, float *freqs, uint64_t cap,
+                                               uint64_t *n_out) {
+  if (!n_out || (!p && p_len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t offs[2] = {0, p_len};
+  uint64_t ho[2];
+  return tfidf_reader_search_phrase_slop_batch(rd, p, offs, &slop, 1, doc_ids, scores, freqs, cap, ho, n_out);
 }
 
 extern "C" int tfidf_last_phrase_stats(const tfidf_index *ix, uint64_t *candidates, uint64_t *row_chunks) {

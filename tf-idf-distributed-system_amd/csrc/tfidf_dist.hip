@@ -2417,13 +2417,15 @@ extern "C" int tfidf_node_search_wildcard_batch(tfidf_node *n, const uint8_t *p_
 
 // ---------------------------------------------------------------------------
 // exact phrase search over the node: every shard's ordered hits, merged per
-// phrase by (score descending, global id ascending)
+// phrase by (score descending, global id ascending).  slops == nullptr: the
+// exact call, freqs are counts; else tfidf_search_phrase_slop_batch per shard,
+// freqs are the words of float frequencies.
 
-extern "C" int tfidf_node_search_phrase_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets,
-                                              uint32_t n_p, uint64_t *doc_ids, float *scores, uint32_t *freqs,
-                                              uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out) {
+static int node_phrase_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets, const uint32_t *slops,
+                             bool sloppy, uint32_t n_p, uint64_t *doc_ids, float *scores, uint32_t *freqs,
+                             uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out) {
   if (!n || !hit_offsets || !n_out || (n_p && (!p_offsets || (!p_utf8 && p_offsets[n_p]))) ||
-      (cap && (!doc_ids || !scores || !freqs)))
+      (cap && (!doc_ids || !scores || !freqs)) || (sloppy && n_p && !slops))
     return errf(TFIDF_E_INVALID_ARG, "NULL argument");
   std::lock_guard<std::mutex> lk(n->mu);
   if (!n->committed) return errf(TFIDF_E_STATE, "phrase search before tfidf_node_commit");
@@ -2447,8 +2449,11 @@ extern "C" int tfidf_node_search_phrase_batch(tfidf_node *n, const uint8_t *p_ut
           b.docs.resize(guess);
           b.scores.resize(guess);
           b.freqs.resize(guess);
-          rc = tfidf_search_phrase_batch(ix, p_utf8, p_offsets, n_p, b.docs.data(), b.scores.data(), b.freqs.data(),
-                                         guess, b.off.data(), &total);
+          rc = sloppy ? tfidf_search_phrase_slop_batch(ix, p_utf8, p_offsets, slops, n_p, b.docs.data(),
+                                                       b.scores.data(), reinterpret_cast<float *>(b.freqs.data()),
+                                                       guess, b.off.data(), &total)
+                      : tfidf_search_phrase_batch(ix, p_utf8, p_offsets, n_p, b.docs.data(), b.scores.data(),
+                                                  b.freqs.data(), guess, b.off.data(), &total);
           if (rc != TFIDF_E_BUFFER) break;
           guess = total;
         }
@@ -2482,6 +2487,20 @@ extern "C" int tfidf_node_search_phrase_batch(tfidf_node *n, const uint8_t *p_ut
     }
   }
   return TFIDF_OK;
+}
+
+extern "C" int tfidf_node_search_phrase_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                              uint32_t n_p, uint64_t *doc_ids, float *scores, uint32_t *freqs,
+                                              uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out) {
+  return node_phrase_batch(n, p_utf8, p_offsets, nullptr, false, n_p, doc_ids, scores, freqs, cap, hit_offsets, n_out);
+}
+
+extern "C" int tfidf_node_search_phrase_slop_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                                   const uint32_t *slops, uint32_t n_p, uint64_t *doc_ids,
+                                                   float *scores, float *freqs, uint64_t cap, uint64_t *hit_offsets,
+                                                   uint64_t *n_out) {
+  return node_phrase_batch(n, p_utf8, p_offsets, slops, true, n_p, doc_ids, scores,
+                           reinterpret_cast<uint32_t *>(freqs), cap, hit_offsets, n_out);
 }
 
 // ---------------------------------------------------------------------------

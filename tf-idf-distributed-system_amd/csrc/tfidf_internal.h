@@ -519,6 +519,14 @@ hipError_t launch_ph_freq(const uint64_t *row_off, uint64_t m_base, const uint32
 hipError_t launch_ph_score(const uint32_t *freq, const uint32_t *docs, const uint32_t *row_q, const float *w,
                            const float *cache, const uint8_t *norm, uint64_t n, uint64_t *key, uint64_t *flag,
                            hipStream_t s);
+// sloppy phrases: slop[phrase]; freq as a float (count of the exact rule at slop 0 or for one term)
+hipError_t launch_ph_sloppy_freq(const uint64_t *row_off, uint64_t m_base, const uint32_t *pos, const uint32_t *ord,
+                                 const uint32_t *row_q, const uint32_t *seq, const uint32_t *seq_off,
+                                 const uint32_t *slop, uint64_t n, float *freq, hipStream_t s);
+hipError_t launch_ph_score_f(const float *freq, const uint32_t *docs, const uint32_t *row_q, const float *w,
+                             const float *cache, const uint8_t *norm, uint64_t n, uint64_t *key, uint64_t *flag,
+                             hipStream_t s);
+// freq: a count, or a float frequency's word (never negative: 0 is "no hit" for both); emit copies it
 hipError_t launch_ph_compact(const uint64_t *key, const uint32_t *freq, const uint64_t *at, uint64_t n,
                              uint64_t *o_key, uint32_t *o_row, hipStream_t s);
 hipError_t ph_sort_bytes(size_t *tmp_bytes, uint32_t n);

@@ -177,6 +177,15 @@ SIGNATURES = {
     "tfidf_node_search_phrase_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U64P, F32P, U32P, C.c_uint64,
                                                  U64P, U64P]),
     "tfidf_last_phrase_stats": (C.c_int, [VP, U64P, U64P]),
+    "tfidf_search_phrase_slop_batch": (C.c_int, [VP, C.c_char_p, U64P, U32P, C.c_uint32, U32P, F32P, F32P, C.c_uint64,
+                                                 U64P, U64P]),
+    "tfidf_reader_search_phrase_slop_batch": (C.c_int, [VP, C.c_char_p, U64P, U32P, C.c_uint32, U32P, F32P, F32P,
+                                                        C.c_uint64, U64P, U64P]),
+    "tfidf_search_phrase_slop": (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, U32P, F32P, F32P, C.c_uint64, U64P]),
+    "tfidf_reader_search_phrase_slop": (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, U32P, F32P, F32P, C.c_uint64,
+                                                  U64P]),
+    "tfidf_node_search_phrase_slop_batch": (C.c_int, [VP, C.c_char_p, U64P, U32P, C.c_uint32, U64P, F32P, F32P,
+                                                      C.c_uint64, U64P, U64P]),
     "tfidf_mlt_params_init": (C.c_int, [MLTP]),
     "tfidf_mlt_terms_batch": _MLT_TERMS_SIG,
     "tfidf_reader_mlt_terms_batch": _MLT_TERMS_SIG,

@@ -508,6 +508,14 @@ class Node:
         return E._phrase_lists(*E._phrase_batch_arrays(L.load().tfidf_node_search_phrase_batch, self._h, phrases,
                                                        dtype=np.uint64))
 
+    def search_phrase_slop_batch(self, phrases, slops):
+        """ShardIndex.search_phrase_slop_batch over the node: [[(global doc,
+        score, float freq)]], merged as search_phrase_batch merges
+        (tfidf_node_search_phrase_slop_batch)."""
+        from . import engine as E
+        return E._phrase_lists(*E._phrase_batch_arrays(L.load().tfidf_node_search_phrase_slop_batch, self._h, phrases,
+                                                       dtype=np.uint64, slops=slops))
+
     def more_like_this_batch(self, docs, k=10, exclude_seed=True, **params):
         """ShardIndex.more_like_this_batch over the node: ``docs`` are global
         ids; the owning shard picks a seed's interesting terms, every shard

@@ -389,12 +389,20 @@ def _hit_lists(docs, scores, offs):
     return [list(zip(d[o[i]:o[i + 1]], s[o[i]:o[i + 1]])) for i in range(len(o) - 1)]
 
 
-def _phrase_batch_arrays(fn, handle, phrases, cap=None, dtype=np.uint32):
-    """tfidf_[reader_|node_]search_phrase_batch: one call for the sizes (or with
-    ``cap`` result slots), one more for the payload when that was too small.
-    -> (docs dtype[], scores float32[], freqs uint32[], offsets uint64[n_p + 1])."""
+def _phrase_batch_arrays(fn, handle, phrases, cap=None, dtype=np.uint32, slops=None):
+    """tfidf_[reader_|node_]search_phrase[_slop]_batch: one call for the sizes
+    (or with ``cap`` result slots), one more for the payload when that was too
+    small.  -> (docs dtype[], scores float32[], freqs uint32[], offsets
+    uint64[n_p + 1]); with ``slops`` (one per phrase: the _slop_ calls) freqs is
+    float32[]."""
     n_p = len(phrases)
     blob, offs = _key_arrays(phrases)
+    extra, ft, fct = (), np.uint32, C.c_uint32
+    if slops is not None:
+        slops = np.ascontiguousarray(slops, np.uint32)
+        if slops.shape != (n_p,):
+            raise ValueError("one slop per phrase")
+        extra, ft, fct = (L.ptr(slops, C.c_uint32),), np.float32, C.c_float
     hit_offs = np.zeros(n_p + 1, np.uint64)
     n = C.c_uint64()
     ct = C.c_uint32 if dtype == np.uint32 else C.c_uint64
@@ -402,9 +410,9 @@ def _phrase_batch_arrays(fn, handle, phrases, cap=None, dtype=np.uint32):
     for _ in range(2):
         docs = np.empty(max(cap, 1), dtype)
         scores = np.empty(max(cap, 1), np.float32)
-        freqs = np.empty(max(cap, 1), np.uint32)
-        rc = fn(handle, blob, L.ptr(offs, C.c_uint64), n_p, L.ptr(docs, ct) if cap else None,
-                L.ptr(scores, C.c_float) if cap else None, L.ptr(freqs, C.c_uint32) if cap else None, cap,
+        freqs = np.empty(max(cap, 1), ft)
+        rc = fn(handle, blob, L.ptr(offs, C.c_uint64), *extra, n_p, L.ptr(docs, ct) if cap else None,
+                L.ptr(scores, C.c_float) if cap else None, L.ptr(freqs, fct) if cap else None, cap,
                 L.ptr(hit_offs, C.c_uint64), C.byref(n))
         if rc != L.E_BUFFER:
             break
@@ -418,16 +426,18 @@ def _phrase_lists(docs, scores, freqs, offs):
     return [list(zip(d[o[i]:o[i + 1]], s[o[i]:o[i + 1]], f[o[i]:o[i + 1]])) for i in range(len(o) - 1)]
 
 
-def _phrase_single(fn, handle, phrase):
-    """tfidf_[reader_]search_phrase -> [(doc, score, freq)]."""
+def _phrase_single(fn, handle, phrase, slop=None):
+    """tfidf_[reader_]search_phrase[_slop] -> [(doc, score, freq)]; with
+    ``slop`` (the _slop calls) freq is a float."""
     n = C.c_uint64()
     cap = 0
+    extra, ft, fct = ((), np.uint32, C.c_uint32) if slop is None else ((slop,), np.float32, C.c_float)
     for _ in range(8):                      # as _wildcard_docs_arrays
         docs = np.empty(max(cap, 1), np.uint32)
         scores = np.empty(max(cap, 1), np.float32)
-        freqs = np.empty(max(cap, 1), np.uint32)
-        rc = fn(handle, phrase, len(phrase), L.ptr(docs, C.c_uint32) if cap else None,
-                L.ptr(scores, C.c_float) if cap else None, L.ptr(freqs, C.c_uint32) if cap else None, cap, C.byref(n))
+        freqs = np.empty(max(cap, 1), ft)
+        rc = fn(handle, phrase, len(phrase), *extra, L.ptr(docs, C.c_uint32) if cap else None,
+                L.ptr(scores, C.c_float) if cap else None, L.ptr(freqs, fct) if cap else None, cap, C.byref(n))
         if rc != L.E_BUFFER:
             break
         cap = n.value
@@ -721,6 +731,23 @@ class ShardIndex:
         """[search_phrase(p) for p in phrases] in one pass; a phrase that is
         not UTF-8 has no hits."""
         return _phrase_lists(*self.search_phrase_batch_arrays(phrases))
+
+    def search_phrase_slop(self, phrase: bytes, slop: int):
+        """search_phrase with Lucene's slop (tfidf_search_phrase_slop): [(doc,
+        score, freq)] with the float frequency of SloppyPhraseMatcher, the sum
+        of 1 / (1 + matchLength) over the matches within ``slop``; slop 0 is
+        search_phrase with freq as a float.  With slop > 0 a phrase that
+        repeats a term or has more than 64 terms is E_UNSUPPORTED_QUERY."""
+        return _phrase_single(L.load().tfidf_search_phrase_slop, self._h, phrase, int(slop))
+
+    def search_phrase_slop_batch_arrays(self, phrases, slops, cap=None):
+        """(docs uint32[], scores float32[], freqs float32[], offsets uint64[])
+        of tfidf_search_phrase_slop_batch: phrase i is searched with slops[i]."""
+        return _phrase_batch_arrays(L.load().tfidf_search_phrase_slop_batch, self._h, phrases, cap, slops=slops)
+
+    def search_phrase_slop_batch(self, phrases, slops):
+        """[search_phrase_slop(p, s) for p, s in zip(phrases, slops)] in one pass."""
+        return _phrase_lists(*self.search_phrase_slop_batch_arrays(phrases, slops))
 
     def last_phrase_stats(self):
         """(candidate rows scanned, row chunks) of the last phrase search on
@@ -1169,6 +1196,18 @@ class Reader:
     def search_phrase_batch(self, phrases):
         """ShardIndex.search_phrase_batch on this reader's snapshot."""
         return _phrase_lists(*self.search_phrase_batch_arrays(phrases))
+
+    def search_phrase_slop(self, phrase: bytes, slop: int):
+        """ShardIndex.search_phrase_slop on this reader's snapshot."""
+        return _phrase_single(L.load().tfidf_reader_search_phrase_slop, self._h, phrase, int(slop))
+
+    def search_phrase_slop_batch_arrays(self, phrases, slops, cap=None):
+        """ShardIndex.search_phrase_slop_batch_arrays on this reader's snapshot."""
+        return _phrase_batch_arrays(L.load().tfidf_reader_search_phrase_slop_batch, self._h, phrases, cap, slops=slops)
+
+    def search_phrase_slop_batch(self, phrases, slops):
+        """ShardIndex.search_phrase_slop_batch on this reader's snapshot."""
+        return _phrase_lists(*self.search_phrase_slop_batch_arrays(phrases, slops))
 
     def more_like_this(self, doc, k=10, exclude_seed=True, **params):
         """ShardIndex.more_like_this on this reader's snapshot."""

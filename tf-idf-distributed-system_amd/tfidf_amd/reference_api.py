@@ -161,6 +161,26 @@ class Worker:
                 out.append(info)
             return out
 
+    # No reference counterpart: search_phrase with Lucene's slop (the words of
+    # ``query`` within ``slop`` position moves of the phrase, in any order once
+    # the slop allows it); "freq" is SloppyPhraseMatcher's float frequency.
+    # With slop > 0 a query that repeats a word or has more than 64 words is a
+    # ValueError.
+    def search_near(self, query: str, slop: int):
+        with self.index.reader() as rd:
+            try:
+                hits = rd.search_phrase_slop(query.encode(), slop)
+            except L.TfidfError as e:
+                if e.code == L.E_UNSUPPORTED_QUERY:
+                    raise ValueError(str(e)) from None
+                raise
+            out = []
+            for d, s, f in hits:
+                info = document_score_info(rd.doc_key(d).decode(), s)
+                info["freq"] = f
+                out.append(info)
+            return out
+
     # No reference counterpart ("contents" has no term vectors, so Lucene's
     # MoreLikeThis.like(docNum) would find no terms there): the ``k``
     # documents most like the document whose key is ``name``, without that

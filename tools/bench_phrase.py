@@ -20,6 +20,13 @@ over --runs timed rounds after --warmup (a round alternates the two routes):
 plus the candidates (phrase, document) scanned, their document bytes, bytes
 scanned per device second and the row chunks of the call.  One JSON file per
 shape under --out-dir, one line per shape on stdout.
+
+--slop N times tfidf_reader_search_phrase_slop_batch with slop N for every
+phrase instead (phrases that repeat a word are not drawn; N = 0 is the exact
+rule through the sloppy call).  The host route stays the exact count: before
+anything is timed its hits must be among the sloppy hits (all of them at N =
+0).  The shapes and files are then named slopN_<shape>, and the JSON says
+"slop": N.
 """
 import argparse
 import ctypes as C
@@ -45,8 +52,9 @@ def spread(xs):
     return {"median": float(np.median(xs)), "min": float(min(xs)), "max": float(max(xs))}
 
 
-def draw_phrases(rd, n, rng):
-    """n phrases of 2 and 3 consecutive tokens of randomly chosen documents -> [(bytes, [terms])]."""
+def draw_phrases(rd, n, rng, distinct=False):
+    """n phrases of 2 and 3 consecutive tokens of randomly chosen documents -> [(bytes, [terms])];
+    distinct: none that repeats a token."""
     out = []
     while len(out) < n:
         toks = analyze(rd.doc_text(rng.randrange(rd.num_docs)))
@@ -54,6 +62,8 @@ def draw_phrases(rd, n, rng):
         if len(toks) < m:
             continue
         at = rng.randrange(len(toks) - m + 1)
+        if distinct and len(set(toks[at:at + m])) < m:
+            continue
         out.append((b" ".join(toks[at:at + m]), toks[at:at + m]))
     return out
 
@@ -83,10 +93,12 @@ def host_route(rd, phrases):
 
 
 class RawPhrase:
-    """tfidf_reader_search_phrase_batch into buffers allocated once."""
+    """tfidf_reader_search_phrase_batch (slop None) or tfidf_reader_search_phrase_slop_batch
+    into buffers allocated once."""
 
-    def __init__(self, rd, phrases):
+    def __init__(self, rd, phrases, slop=None):
         self.rd, self.n_p = rd, len(phrases)
+        self.slops = None if slop is None else np.full(self.n_p, slop, np.uint32)
         self.blob = b"".join(p for p, _ in phrases)
         self.offs = np.zeros(self.n_p + 1, np.uint64)
         self.offs[1:] = np.cumsum([len(p) for p, _ in phrases], dtype=np.uint64)
@@ -99,9 +111,18 @@ class RawPhrase:
 
     def size(self, cap):
         self.cap = cap
-        self.docs, self.scores, self.freqs = np.empty(cap, np.uint32), np.empty(cap, np.float32), np.empty(cap, np.uint32)
+        self.docs, self.scores = np.empty(cap, np.uint32), np.empty(cap, np.float32)
+        self.freqs = np.empty(cap, np.uint32 if self.slops is None else np.float32)
 
     def call(self):
+        if self.slops is not None:
+            rc = L.load().tfidf_reader_search_phrase_slop_batch(
+                self.rd._h, self.blob, L.ptr(self.offs, C.c_uint64), L.ptr(self.slops, C.c_uint32), self.n_p,
+                L.ptr(self.docs, C.c_uint32), L.ptr(self.scores, C.c_float), L.ptr(self.freqs, C.c_float), self.cap,
+                L.ptr(self.hit_offs, C.c_uint64), C.byref(self.n))
+            if rc not in (L.OK, L.E_BUFFER):
+                L.check(rc)
+            return rc
         rc = L.load().tfidf_reader_search_phrase_batch(
             self.rd._h, self.blob, L.ptr(self.offs, C.c_uint64), self.n_p, L.ptr(self.docs, C.c_uint32),
             L.ptr(self.scores, C.c_float), L.ptr(self.freqs, C.c_uint32), self.cap, L.ptr(self.hit_offs, C.c_uint64),
@@ -115,16 +136,19 @@ class RawPhrase:
         return dict(zip(self.docs[a:z].tolist(), self.freqs[a:z].tolist()))
 
 
-def shape(name, g, rd, lens, n_p, n_host, runs, warmup, extra):
+def shape(name, g, rd, lens, n_p, n_host, runs, warmup, extra, slop=None):
     rng = random.Random(SEED + n_p)
-    phrases = draw_phrases(rd, n_p, rng)
+    phrases = draw_phrases(rd, n_p, rng, distinct=slop is not None)
     sub = sorted(rng.sample(range(n_p), min(n_host, n_p)))
     sub_phrases = [phrases[i] for i in sub]
-    raw = RawPhrase(rd, phrases)
+    raw = RawPhrase(rd, phrases, slop)
     # the same hits and frequencies on the subset, before anything is timed
     want, host_cand, host_bytes = host_route(rd, sub_phrases)
     for i, w in zip(sub, want):
-        assert raw.hits(i) == w and w, (name, phrases[i][0])
+        if slop:
+            assert set(w) <= set(raw.hits(i)) and w, (name, phrases[i][0])
+        else:
+            assert raw.hits(i) == w and w, (name, phrases[i][0])
     cand, row_chunks = g.last_phrase_stats()
     # document bytes of the candidates: the conjunctions' hits
     docs, _, _ = rd.search_batch_all_arrays([b" AND ".join(dict.fromkeys(t)) for _, t in phrases])
@@ -155,6 +179,8 @@ def shape(name, g, rd, lens, n_p, n_host, runs, warmup, extra):
     res["host_scan_GBs_wall"] = host_bytes / max(res["host"]["wall_ms"]["median"] * 1e-3, 1e-9) / 1e9
     res["wall_per_phrase_speedup_over_host"] = res["host"]["wall_ms_per_phrase"] / res["device"]["wall_ms_per_phrase"]
     res.update(extra)
+    if slop is not None:
+        res["slop"] = slop
     return res
 
 
@@ -175,10 +201,13 @@ def main():
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out-dir", default=os.path.join(REPO, "profiles", "phrase"))
+    ap.add_argument("--slop", type=int, default=None,
+                    help="time the sloppy call with this slop for every phrase (default: the exact call)")
     ap.add_argument("--skip", default="", help="comma-separated shapes to leave out (cfg2, book)")
     args = ap.parse_args()
     os.makedirs(args.out_dir, exist_ok=True)
     skip = set(args.skip.split(",")) if args.skip else set()
+    pre = "" if args.slop is None else "slop%d_" % args.slop
 
     def emit(res):
         line = json.dumps(res)
@@ -196,7 +225,8 @@ def main():
         extra = {"corpus": "cfg2: %d docs x U[400,600] tokens, V=100000" % n}
         with g.reader() as rd:
             for n_p in [int(x) for x in args.batches.split(",")]:
-                emit(shape("cfg2-phrase-%d" % n_p, g, rd, lens, n_p, args.host_phrases, args.runs, args.warmup, extra))
+                emit(shape(pre + "cfg2-phrase-%d" % n_p, g, rd, lens, n_p, args.host_phrases, args.runs, args.warmup, extra,
+                           args.slop))
         g.close()
         dc.free()
     if "book" not in skip:
@@ -208,8 +238,8 @@ def main():
         lens = doc_lengths(dc)
         extra = {"corpus": "books: %d docs x %d tokens, V=100000" % (nb, T)}
         with g.reader() as rd:
-            emit(shape("book-phrase-%d" % args.book_phrases, g, rd, lens, args.book_phrases, args.host_phrases, args.runs,
-                       args.warmup, extra))
+            emit(shape(pre + "book-phrase-%d" % args.book_phrases, g, rd, lens, args.book_phrases, args.host_phrases,
+                       args.runs, args.warmup, extra, args.slop))
         g.close()
         dc.free()
     return 0
