@@ -569,6 +569,71 @@ int tfidf_reader_search_wildcard(tfidf_reader *rd, const uint8_t *pattern, uint6
  * matches found and the union chunks (0 for the term calls). */
 int tfidf_last_wildcard_stats(const tfidf_index *ix, uint64_t *scan_chunks, uint64_t *matches,
                               uint64_t *union_chunks);
+/* ---- regular-expression search (Lucene's RegexpQuery; DESIGN.md section 2,
+ * "Regular-expression search"; the rules and limits are csrc/regex_plan.h) ----
+ * Pattern: a byte string, not tokenised and not parsed as a query, decoded as
+ *   strict UTF-8 into code points and read by the grammar of Lucene 9.8 RegExp:
+ *   union `|`, intersection `&`, concatenation, the repeats `? * + {n} {n,}
+ *   {n,m}`, complement `~`, classes `[...]` and `[^...]` with ranges, `.` (one
+ *   code point), `#` (the empty language), `@` (any string), `"..."` (literal),
+ *   `()` (the empty string), groups, `\d \D \s \S \w \W` (outside brackets)
+ *   and `\x` (the literal x).  `^` and `$` are literals: there are no anchors
+ *   and no lazy quantifiers.  Unlike the wildcard calls the pattern is NOT
+ *   lower-cased (Lucene does not lower-case it either): the vocabulary is
+ *   lower-case, so "Foo.*" matches nothing.  A pattern that is not strict UTF-8
+ *   matches nothing without failing the call; the empty pattern is the
+ *   empty-string language and matches no term.
+ * Match: the whole vocabulary term (the vocabulary of the fuzzy and wildcard
+ *   calls: local df >= 1) belongs to the pattern's language, over code points.
+ * Errors, with nothing written: a syntax error in any pattern (an unbalanced
+ *   `(`, `[` or `"`, `{` without an integer, a dangling `\`, a repeat with
+ *   nothing before it, an empty alternative, an empty class, a range that runs
+ *   down) answers TFIDF_E_QUERY_SYNTAX; `<` (named automata, numeric
+ *   intervals) and a pattern whose minimal DFA table exceeds 32 KiB
+ *   (kRxMaxTableBytes: at least every DFA of <= 257 states and <= 32 classes)
+ *   or whose compilation exceeds the work limits (Lucene's
+ *   TooComplexToDeterminizeException) answer TFIDF_E_UNSUPPORTED_QUERY.
+ *   tfidf_last_error carries the pattern's index and the byte offset.
+ * The outputs, the CSR layouts, the TFIDF_E_BUFFER / size-query protocol, the
+ *   n_p limits, TFIDF_E_STATE before the first commit, *ms_device and running
+ *   beside readers, tfidf_add_docs and tfidf_commit are those of the wildcard
+ *   twins: tfidf_regex_terms* return the matching terms in (df descending,
+ *   bytes ascending) order, the first max_out (1..1024), n_matched before
+ *   truncation; tfidf_search_regex* the live documents holding any matching
+ *   term, doc id ascending, every hit the constant score 1.0f, no clause
+ *   limit.  Scratch is bounded as for the wildcard calls; the patterns' tables
+ *   are scanned in chunks that fit the kernels' 32 KiB staging area. */
+int tfidf_regex_terms_batch(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                            uint32_t max_out, uint64_t *cand_offsets, uint64_t *n_matched, uint64_t *term_offsets,
+                            uint8_t *terms, uint64_t terms_cap, uint32_t *df, uint64_t cand_cap, uint64_t *n_cands,
+                            uint64_t *n_term_bytes, float *ms_device);
+int tfidf_reader_regex_terms_batch(tfidf_reader *rd, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                                   uint32_t max_out, uint64_t *cand_offsets, uint64_t *n_matched,
+                                   uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *df,
+                                   uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device);
+int tfidf_regex_terms(tfidf_index *ix, const uint8_t *pattern, uint64_t len, uint32_t max_out, uint64_t *n_matched,
+                      uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *df, uint64_t cand_cap,
+                      uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device);
+int tfidf_reader_regex_terms(tfidf_reader *rd, const uint8_t *pattern, uint64_t len, uint32_t max_out,
+                             uint64_t *n_matched, uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap,
+                             uint32_t *df, uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes,
+                             float *ms_device);
+int tfidf_search_regex_batch(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                             uint32_t *doc_ids, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_matched,
+                             uint64_t *n_out, float *ms_device);
+int tfidf_reader_search_regex_batch(tfidf_reader *rd, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                                    uint32_t *doc_ids, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_matched,
+                                    uint64_t *n_out, float *ms_device);
+int tfidf_search_regex(tfidf_index *ix, const uint8_t *pattern, uint64_t len, uint32_t *doc_ids, uint64_t cap,
+                       uint64_t *n_matched, uint64_t *n_out, float *ms_device);
+int tfidf_reader_search_regex(tfidf_reader *rd, const uint8_t *pattern, uint64_t len, uint32_t *doc_ids,
+                              uint64_t cap, uint64_t *n_matched, uint64_t *n_out, float *ms_device);
+/* Of the last regex call that ran on this index (any form): the scans of the
+ * dictionary (one per staged chunk of tables), the (pattern, term) matches
+ * found, the union chunks (0 for the term calls) and the bytes of the DFA
+ * tables the call staged. */
+int tfidf_last_regex_stats(const tfidf_index *ix, uint64_t *scan_chunks, uint64_t *matches, uint64_t *union_chunks,
+                           uint64_t *table_bytes);
 /* ---- exact phrase search (no reference counterpart: Worker.java:225-227
  * escapes the quotes away; DESIGN.md section 2, "Phrase search") ----
  * The phrase bytes are analysed as a whole the way a document is (they are not
@@ -1083,6 +1148,16 @@ int tfidf_node_wildcard_terms_batch(tfidf_node *n, const uint8_t *p_utf8, const 
 int tfidf_node_search_wildcard_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
                                      uint64_t *doc_ids, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_matched,
                                      uint64_t *n_out, float *ms_device);
+/* The regex calls over the node: the shard merge of the wildcard node calls
+ * (df summed over the shards, distinct n_matched, global doc ids).  A pattern
+ * in error fails the call before any shard runs. */
+int tfidf_node_regex_terms_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                                 uint32_t max_out, uint64_t *cand_offsets, uint64_t *n_matched,
+                                 uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint64_t *df,
+                                 uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device);
+int tfidf_node_search_regex_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                                  uint64_t *doc_ids, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_matched,
+                                  uint64_t *n_out, float *ms_device);
 /* tfidf_search_phrase_batch over the node, after tfidf_node_commit, in both
  * statistics modes: every shard with documents runs the batch at once on its
  * own device, doc_ids become global by the shard's doc_base, and the host

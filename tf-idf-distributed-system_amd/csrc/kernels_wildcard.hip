@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include "tfidf_internal.h"
+#include "wave_ops.h"
 #include "wildcard_plan.h"
 
 namespace tfidf {
@@ -62,17 +63,6 @@ __device__ __forceinline__ void wc_flush(const FzScan &a, WcLds &L) {
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < a.n_terms; i += kWcThreads)
     if (L.cnt[i]) atomicAdd(a.counts + i, L.cnt[i]);
-}
-
-// wave-aggregated append: the lanes with `take` get consecutive positions from one atomicAdd
-__device__ __forceinline__ uint32_t wc_wave_pos(uint32_t *cursor, bool take, uint32_t lane) {
-  const uint64_t m = __ballot(take);
-  if (m == 0) return 0;
-  const uint32_t leader = (uint32_t)__builtin_ctzll(m);
-  uint32_t base = 0;
-  if (lane == leader) base = atomicAdd(cursor, (uint32_t)__popcll(m));
-  base = (uint32_t)__shfl((int)base, (int)leader, 64);
-  return base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
 }
 
 // the chunk's patterns against this lane's candidate (have: the lane holds

@@ -28,6 +28,7 @@
 #include "compact_plan.h"
 #include "fuzzy_plan.h"
 #include "wildcard_plan.h"
+#include "regex_plan.h"
 #include "mlt_plan.h"
 #include "phrase_plan.h"
 #include "snippet_plan.h"
@@ -354,6 +355,7 @@ struct SearchCtx {
   DevMem ph_in, ph_s, ph_o, ph_tmp;         // phrase search: phrases' keys / sequences / weights, per-row arrays, ordered hits, sort scratch
   DevMem ml_in, ml_c, ml_tmp;               // more-like-this: staged seeds + row extents + counters, candidates, sort scratch
   DevMem wc_bits, wc_cnt, wc_out, wc_len;   // wildcard union: pattern bitmaps, (pattern, block) counts, doc ids, matched rows' lengths
+  DevMem rx_tab;                            // regex scan: the staged DFA tables of a scan chunk
   PinnedVec<uint32_t> q_host, q_res, q_cand_h;   // q_cand_h: fused single query's block candidates (host merge)
   std::vector<uint64_t> q_merge;
   std::vector<uint32_t> q_units;            // batch scoring units {q, b0, b1, 0} (run_scoring)
@@ -363,7 +365,7 @@ struct SearchCtx {
       : dev(d), q_in(d), q_out(d), cand(d), cand_n(d), out_doc(d), out_score(d), hits(d), hits_n(d), hits_c(d),
         hits_s(d), hits_P(d), ovf(d), hl_in(d), hl_cnt(d), hl_m(d), hl_s(d), hl_o(d), fz_in(d), fz_hs(d), fz_c(d),
         fz_tmp(d), ph_in(d), ph_s(d), ph_o(d), ph_tmp(d), ml_in(d), ml_c(d), ml_tmp(d), wc_bits(d),
-        wc_cnt(d), wc_out(d), wc_len(d) {}
+        wc_cnt(d), wc_out(d), wc_len(d), rx_tab(d) {}
   int init() {
     DeviceGuard g(dev);
     if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess ||
@@ -414,6 +416,7 @@ struct tfidf_index {
   uint64_t last_ph_candidates = 0, last_ph_row_chunks = 0;    // of the last phrase search (ms_mu)
   uint64_t last_mlt_entries = 0, last_mlt_chunks = 0;         // of the last more-like-this call (ms_mu)
   uint64_t last_wc_scan_chunks = 0, last_wc_matches = 0, last_wc_union_chunks = 0;   // of the last wildcard call (ms_mu)
+  uint64_t last_rx_scan_chunks = 0, last_rx_matches = 0, last_rx_union_chunks = 0, last_rx_table_bytes = 0;   // of the last regex call (ms_mu)
 
   // staged corpus (builder)
   std::shared_ptr<DevMem> text, offsets;   // offsets: u64[n_staged + 1]
@@ -3345,43 +3348,79 @@ extern "C" int tfidf_last_fuzzy_chunks(const tfidf_index *ix, uint64_t *scan_chu
 // Every hit of the document route scores 1.0 (Lucene's constant-score rewrite
 // of a multi-term query, boost 1), so no score is returned, and no clause
 // limit applies: the matched terms never become scorer clauses.
+// Regular-expression search (regex_plan.h, kernels_regex.hip) runs the same
+// driver: only the scan step differs (DFA tables staged in a buffer of their
+// own, chunked by their bytes, walked by k_rx_scan / k_rx_hashed).
 
 constexpr uint64_t kWcMatchBudget = 1ull << 22;  // (pattern, term) matches per fill, as kFzCandBudget
 constexpr uint64_t kWcHitBudget = 1ull << 27;    // bitmap bits per union chunk: 16 MiB of bitmaps, <= 512 MiB of doc ids
 static_assert(kWcChunkPatterns <= kFzChunkTerms && kWcChunkElems <= kFzChunkCps, "the staging area of the fuzzy scan holds a pattern chunk");
 
-static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
-                       bool want_docs, uint32_t max_out, WildcardLists *out) {
+// What a matcher brings to the shared driver: its name in messages, the knobs
+// of its budgets, how its staged words are counted and chunked, where they are
+// staged on the device, its two scan kernels and where its stats go.
+struct MultiTermRoute {
+  const char *what, *match_knob, *hit_knob;
+  uint32_t unit_bytes;                      // n_el counts a pattern's staged words in this unit
+  size_t stage_words;                       // words a scan chunk stages at most
+  void (*plan)(const uint32_t *n_el, uint64_t n, std::vector<uint64_t> *cuts);
+  DevMem SearchCtx::*stage;                 // a staging buffer of the route's own (nullptr: the fuzzy scan's element area)
+  hipError_t (*scan)(bool fill, const FzScan &a, int max_grid, hipStream_t s);
+  hipError_t (*scan_hashed)(bool fill, const FzScan &a, const uint8_t *text, uint64_t text_bytes, int max_grid,
+                            hipStream_t s);
+  void (*publish)(tfidf_index *ix, uint64_t scans, uint64_t matches, uint64_t unions, uint64_t staged_bytes);
+};
+static const MultiTermRoute kWildcardRoute = {
+    "wildcard", "TFIDF_WILDCARD_MATCH_BUDGET", "TFIDF_WILDCARD_HIT_BUDGET", 4, kWcChunkElems,
+    [](const uint32_t *n_el, uint64_t n, std::vector<uint64_t> *cuts) { wc_plan_scan_chunks(n_el, n, cuts); },
+    nullptr, launch_wc_scan, launch_wc_hashed,
+    [](tfidf_index *ix, uint64_t scans, uint64_t matches, uint64_t unions, uint64_t) {
+      ix->last_wc_scan_chunks = scans;
+      ix->last_wc_matches = matches;
+      ix->last_wc_union_chunks = unions;
+    }};
+static const MultiTermRoute kRegexRoute = {
+    "regex", "TFIDF_REGEX_MATCH_BUDGET", "TFIDF_REGEX_HIT_BUDGET", 1, kRxStageWords,
+    [](const uint32_t *n_el, uint64_t n, std::vector<uint64_t> *cuts) {
+      rx_plan_scan_chunks(n_el, n, hl_budget("TFIDF_REGEX_TABLE_BUDGET", kRxStageBytes), cuts);
+    },
+    &SearchCtx::rx_tab, launch_rx_scan, launch_rx_hashed,      // the fuzzy scan's element area is too small for tables
+    [](tfidf_index *ix, uint64_t scans, uint64_t matches, uint64_t unions, uint64_t staged_bytes) {
+      ix->last_rx_scan_chunks = scans;
+      ix->last_rx_matches = matches;
+      ix->last_rx_union_chunks = unions;
+      ix->last_rx_table_bytes = staged_bytes;
+    }};
+
+// els[i]: what pattern i stages for its scan (empty: a pattern that matches
+// nothing): wildcard elements or the words of a DFA table.
+static int multiterm_on(tfidf_index *ix, Snapshot &S, const std::vector<std::vector<uint32_t>> &els, uint32_t n_p,
+                        const MultiTermRoute &R, bool want_docs, uint32_t max_out, WildcardLists *out) {
+  const char *const what = R.what;
   out->ms_device = 0.0f;
   out->terms.assign(want_docs ? 0 : n_p, {});
   out->n_matched.assign(n_p, 0);
   out->docs.clear();
   out->hit_off.assign((size_t)n_p + 1, 0);
-  std::vector<std::vector<uint32_t>> els(n_p);
-  std::vector<uint32_t> n_el(n_p, 0);
-  uint32_t buf[kWcMaxElems];
+  std::vector<uint32_t> n_el(n_p, 0);          // elements of a wildcard pattern, bytes of a regex table
   bool any = false;
   for (uint32_t i = 0; i < n_p; i++) {
-    const uint64_t len = p_offsets[i + 1] - p_offsets[i];
-    if (len == 0) continue;
-    n_el[i] = wc_parse(p_utf8 + p_offsets[i], len, buf);
-    els[i].assign(buf, buf + n_el[i]);
+    n_el[i] = (uint32_t)(els[i].size() * 4 / R.unit_bytes);
     any = any || n_el[i];
   }
-  uint64_t n_scan = 0, n_match = 0, n_union = 0;
+  uint64_t n_scan = 0, n_match = 0, n_union = 0, n_tab_bytes = 0;
   auto publish = [&](float ms) {
     std::lock_guard<std::mutex> lk(ix->ms_mu);
-    ix->last_wc_scan_chunks = n_scan;
-    ix->last_wc_matches = n_match;
-    ix->last_wc_union_chunks = n_union;
+    R.publish(ix, n_scan, n_match, n_union, n_tab_bytes);
     ix->last_ms_scoring = 0.0f;
     ix->last_ms_total = ms;
   };
   if (!any || S.n_docs == 0 || S.C == 0) { publish(0.0f); return TFIDF_OK; }
   std::vector<uint64_t> cuts;
-  wc_plan_scan_chunks(n_el.data(), n_p, &cuts);
-  const uint64_t budget = std::min<uint64_t>(hl_budget("TFIDF_WILDCARD_MATCH_BUDGET", kWcMatchBudget), 1ull << 30);
-  const uint64_t hit_budget = hl_budget("TFIDF_WILDCARD_HIT_BUDGET", kWcHitBudget);
+  R.plan(n_el.data(), n_p, &cuts);
+  const uint64_t budget = std::min<uint64_t>(hl_budget(R.match_knob, kWcMatchBudget), 1ull << 30);
+  const uint64_t hit_budget = hl_budget(R.hit_knob, kWcHitBudget);
+  const size_t stage_words = R.stage_words;
   const uint32_t nb = (uint32_t)((S.n_docs + kBlockDocs - 1) / kBlockDocs);
   if (!S.term_major && nb != S.n_blocks) return fail(TFIDF_E_STATE, "block count of the snapshot is off");
 
@@ -3403,6 +3442,10 @@ static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, cons
            *d_cnt = reinterpret_cast<uint32_t *>(ib + in_cnt), *d_seg = reinterpret_cast<uint32_t *>(ib + in_seg),
            *d_oo = reinterpret_cast<uint32_t *>(ib + in_oo), *d_take = reinterpret_cast<uint32_t *>(ib + in_take),
            *d_cur = reinterpret_cast<uint32_t *>(ib + in_cur), *d_hsn = d_cur + 1;
+  if (R.stage) {
+    HIP_TRY((X.*R.stage).reserve(R.stage_words * 4));
+    d_cps = (X.*R.stage).as<uint32_t>();
+  }
 
   FzScan a{};
   a.dict = S.dict.as<uint64_t>();
@@ -3413,6 +3456,13 @@ static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, cons
   a.counts = d_cnt;
   a.cursor = d_cur;
   const uint8_t *d_text = S.text->as<uint8_t>();
+  // the scan step of the two matchers
+  auto scan = [&](bool fill, const FzScan &f) {
+    return R.scan(fill, f, max_grid, s);
+  };
+  auto scan_hashed = [&](bool fill, const FzScan &f) {
+    return R.scan_hashed(fill, f, d_text, S.text_bytes, max_grid, s);
+  };
   bool listed = false;                     // the hashed slots are listed by the first counting scan
   uint32_t hs_n = 0;
 
@@ -3440,9 +3490,10 @@ static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, cons
     const uint64_t t0 = cuts[ci], nt = cuts[ci + 1] - t0;
     fz_stage_terms(els, t0, t0 + nt, &st);
     if (st.cps.empty()) continue;                                   // only patterns that match nothing
-    if (nt > kWcChunkPatterns || st.cps.size() > kWcChunkElems)
-      return fail(TFIDF_E_STATE, "wildcard scan chunk over its limits");
+    if (nt > kWcChunkPatterns || st.cps.size() > stage_words)
+      return fail(TFIDF_E_STATE, "%s scan chunk over its limits", what);
     n_scan++;
+    n_tab_bytes += st.cps.size() * 4;
     HIP_TRY(hipMemcpyAsync(d_off, st.off.data(), (nt + 1) * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_cps, st.cps.data(), st.cps.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(d_cnt, 0, nt * 4, s));
@@ -3460,7 +3511,7 @@ static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, cons
       a.hs_count = d_hsn;
       a.hs_cap = (uint32_t)(X.fz_hs.bytes / 4);
     }
-    HIP_TRY(launch_wc_scan(false, a, max_grid, s));
+    HIP_TRY(scan(false, a));
     if (!listed) {
       HIP_TRY(hipMemcpyAsync(&hs_n, d_hsn, 4, hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
@@ -3471,14 +3522,14 @@ static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, cons
         l.n_terms = 0;
         l.hs_list = X.fz_hs.as<uint32_t>();
         l.hs_cap = hs_n;
-        HIP_TRY(launch_wc_scan(false, l, max_grid, s));
+        HIP_TRY(scan(false, l));
       }
       listed = true;
     }
     a.hs_list = X.fz_hs.as<uint32_t>();
     a.hs_count = nullptr;
     a.hs_n = hs_n;
-    HIP_TRY(launch_wc_hashed(false, a, d_text, S.text_bytes, max_grid, s));
+    HIP_TRY(scan_hashed(false, a));
     counts.resize(nt);
     HIP_TRY(hipMemcpyAsync(counts.data(), d_cnt, nt * 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -3512,8 +3563,8 @@ static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, cons
       f.keys = k_in;
       f.slots = s_in;
       f.cap = (uint32_t)T;
-      HIP_TRY(launch_wc_scan(true, f, max_grid, s));
-      HIP_TRY(launch_wc_hashed(true, f, d_text, S.text_bytes, max_grid, s));
+      HIP_TRY(scan(true, f));
+      HIP_TRY(scan_hashed(true, f));
       size_t tmp_bytes = 0;
       HIP_TRY(fz_sort(nullptr, &tmp_bytes, k_in, k_out, s_in, s_out, (uint32_t)T, s));
       HIP_TRY(X.fz_tmp.reserve(tmp_bytes));
@@ -3555,7 +3606,7 @@ static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, cons
           HIP_TRY(hipMemcpyAsync(h_cnt.data(), u.cnt, (n_pb + 1) * 8, hipMemcpyDeviceToHost, s));
           HIP_TRY(hipStreamSynchronize(s));
           const uint64_t H = h_cnt[n_pb];
-          if (H > np * S.n_docs) return fail(TFIDF_E_STATE, "wildcard union counted more hits than documents");
+          if (H > np * S.n_docs) return fail(TFIDF_E_STATE, "%s union counted more hits than documents", what);
           for (uint64_t t = 0; t < np; t++)
             out->hit_off[t0 + a0 + u0 + t + 1] = h_cnt[(t + 1) * nb] - h_cnt[t * nb];
           if (H == 0) continue;
@@ -3583,7 +3634,7 @@ static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, cons
         HIP_TRY(hipStreamSynchronize(s));
         n_take = 0;
         for (uint64_t t = 0; t < na; t++) {
-          if (take[t] > seg[t + 1] - seg[t]) return fail(TFIDF_E_STATE, "wildcard selection past its segment");
+          if (take[t] > seg[t + 1] - seg[t]) return fail(TFIDF_E_STATE, "%s selection past its segment", what);
           oo[t] = (uint32_t)n_take;
           n_take += take[t];
         }
@@ -3603,7 +3654,7 @@ static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, cons
         L.reserve(oo[t + 1] - oo[t]);
         for (uint32_t i = oo[t]; i < oo[t + 1]; i++) {
           if (fz_key_term(h_keys[i]) != t || h_slots[i] >= S.C)
-            return fail(TFIDF_E_STATE, "wildcard match %u of pattern %llu is out of place", i, (unsigned long long)t);
+            return fail(TFIDF_E_STATE, "%s match %u of pattern %llu is out of place", what, i, (unsigned long long)t);
           if (int rc = slot_term(S, h_slots[i], &ts)) return rc;
           L.push_back(FuzzyCand{ts, fz_key_df(h_keys[i]), 0});
         }
@@ -3616,7 +3667,7 @@ static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, cons
     }
   }
   for (uint32_t i = 0; i < n_p; i++) out->hit_off[i + 1] += out->hit_off[i];
-  if (want_docs && out->hit_off[n_p] != out->docs.size()) return fail(TFIDF_E_STATE, "wildcard hit lists are out of step");
+  if (want_docs && out->hit_off[n_p] != out->docs.size()) return fail(TFIDF_E_STATE, "%s hit lists are out of step", what);
   HIP_TRY(hipEventRecord(X.ev[QEV_1], s));
   HIP_TRY(hipStreamSynchronize(s));
   HIP_TRY(hipEventElapsedTime(&out->ms_device, X.ev[QEV_0], X.ev[QEV_1]));
@@ -3624,7 +3675,21 @@ static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, cons
   return TFIDF_OK;
 }
 
-static int wildcard_check_args(const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p) {
+// the wildcard route's parse step
+static int wildcard_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                       bool want_docs, uint32_t max_out, WildcardLists *out) {
+  std::vector<std::vector<uint32_t>> els(n_p);
+  uint32_t buf[kWcMaxElems];
+  for (uint32_t i = 0; i < n_p; i++) {
+    const uint64_t len = p_offsets[i + 1] - p_offsets[i];
+    if (len == 0) continue;
+    const uint32_t n = wc_parse(p_utf8 + p_offsets[i], len, buf);
+    els[i].assign(buf, buf + n);
+  }
+  return multiterm_on(ix, S, els, n_p, kWildcardRoute, want_docs, max_out, out);
+}
+
+static int multiterm_check_args(const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p) {
   if (n_p > kWcMaxPatterns) return fail(TFIDF_E_INVALID_ARG, "more than %u patterns in one call", kWcMaxPatterns);
   if (n_p && (!p_offsets || (!p_utf8 && p_offsets[n_p] != p_offsets[0])))
     return fail(TFIDF_E_INVALID_ARG, "NULL argument");
@@ -3636,24 +3701,60 @@ static int wildcard_check_args(const uint8_t *p_utf8, const uint64_t *p_offsets,
 int tfidf::index_wildcard(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p, bool docs,
                           uint32_t max_out, WildcardLists *out) {
   if (!ix || !out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
-  if (int rc = wildcard_check_args(p_utf8, p_offsets, n_p)) return rc;
+  if (int rc = multiterm_check_args(p_utf8, p_offsets, n_p)) return rc;
   if (max_out > kWcMaxOut) return fail(TFIDF_E_INVALID_ARG, "max_out %u above %u", max_out, kWcMaxOut);
   const std::shared_ptr<Snapshot> snap = current(ix);
   if (!snap) return fail(TFIDF_E_STATE, "wildcard search before commit");
   return wildcard_on(ix, *snap, p_utf8, p_offsets, n_p, docs, max_out, out);
 }
 
+// the regex route's parse step: every pattern to its DFA table (empty: a pattern
+// that matches nothing).  The first pattern in error fails the call.
+int tfidf::regex_compile_all(const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                             std::vector<std::vector<uint32_t>> *tabs) {
+  tabs->assign(n_p, {});
+  for (uint32_t i = 0; i < n_p; i++) {
+    uint64_t err_at = 0;
+    const uint64_t len = p_offsets[i + 1] - p_offsets[i];
+    const int rc = rx_compile(len ? p_utf8 + p_offsets[i] : nullptr, len, &(*tabs)[i], &err_at);
+    if (rc == kRxSyntax)
+      return fail(TFIDF_E_QUERY_SYNTAX, "regex pattern %u: syntax error at byte %llu", i, (unsigned long long)err_at);
+    if (rc == kRxUnsupported)
+      return fail(TFIDF_E_UNSUPPORTED_QUERY,
+                  "regex pattern %u: unsupported at byte %llu ('<', or an automaton over the limits of regex_plan.h)", i,
+                  (unsigned long long)err_at);
+    if (rx_table_matches_nothing((*tabs)[i])) (*tabs)[i].clear();
+  }
+  return TFIDF_OK;
+}
+
+int tfidf::index_regex(tfidf_index *ix, const std::vector<std::vector<uint32_t>> &tabs, bool docs, uint32_t max_out,
+                       WildcardLists *out) {
+  if (!ix || !out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (tabs.size() > kWcMaxPatterns) return fail(TFIDF_E_INVALID_ARG, "more than %u patterns in one call", kWcMaxPatterns);
+  if (max_out > kWcMaxOut) return fail(TFIDF_E_INVALID_ARG, "max_out %u above %u", max_out, kWcMaxOut);
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "regex search before commit");
+  return multiterm_on(ix, *snap, tabs, (uint32_t)tabs.size(), kRegexRoute, docs, max_out, out);
+}
+
 // the CSR output of the term calls: offsets, n_matched and the totals always, the payload when it fits
-static int wildcard_terms_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, const uint64_t *p_offsets,
+// (regex: a pattern in error fails the call before anything is written)
+static int multiterm_terms_on(tfidf_index *ix, Snapshot &S, bool regex, const uint8_t *p_utf8, const uint64_t *p_offsets,
                              uint32_t n_p, uint32_t max_out, uint64_t *cand_offsets, uint64_t *n_matched,
                              uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *df,
                              uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device) {
-  if (int rc = wildcard_check_args(p_utf8, p_offsets, n_p)) return rc;
+  if (int rc = multiterm_check_args(p_utf8, p_offsets, n_p)) return rc;
   if (max_out < 1 || max_out > kWcMaxOut) return fail(TFIDF_E_INVALID_ARG, "max_out %u outside 1..%u", max_out, kWcMaxOut);
   if (!cand_offsets || (n_p && !n_matched) || !n_cands || !n_term_bytes) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::vector<std::vector<uint32_t>> tabs;
+  if (regex)
+    if (int rc = regex_compile_all(p_utf8, p_offsets, n_p, &tabs)) return rc;
   if (ms_device) *ms_device = 0.0f;
   WildcardLists wl;
-  if (int rc = wildcard_on(ix, S, p_utf8, p_offsets, n_p, false, max_out, &wl)) return rc;
+  if (int rc = regex ? multiterm_on(ix, S, tabs, n_p, kRegexRoute, false, max_out, &wl)
+                     : wildcard_on(ix, S, p_utf8, p_offsets, n_p, false, max_out, &wl))
+    return rc;
   if (ms_device) *ms_device = wl.ms_device;
   uint64_t nc = 0, nbytes = 0;
   cand_offsets[0] = 0;
@@ -3681,14 +3782,19 @@ static int wildcard_terms_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8
 }
 
 // the output of the document calls: hit_offsets, n_matched and *n_out always, the doc ids when they fit
-static int wildcard_docs_on(tfidf_index *ix, Snapshot &S, const uint8_t *p_utf8, const uint64_t *p_offsets,
+static int multiterm_docs_on(tfidf_index *ix, Snapshot &S, bool regex, const uint8_t *p_utf8, const uint64_t *p_offsets,
                             uint32_t n_p, uint32_t *doc_ids, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_matched,
                             uint64_t *n_out, float *ms_device) {
-  if (int rc = wildcard_check_args(p_utf8, p_offsets, n_p)) return rc;
+  if (int rc = multiterm_check_args(p_utf8, p_offsets, n_p)) return rc;
   if (!hit_offsets || (n_p && !n_matched) || !n_out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::vector<std::vector<uint32_t>> tabs;
+  if (regex)
+    if (int rc = regex_compile_all(p_utf8, p_offsets, n_p, &tabs)) return rc;
   if (ms_device) *ms_device = 0.0f;
   WildcardLists wl;
-  if (int rc = wildcard_on(ix, S, p_utf8, p_offsets, n_p, true, 0, &wl)) return rc;
+  if (int rc = regex ? multiterm_on(ix, S, tabs, n_p, kRegexRoute, true, 0, &wl)
+                     : wildcard_on(ix, S, p_utf8, p_offsets, n_p, true, 0, &wl))
+    return rc;
   if (ms_device) *ms_device = wl.ms_device;
   for (uint32_t i = 0; i < n_p; i++) n_matched[i] = wl.n_matched[i];
   memcpy(hit_offsets, wl.hit_off.data(), ((size_t)n_p + 1) * 8);
@@ -3705,7 +3811,7 @@ extern "C" int tfidf_reader_wildcard_terms_batch(tfidf_reader *rd, const uint8_t
                                                  uint64_t terms_cap, uint32_t *df, uint64_t cand_cap,
                                                  uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device) {
   if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
-  return wildcard_terms_on(rd->ix, *rd->S, p_utf8, p_offsets, n_p, max_out, cand_offsets, n_matched, term_offsets,
+  return multiterm_terms_on(rd->ix, *rd->S, false, p_utf8, p_offsets, n_p, max_out, cand_offsets, n_matched, term_offsets,
                            terms, terms_cap, df, cand_cap, n_cands, n_term_bytes, ms_device);
 }
 
@@ -3715,11 +3821,11 @@ extern "C" int tfidf_wildcard_terms_batch(tfidf_index *ix, const uint8_t *p_utf8
                                           uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes,
                                           float *ms_device) {
   if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
-  if (int rc = wildcard_check_args(p_utf8, p_offsets, n_p)) return rc;
+  if (int rc = multiterm_check_args(p_utf8, p_offsets, n_p)) return rc;
   if (max_out < 1 || max_out > kWcMaxOut) return fail(TFIDF_E_INVALID_ARG, "max_out %u outside 1..%u", max_out, kWcMaxOut);
   const std::shared_ptr<Snapshot> snap = current(ix);
   if (!snap) return fail(TFIDF_E_STATE, "wildcard lookup before commit");
-  return wildcard_terms_on(ix, *snap, p_utf8, p_offsets, n_p, max_out, cand_offsets, n_matched, term_offsets, terms,
+  return multiterm_terms_on(ix, *snap, false, p_utf8, p_offsets, n_p, max_out, cand_offsets, n_matched, term_offsets, terms,
                            terms_cap, df, cand_cap, n_cands, n_term_bytes, ms_device);
 }
 
@@ -3727,7 +3833,7 @@ extern "C" int tfidf_reader_search_wildcard_batch(tfidf_reader *rd, const uint8_
                                                   uint32_t n_p, uint32_t *doc_ids, uint64_t cap, uint64_t *hit_offsets,
                                                   uint64_t *n_matched, uint64_t *n_out, float *ms_device) {
   if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
-  return wildcard_docs_on(rd->ix, *rd->S, p_utf8, p_offsets, n_p, doc_ids, cap, hit_offsets, n_matched, n_out,
+  return multiterm_docs_on(rd->ix, *rd->S, false, p_utf8, p_offsets, n_p, doc_ids, cap, hit_offsets, n_matched, n_out,
                           ms_device);
 }
 
@@ -3735,10 +3841,10 @@ extern "C" int tfidf_search_wildcard_batch(tfidf_index *ix, const uint8_t *p_utf
                                            uint32_t n_p, uint32_t *doc_ids, uint64_t cap, uint64_t *hit_offsets,
                                            uint64_t *n_matched, uint64_t *n_out, float *ms_device) {
   if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
-  if (int rc = wildcard_check_args(p_utf8, p_offsets, n_p)) return rc;
+  if (int rc = multiterm_check_args(p_utf8, p_offsets, n_p)) return rc;
   const std::shared_ptr<Snapshot> snap = current(ix);
   if (!snap) return fail(TFIDF_E_STATE, "wildcard search before commit");
-  return wildcard_docs_on(ix, *snap, p_utf8, p_offsets, n_p, doc_ids, cap, hit_offsets, n_matched, n_out, ms_device);
+  return multiterm_docs_on(ix, *snap, false, p_utf8, p_offsets, n_p, doc_ids, cap, hit_offsets, n_matched, n_out, ms_device);
 }
 
 // the batch of one, without the offsets arrays of the input and of the patterns' lists
@@ -3787,6 +3893,101 @@ extern "C" int tfidf_last_wildcard_stats(const tfidf_index *ix, uint64_t *scan_c
   if (scan_chunks) *scan_chunks = ix->last_wc_scan_chunks;
   if (matches) *matches = ix->last_wc_matches;
   if (union_chunks) *union_chunks = ix->last_wc_union_chunks;
+  return TFIDF_OK;
+}
+
+// ---------------------------------------------------------------------------
+// regular-expression search: the wildcard calls' twins on the regex route
+
+extern "C" int tfidf_reader_regex_terms_batch(tfidf_reader *rd, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                                 uint32_t n_p, uint32_t max_out, uint64_t *cand_offsets,
+                                                 uint64_t *n_matched, uint64_t *term_offsets, uint8_t *terms,
+                                                 uint64_t terms_cap, uint32_t *df, uint64_t cand_cap,
+                                                 uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  return multiterm_terms_on(rd->ix, *rd->S, true, p_utf8, p_offsets, n_p, max_out, cand_offsets, n_matched, term_offsets,
+                           terms, terms_cap, df, cand_cap, n_cands, n_term_bytes, ms_device);
+}
+
+extern "C" int tfidf_regex_terms_batch(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                          uint32_t n_p, uint32_t max_out, uint64_t *cand_offsets, uint64_t *n_matched,
+                                          uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *df,
+                                          uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes,
+                                          float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  if (int rc = multiterm_check_args(p_utf8, p_offsets, n_p)) return rc;
+  if (max_out < 1 || max_out > kWcMaxOut) return fail(TFIDF_E_INVALID_ARG, "max_out %u outside 1..%u", max_out, kWcMaxOut);
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "regex lookup before commit");
+  return multiterm_terms_on(ix, *snap, true, p_utf8, p_offsets, n_p, max_out, cand_offsets, n_matched, term_offsets, terms,
+                           terms_cap, df, cand_cap, n_cands, n_term_bytes, ms_device);
+}
+
+extern "C" int tfidf_reader_search_regex_batch(tfidf_reader *rd, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                                  uint32_t n_p, uint32_t *doc_ids, uint64_t cap, uint64_t *hit_offsets,
+                                                  uint64_t *n_matched, uint64_t *n_out, float *ms_device) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  return multiterm_docs_on(rd->ix, *rd->S, true, p_utf8, p_offsets, n_p, doc_ids, cap, hit_offsets, n_matched, n_out,
+                          ms_device);
+}
+
+extern "C" int tfidf_search_regex_batch(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                           uint32_t n_p, uint32_t *doc_ids, uint64_t cap, uint64_t *hit_offsets,
+                                           uint64_t *n_matched, uint64_t *n_out, float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  if (int rc = multiterm_check_args(p_utf8, p_offsets, n_p)) return rc;
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "regex search before commit");
+  return multiterm_docs_on(ix, *snap, true, p_utf8, p_offsets, n_p, doc_ids, cap, hit_offsets, n_matched, n_out, ms_device);
+}
+
+// the batch of one, without the offsets arrays of the input and of the patterns' lists
+extern "C" int tfidf_reader_regex_terms(tfidf_reader *rd, const uint8_t *pattern, uint64_t len, uint32_t max_out,
+                                           uint64_t *n_matched, uint64_t *term_offsets, uint8_t *terms,
+                                           uint64_t terms_cap, uint32_t *df, uint64_t cand_cap, uint64_t *n_cands,
+                                           uint64_t *n_term_bytes, float *ms_device) {
+  if (!n_matched || (!pattern && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t p_off[2] = {0, len};
+  uint64_t c_off[2];
+  return tfidf_reader_regex_terms_batch(rd, pattern, p_off, 1, max_out, c_off, n_matched, term_offsets, terms,
+                                           terms_cap, df, cand_cap, n_cands, n_term_bytes, ms_device);
+}
+
+extern "C" int tfidf_regex_terms(tfidf_index *ix, const uint8_t *pattern, uint64_t len, uint32_t max_out,
+                                    uint64_t *n_matched, uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap,
+                                    uint32_t *df, uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes,
+                                    float *ms_device) {
+  if (!n_matched || (!pattern && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t p_off[2] = {0, len};
+  uint64_t c_off[2];
+  return tfidf_regex_terms_batch(ix, pattern, p_off, 1, max_out, c_off, n_matched, term_offsets, terms, terms_cap,
+                                    df, cand_cap, n_cands, n_term_bytes, ms_device);
+}
+
+extern "C" int tfidf_reader_search_regex(tfidf_reader *rd, const uint8_t *pattern, uint64_t len, uint32_t *doc_ids,
+                                            uint64_t cap, uint64_t *n_matched, uint64_t *n_out, float *ms_device) {
+  if (!n_matched || (!pattern && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t p_off[2] = {0, len};
+  uint64_t h_off[2];
+  return tfidf_reader_search_regex_batch(rd, pattern, p_off, 1, doc_ids, cap, h_off, n_matched, n_out, ms_device);
+}
+
+extern "C" int tfidf_search_regex(tfidf_index *ix, const uint8_t *pattern, uint64_t len, uint32_t *doc_ids,
+                                     uint64_t cap, uint64_t *n_matched, uint64_t *n_out, float *ms_device) {
+  if (!n_matched || (!pattern && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t p_off[2] = {0, len};
+  uint64_t h_off[2];
+  return tfidf_search_regex_batch(ix, pattern, p_off, 1, doc_ids, cap, h_off, n_matched, n_out, ms_device);
+}
+
+extern "C" int tfidf_last_regex_stats(const tfidf_index *ix, uint64_t *scan_chunks, uint64_t *matches,
+                                      uint64_t *union_chunks, uint64_t *table_bytes) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->ms_mu);
+  if (scan_chunks) *scan_chunks = ix->last_rx_scan_chunks;
+  if (matches) *matches = ix->last_rx_matches;
+  if (union_chunks) *union_chunks = ix->last_rx_union_chunks;
+  if (table_bytes) *table_bytes = ix->last_rx_table_bytes;
   return TFIDF_OK;
 }
 

@@ -2276,25 +2276,28 @@ extern "C" int tfidf_node_fuzzy_terms_batch(tfidf_node *n, const uint8_t *t_utf8
 }
 
 // ---------------------------------------------------------------------------
-// wildcard search over the node: every shard's untruncated term lists merged by
-// term bytes; the shards' ascending hit lists put one after the other
+// wildcard and regex search over the node: every shard's untruncated term lists
+// merged by term bytes; the shards' ascending hit lists put one after the other
 
-static int node_wildcard_run(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p, bool docs,
-                             std::vector<WildcardLists> *sh, std::vector<uint8_t> *ran) {
+// tabs: the compiled tables of a regex call (compiled once for every shard and pass), NULL for a wildcard call
+static int node_multiterm_run(tfidf_node *n, const std::vector<std::vector<uint32_t>> *tabs, const uint8_t *p_utf8,
+                              const uint64_t *p_offsets, uint32_t n_p, bool docs, std::vector<WildcardLists> *sh,
+                              std::vector<uint8_t> *ran) {
   const size_t G = n->shards.size();
   sh->assign(G, {});
   ran->assign(G, 0);
   return n->pool->run([&](uint32_t g) {
     tfidf_index *ix = n->shards[g];
     if (!index_committed(ix) || index_num_docs(ix) == 0) return (int)TFIDF_OK;
-    const int rc = index_wildcard(ix, p_utf8, p_offsets, n_p, docs, 0, &(*sh)[g]);
+    const int rc = tabs ? index_regex(ix, *tabs, docs, 0, &(*sh)[g])
+                        : index_wildcard(ix, p_utf8, p_offsets, n_p, docs, 0, &(*sh)[g]);
     (*ran)[g] = rc == TFIDF_OK;
     return rc;
   });
 }
 
 // pattern i's terms over the shards by term bytes (df summed), in the order of the single index
-static void node_wildcard_merge(const std::vector<WildcardLists> &sh, const std::vector<uint8_t> &ran, uint32_t i,
+static void node_multiterm_merge(const std::vector<WildcardLists> &sh, const std::vector<uint8_t> &ran, uint32_t i,
                                 std::vector<FuzzyCand> *L) {
   std::map<std::string, FuzzyCand> by;
   for (size_t g = 0; g < sh.size(); g++) {
@@ -2313,7 +2316,7 @@ static void node_wildcard_merge(const std::vector<WildcardLists> &sh, const std:
   });
 }
 
-static int node_wildcard_args(const tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p) {
+static int node_multiterm_args(const tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p) {
   if (!n || (n_p && (!p_offsets || (!p_utf8 && p_offsets[n_p] != p_offsets[0]))))
     return errf(TFIDF_E_INVALID_ARG, "NULL argument");
   if (n_p > 65536) return errf(TFIDF_E_INVALID_ARG, "more than 65536 patterns in one call");
@@ -2322,26 +2325,29 @@ static int node_wildcard_args(const tfidf_node *n, const uint8_t *p_utf8, const 
   return TFIDF_OK;
 }
 
-extern "C" int tfidf_node_wildcard_terms_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets,
-                                               uint32_t n_p, uint32_t max_out, uint64_t *cand_offsets,
-                                               uint64_t *n_matched, uint64_t *term_offsets, uint8_t *terms,
-                                               uint64_t terms_cap, uint64_t *df, uint64_t cand_cap, uint64_t *n_cands,
-                                               uint64_t *n_term_bytes, float *ms_device) {
-  if (int rc = node_wildcard_args(n, p_utf8, p_offsets, n_p)) return rc;
+static int node_multiterm_terms(tfidf_node *n, bool regex, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                               uint32_t n_p, uint32_t max_out, uint64_t *cand_offsets, uint64_t *n_matched,
+                               uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint64_t *df,
+                               uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device) {
+  const char *const what = regex ? "regex" : "wildcard";
+  if (int rc = node_multiterm_args(n, p_utf8, p_offsets, n_p)) return rc;
   if (!cand_offsets || (n_p && !n_matched) || !n_cands || !n_term_bytes) return errf(TFIDF_E_INVALID_ARG, "NULL argument");
   if (max_out < 1 || max_out > 1024) return errf(TFIDF_E_INVALID_ARG, "max_out %u outside 1..1024", max_out);
+  std::vector<std::vector<uint32_t>> tabs;       // a pattern in error fails the call before any shard runs
+  if (regex)
+    if (int rc = regex_compile_all(p_utf8, p_offsets, n_p, &tabs)) return rc;
   std::lock_guard<std::mutex> lk(n->mu);
   if (ms_device) *ms_device = 0.0f;
-  if (!n->committed) return errf(TFIDF_E_STATE, "wildcard lookup before tfidf_node_commit");
+  if (!n->committed) return errf(TFIDF_E_STATE, "%s lookup before tfidf_node_commit", what);
   std::vector<WildcardLists> sh;
   std::vector<uint8_t> ran;
-  if (int rc = node_wildcard_run(n, p_utf8, p_offsets, n_p, false, &sh, &ran)) return rc;
+  if (int rc = node_multiterm_run(n, regex ? &tabs : nullptr, p_utf8, p_offsets, n_p, false, &sh, &ran)) return rc;
   std::vector<std::vector<FuzzyCand>> merged(n_p);
   uint64_t nc = 0, nb = 0;
   cand_offsets[0] = 0;
   for (uint32_t i = 0; i < n_p; i++) {
     std::vector<FuzzyCand> &L = merged[i];
-    node_wildcard_merge(sh, ran, i, &L);
+    node_multiterm_merge(sh, ran, i, &L);
     n_matched[i] = L.size();
     if (L.size() > max_out) L.resize(max_out);
     nc += L.size();
@@ -2367,30 +2373,51 @@ extern "C" int tfidf_node_wildcard_terms_batch(tfidf_node *n, const uint8_t *p_u
   return TFIDF_OK;
 }
 
-extern "C" int tfidf_node_search_wildcard_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets,
-                                                uint32_t n_p, uint64_t *doc_ids, uint64_t cap, uint64_t *hit_offsets,
-                                                uint64_t *n_matched, uint64_t *n_out, float *ms_device) {
-  if (int rc = node_wildcard_args(n, p_utf8, p_offsets, n_p)) return rc;
+extern "C" int tfidf_node_wildcard_terms_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                               uint32_t n_p, uint32_t max_out, uint64_t *cand_offsets,
+                                               uint64_t *n_matched, uint64_t *term_offsets, uint8_t *terms,
+                                               uint64_t terms_cap, uint64_t *df, uint64_t cand_cap, uint64_t *n_cands,
+                                               uint64_t *n_term_bytes, float *ms_device) {
+  return node_multiterm_terms(n, false, p_utf8, p_offsets, n_p, max_out, cand_offsets, n_matched, term_offsets, terms,
+                             terms_cap, df, cand_cap, n_cands, n_term_bytes, ms_device);
+}
+
+extern "C" int tfidf_node_regex_terms_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                            uint32_t n_p, uint32_t max_out, uint64_t *cand_offsets,
+                                            uint64_t *n_matched, uint64_t *term_offsets, uint8_t *terms,
+                                            uint64_t terms_cap, uint64_t *df, uint64_t cand_cap, uint64_t *n_cands,
+                                            uint64_t *n_term_bytes, float *ms_device) {
+  return node_multiterm_terms(n, true, p_utf8, p_offsets, n_p, max_out, cand_offsets, n_matched, term_offsets, terms,
+                             terms_cap, df, cand_cap, n_cands, n_term_bytes, ms_device);
+}
+
+static int node_multiterm_docs(tfidf_node *n, bool regex, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                              uint64_t *doc_ids, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_matched,
+                              uint64_t *n_out, float *ms_device) {
+  if (int rc = node_multiterm_args(n, p_utf8, p_offsets, n_p)) return rc;
   if (!hit_offsets || (n_p && !n_matched) || !n_out) return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::vector<std::vector<uint32_t>> tabs;       // a pattern in error fails the call before any shard runs
+  if (regex)
+    if (int rc = regex_compile_all(p_utf8, p_offsets, n_p, &tabs)) return rc;
   std::lock_guard<std::mutex> lk(n->mu);
   if (ms_device) *ms_device = 0.0f;
-  if (!n->committed) return errf(TFIDF_E_STATE, "wildcard search before tfidf_node_commit");
+  if (!n->committed) return errf(TFIDF_E_STATE, "%s search before tfidf_node_commit", regex ? "regex" : "wildcard");
   const size_t G = n->shards.size();
   std::vector<WildcardLists> sh, tsh;
   std::vector<uint8_t> ran, tran;
-  if (int rc = node_wildcard_run(n, p_utf8, p_offsets, n_p, true, &sh, &ran)) return rc;
+  if (int rc = node_multiterm_run(n, regex ? &tabs : nullptr, p_utf8, p_offsets, n_p, true, &sh, &ran)) return rc;
   // the distinct matching terms need the shards' term strings when more than one shard ran
   size_t n_ran = 0;
   for (size_t g = 0; g < G; g++) n_ran += ran[g];
   if (n_ran > 1)
-    if (int rc = node_wildcard_run(n, p_utf8, p_offsets, n_p, false, &tsh, &tran)) return rc;
+    if (int rc = node_multiterm_run(n, regex ? &tabs : nullptr, p_utf8, p_offsets, n_p, false, &tsh, &tran)) return rc;
   std::vector<FuzzyCand> L;
   uint64_t total = 0;
   hit_offsets[0] = 0;
   for (uint32_t i = 0; i < n_p; i++) {
     n_matched[i] = 0;
     if (n_ran > 1) {
-      node_wildcard_merge(tsh, tran, i, &L);
+      node_multiterm_merge(tsh, tran, i, &L);
       n_matched[i] = L.size();
     }
     for (size_t g = 0; g < G; g++) {
@@ -2413,6 +2440,18 @@ extern "C" int tfidf_node_search_wildcard_batch(tfidf_node *n, const uint8_t *p_
       for (uint64_t j = sh[g].hit_off[i]; j < sh[g].hit_off[i + 1]; j++) doc_ids[o++] = n->doc_base[g] + sh[g].docs[j];
     }
   return TFIDF_OK;
+}
+
+extern "C" int tfidf_node_search_wildcard_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                                uint32_t n_p, uint64_t *doc_ids, uint64_t cap, uint64_t *hit_offsets,
+                                                uint64_t *n_matched, uint64_t *n_out, float *ms_device) {
+  return node_multiterm_docs(n, false, p_utf8, p_offsets, n_p, doc_ids, cap, hit_offsets, n_matched, n_out, ms_device);
+}
+
+extern "C" int tfidf_node_search_regex_batch(tfidf_node *n, const uint8_t *p_utf8, const uint64_t *p_offsets,
+                                             uint32_t n_p, uint64_t *doc_ids, uint64_t cap, uint64_t *hit_offsets,
+                                             uint64_t *n_matched, uint64_t *n_out, float *ms_device) {
+  return node_multiterm_docs(n, true, p_utf8, p_offsets, n_p, doc_ids, cap, hit_offsets, n_matched, n_out, ms_device);
 }
 
 // ---------------------------------------------------------------------------

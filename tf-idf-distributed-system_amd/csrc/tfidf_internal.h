@@ -502,6 +502,13 @@ struct WcUnion {
   uint32_t *out;
   uint64_t out_cap;
 };
+// --- regular-expression search (kernels_regex.hip; rules in regex_plan.h) ---
+// The scan takes an FzScan: t_cps holds the words of the patterns' DFA tables,
+// n_terms <= kWcChunkPatterns tables of t_off[n_terms] - t_off[0] <=
+// kRxStageWords words; max_edits and prefix_len are not read.
+hipError_t launch_rx_scan(bool fill, const FzScan &a, int max_grid, hipStream_t s);
+hipError_t launch_rx_hashed(bool fill, const FzScan &a, const uint8_t *text, uint64_t text_bytes, int max_grid,
+                            hipStream_t s);
 hipError_t launch_wc_union_block(const WcUnion &a, hipStream_t s);
 hipError_t launch_wc_rows(const WcUnion &a, uint32_t M, hipStream_t s);
 hipError_t launch_wc_union_term(const WcUnion &a, uint32_t M, uint64_t n_post_bound, int max_grid, hipStream_t s);
@@ -609,6 +616,13 @@ struct WildcardLists {
 };
 int index_wildcard(tfidf_index *ix, const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p, bool docs,
                    uint32_t max_out, WildcardLists *out);
+// the same for regular expressions, from compiled tables (a node compiles once for all its
+// shards).  regex_compile_all: the patterns' DFA tables (empty: matches nothing), or the first
+// pattern's error (TFIDF_E_QUERY_SYNTAX / TFIDF_E_UNSUPPORTED_QUERY).
+int index_regex(tfidf_index *ix, const std::vector<std::vector<uint32_t>> &tabs, bool docs, uint32_t max_out,
+                WildcardLists *out);
+int regex_compile_all(const uint8_t *p_utf8, const uint64_t *p_offsets, uint32_t n_p,
+                      std::vector<std::vector<uint32_t>> *tabs);
 // more-like-this on the snapshot published now: per seed (a committed doc id)
 // its interesting terms in selection order and the candidates before truncation
 struct MltRules;

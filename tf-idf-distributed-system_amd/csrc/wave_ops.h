@@ -33,4 +33,15 @@ __device__ __forceinline__ uint32_t cursor_bump(uint32_t *cur, uint32_t key, uin
   return base + rank;
 }
 
+// Wave-aggregated append (the wildcard and regex scans): the lanes with `take` get consecutive positions from one atomicAdd
+__device__ __forceinline__ uint32_t wc_wave_pos(uint32_t *cursor, bool take, uint32_t lane) {
+  const uint64_t m = __ballot(take);
+  if (m == 0) return 0;
+  const uint32_t leader = (uint32_t)__builtin_ctzll(m);
+  uint32_t base = 0;
+  if (lane == leader) base = atomicAdd(cursor, (uint32_t)__popcll(m));
+  base = (uint32_t)__shfl((int)base, (int)leader, 64);
+  return base + (uint32_t)__popcll(m & ((1ull << lane) - 1));
+}
+
 }  // namespace tfidf

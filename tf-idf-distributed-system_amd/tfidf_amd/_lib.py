@@ -168,6 +168,18 @@ SIGNATURES = {
     "tfidf_search_wildcard": _WILDCARD_DOCS_SINGLE_SIG,
     "tfidf_reader_search_wildcard": _WILDCARD_DOCS_SINGLE_SIG,
     "tfidf_last_wildcard_stats": (C.c_int, [VP, U64P, U64P, U64P]),
+    # the regex calls are shaped exactly like their wildcard twins
+    "tfidf_regex_terms_batch": _wildcard_terms_sig(U32P),
+    "tfidf_reader_regex_terms_batch": _wildcard_terms_sig(U32P),
+    "tfidf_node_regex_terms_batch": _wildcard_terms_sig(U64P),
+    "tfidf_regex_terms": _WILDCARD_TERMS_SINGLE_SIG,
+    "tfidf_reader_regex_terms": _WILDCARD_TERMS_SINGLE_SIG,
+    "tfidf_search_regex_batch": _wildcard_docs_sig(U32P),
+    "tfidf_reader_search_regex_batch": _wildcard_docs_sig(U32P),
+    "tfidf_node_search_regex_batch": _wildcard_docs_sig(U64P),
+    "tfidf_search_regex": _WILDCARD_DOCS_SINGLE_SIG,
+    "tfidf_reader_search_regex": _WILDCARD_DOCS_SINGLE_SIG,
+    "tfidf_last_regex_stats": (C.c_int, [VP, U64P, U64P, U64P, U64P]),
     "tfidf_search_phrase_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U32P, F32P, U32P, C.c_uint64, U64P,
                                             U64P]),
     "tfidf_reader_search_phrase_batch": (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, U32P, F32P, U32P, C.c_uint64,

@@ -500,6 +500,20 @@ class Node:
         return E._wildcard_doc_lists(E._wildcard_docs_arrays(L.load().tfidf_node_search_wildcard_batch, self._h,
                                                              patterns, dtype=np.uint64))
 
+    def regex_terms_batch(self, patterns, max_out=10):
+        """ShardIndex.regex_terms_batch over the node's vocabulary, merged as
+        wildcard_terms_batch merges (tfidf_node_regex_terms_batch)."""
+        from . import engine as E
+        return E._wildcard_term_lists(E._wildcard_terms_arrays(L.load().tfidf_node_regex_terms_batch, self._h,
+                                                               patterns, max_out, df_dtype=np.uint64))
+
+    def search_regex_batch(self, patterns):
+        """ShardIndex.search_regex_batch over the node: [(ascending global doc
+        ids, distinct matching terms)] (tfidf_node_search_regex_batch)."""
+        from . import engine as E
+        return E._wildcard_doc_lists(E._wildcard_docs_arrays(L.load().tfidf_node_search_regex_batch, self._h,
+                                                             patterns, dtype=np.uint64))
+
     def search_phrase_batch(self, phrases):
         """ShardIndex.search_phrase_batch over the node: [[(global doc, score,
         freq)]], every shard's hits merged per phrase by (score desc, global id

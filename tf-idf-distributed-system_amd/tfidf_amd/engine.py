@@ -707,6 +707,43 @@ class ShardIndex:
         L.check(L.load().tfidf_last_wildcard_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def regex_terms(self, pattern: bytes, max_out=10):
+        """([(term bytes, df)], n_matched): the vocabulary terms that belong to
+        the regular expression's language (Lucene's RegExp syntax, matched over
+        code points, the pattern not lower-cased), df descending then bytes;
+        at most max_out (1..1024) of the n_matched there are.  A syntax error
+        raises E_QUERY_SYNTAX, ``<`` or a too complex pattern
+        E_UNSUPPORTED_QUERY (tfidf_regex_terms)."""
+        return _wildcard_terms_single(L.load().tfidf_regex_terms, self._h, pattern, max_out)
+
+    def regex_terms_batch(self, patterns, max_out=10):
+        """[regex_terms(p, max_out) for p in patterns] from one pass over the
+        dictionary per chunk of patterns' tables (tfidf_regex_terms_batch)."""
+        return _wildcard_term_lists(_wildcard_terms_arrays(L.load().tfidf_regex_terms_batch, self._h, patterns,
+                                                           max_out))
+
+    def search_regex(self, pattern: bytes):
+        """(ascending doc ids, n_matched): the live documents holding a term of
+        the pattern's language; every hit scores 1.0, and no clause limit
+        applies (tfidf_search_regex)."""
+        return _wildcard_docs_single(L.load().tfidf_search_regex, self._h, pattern)
+
+    def search_regex_batch_arrays(self, patterns, cap=None):
+        """(doc ids uint32[], hit offsets uint64[n + 1], n_matched uint64[n], ms_device) of tfidf_search_regex_batch."""
+        return _wildcard_docs_arrays(L.load().tfidf_search_regex_batch, self._h, patterns, cap)
+
+    def search_regex_batch(self, patterns):
+        """[search_regex(p) for p in patterns] (tfidf_search_regex_batch)."""
+        return _wildcard_doc_lists(self.search_regex_batch_arrays(patterns))
+
+    def last_regex_stats(self):
+        """(dictionary scans, (pattern, term) matches, union chunks, bytes of
+        staged DFA tables) of the last regex call on this index or one of its
+        readers (tfidf_last_regex_stats)."""
+        a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        L.check(L.load().tfidf_last_regex_stats(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return a.value, b.value, c.value, d.value
+
     def last_fuzzy_chunks(self):
         """(dictionary scans, candidate chunks) of the last fuzzy lookup on
         this index or one of its readers (tfidf_last_fuzzy_chunks)."""
@@ -1175,6 +1212,27 @@ class Reader:
     def search_wildcard_batch(self, patterns):
         """ShardIndex.search_wildcard_batch on this reader's snapshot."""
         return _wildcard_doc_lists(self.search_wildcard_batch_arrays(patterns))
+
+    def regex_terms(self, pattern: bytes, max_out=10):
+        """ShardIndex.regex_terms on this reader's snapshot."""
+        return _wildcard_terms_single(L.load().tfidf_reader_regex_terms, self._h, pattern, max_out)
+
+    def regex_terms_batch(self, patterns, max_out=10):
+        """ShardIndex.regex_terms_batch on this reader's snapshot."""
+        return _wildcard_term_lists(_wildcard_terms_arrays(L.load().tfidf_reader_regex_terms_batch, self._h,
+                                                           patterns, max_out))
+
+    def search_regex(self, pattern: bytes):
+        """ShardIndex.search_regex on this reader's snapshot."""
+        return _wildcard_docs_single(L.load().tfidf_reader_search_regex, self._h, pattern)
+
+    def search_regex_batch_arrays(self, patterns, cap=None):
+        """(doc ids uint32[], hit offsets uint64[n + 1], n_matched uint64[n], ms_device) of tfidf_reader_search_regex_batch."""
+        return _wildcard_docs_arrays(L.load().tfidf_reader_search_regex_batch, self._h, patterns, cap)
+
+    def search_regex_batch(self, patterns):
+        """ShardIndex.search_regex_batch on this reader's snapshot."""
+        return _wildcard_doc_lists(self.search_regex_batch_arrays(patterns))
 
     def fuzzy_terms_batch_arrays(self, terms, max_edits=2, prefix_len=0, max_out=10):
         """(cand offsets, n_within, term offsets, term blob, df, dist, ms_device) of tfidf_reader_fuzzy_terms_batch."""

@@ -272,6 +272,15 @@ class Worker:
             docs, _ = rd.search_wildcard(pattern)
             return [document_score_info(rd.doc_key(d).decode(), 1.0) for d in docs]
 
+    # No reference counterpart: the documents holding a term of the regular
+    # expression's language (Lucene's RegExp syntax; the pattern is not
+    # lower-cased), every hit with the constant score 1.0 in doc id order, in
+    # the shape of search_prefix.  A pattern in error raises TfidfError.
+    def search_regex(self, pattern: str):
+        with self.index.reader() as rd:
+            docs, _ = rd.search_regex(pattern.encode())
+            return [document_score_info(rd.doc_key(d).decode(), 1.0) for d in docs]
+
     # The type-ahead call: the ``n`` most frequent vocabulary terms that start
     # with ``prefix`` (df descending, then bytes) -> [(term, df)]
     def suggest_terms(self, prefix: str, n=10):
