@@ -202,8 +202,23 @@ int tfidf_add_docs_device(tfidf_index *ix, const void *d_utf8, const void *d_off
  *     result is that of a new index given the same documents.  The index may
  *     also be destroyed and created again with a larger vocab_capacity_log2.
  * With a compaction threshold set (tfidf_set_compact_threshold) the commit
- * first reclaims the dead documents when they hold enough of the staged text. */
+ * first reclaims the dead documents when they hold enough of the staged text.
+ * Incremental commits (IndexWriter never analyses a document twice): a
+ *   snapshot remembers which staged documents its term rows and dictionary
+ *   cover.  When the snapshot a commit rebuilds was built from a prefix of the
+ *   same staged corpus — no clear, load, delete, replace-by-key or compaction
+ *   since, no dead document, the same layout, hash seed and debug knobs — the
+ *   commit tokenizes the documents added since only, and rebuilds df, the
+ *   count table and the postings from the rows of all documents.  Any other
+ *   commit (the first build of a snapshot, a seed retry, the commit after a
+ *   failed one) is a full build.  The published index is the same either way,
+ *   bit for bit.  Commits alternate between two snapshots, so a new document is
+ *   tokenized once for each (by two successive commits).
+ * tfidf_commit_tokenized_docs: what the last tfidf_commit tokenized: *docs
+ *   (may be NULL) = documents, *was_full (may be NULL) = 1 for a full build.
+ *   TFIDF_DEBUG=1 TFIDF_FULL_COMMIT=1 forces full builds (A/B runs). */
 int tfidf_commit(tfidf_index *ix);
+int tfidf_commit_tokenized_docs(const tfidf_index *ix, uint64_t *docs, uint32_t *was_full);
 
 /* ---- document lifecycle: delete, reclaim, read back ----
  * tfidf_delete_docs: IndexWriter.deleteDocuments(new Term("path", key)) for

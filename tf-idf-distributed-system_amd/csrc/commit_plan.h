@@ -1,0 +1,110 @@
+// commit_plan.h — the host side of an incremental tfidf_commit: whether the
+// build target's rows and dictionary can be kept (and from which document the
+// tokenizers then start), and how the kept host lists take the new entries.
+// Plain C++ (no HIP), so the decision is tested on its own
+// (tests/commit_plan_check.cpp).
+#pragma once
+
+#include <stdint.h>
+
+#include <algorithm>
+#include <vector>
+
+namespace tfidf {
+
+// Every knob commit_once reads before the inversion, the A/B switch, and
+// TFIDF_TEST_G4_BITS, which the tokenizer launchers read to choose the
+// dictionary's probe form (kept entries must be found by the form that
+// inserted them).  A snapshot's rows are kept only under the knob values they
+// were built with, so a test that re-commits one index under another knob
+// still runs the path it names.
+constexpr int kCommitKnobs = 11;
+inline const char *const *commit_knob_names() {
+  static const char *const names[kCommitKnobs] = {
+      "TFIDF_NO_UNIWAVE", "TFIDF_NO_UNIFIRST",    "TFIDF_PACK_DOCS",  "TFIDF_NO_UCHUNK",       "TFIDF_TEST_PAIR_UNITS",
+      "TFIDF_UW_FULL",    "TFIDF_TEST_WEAK_HASH", "TFIDF_DEBUG_STOP", "TFIDF_WAVE_WGS_PER_CU", "TFIDF_FULL_COMMIT",
+      "TFIDF_TEST_G4_BITS"};
+  return names;
+}
+constexpr int kKnobFullCommit = 9;
+
+// a knob's value as one word: 0 = unset, else FNV-1a of the string with the top bit set
+inline uint64_t knob_sig(const char *v) {
+  if (!v) return 0;
+  uint64_t h = 1469598103934665603ull;
+  for (; *v; v++) h = (h ^ (uint8_t)*v) * 1099511628211ull;
+  return h | (1ull << 63);
+}
+
+// What a snapshot's rows, per-document words and dictionary depend on besides
+// the documents' own text.
+struct CommitSig {
+  uint64_t epoch = 0;        // tfidf_index::corpus_epoch: clear, load, a moving compaction, any live -> dead
+  uint64_t hash_seed = 0;    // KeyBuilder seed the build ran under
+  uint64_t n_dead = 0;       // rows are kept only without dead documents (csr_row_base by staged id == committed id)
+  uint32_t cap_log2 = 0, C = 0, range_shift = 0, R = 0;
+  bool term_major = false;
+  uint64_t knobs[kCommitKnobs] = {};
+};
+
+inline bool commit_sig_equal(const CommitSig &a, const CommitSig &b) {
+  if (a.epoch != b.epoch || a.hash_seed != b.hash_seed || a.n_dead != b.n_dead || a.cap_log2 != b.cap_log2 ||
+      a.C != b.C || a.range_shift != b.range_shift || a.R != b.R || a.term_major != b.term_major)
+    return false;
+  for (int i = 0; i < kCommitKnobs; i++)
+    if (a.knobs[i] != b.knobs[i]) return false;
+  return true;
+}
+
+struct CommitPlan {
+  bool full = true;
+  uint64_t d_first = 0;      // the tokenizers take documents [d_first, n_staged)
+};
+
+// built / tok_docs: the build target's signature and the staged documents its
+// rows cover (0: nothing kept — a new snapshot, or one a failed commit left);
+// now: this commit's, with the seed of its first attempt.  full_knob: the value
+// of TFIDF_FULL_COMMIT (nullptr = unset).
+inline CommitPlan commit_plan(const CommitSig &built, uint64_t tok_docs, const CommitSig &now, uint64_t n_staged,
+                              const char *full_knob) {
+  CommitPlan p;
+  const bool forced = full_knob && *full_knob && !(full_knob[0] == '0' && !full_knob[1]);
+  if (forced || tok_docs == 0 || tok_docs > n_staged || now.n_dead != 0 || built.n_dead != 0 ||
+      !commit_sig_equal(built, now))
+    return p;
+  p.full = false;
+  p.d_first = tok_docs;
+  return p;
+}
+
+// Malformed document ids: the kept ascending list takes the new build's
+// (any order; in practice all above the kept ones) and stays ascending.
+inline void merge_malformed(std::vector<uint32_t> *kept, const uint32_t *fresh, uint64_t n) {
+  const size_t k = kept->size();
+  kept->insert(kept->end(), fresh, fresh + n);
+  std::sort(kept->begin() + k, kept->end());
+  std::inplace_merge(kept->begin(), kept->begin() + k, kept->end());
+}
+
+// CSR escape list: the device counter starts at the kept count, so the new
+// entries land behind the kept sorted ones.  counter = its value after the
+// tokenizers (it keeps counting past cap; entries past cap were not written).
+struct EscAppend {
+  uint64_t first = 0, count = 0;   // new entries: [first, first + count) of the device list
+  bool overflow = false;
+};
+inline EscAppend esc_append_bounds(uint64_t kept, uint64_t counter, uint64_t cap) {
+  EscAppend a;
+  a.first = kept;
+  a.overflow = counter > cap || counter < kept;
+  a.count = a.overflow ? 0 : counter - kept;
+  return a;
+}
+
+// the kept sorted escapes with the new ones behind them (already in list[kept ..]): sorted as a whole
+inline void esc_merge(std::vector<uint64_t> *list, uint64_t kept) {
+  std::sort(list->begin() + std::min<uint64_t>(kept, list->size()), list->end());
+  std::inplace_merge(list->begin(), list->begin() + std::min<uint64_t>(kept, list->size()), list->end());
+}
+
+}  // namespace tfidf

@@ -766,7 +766,7 @@ __device__ __forceinline__ DocMeta unit_meta(const BuildParams &p, uint64_t u, u
     m.np = 1;
     m.ok = true;
   } else {
-    m.d = u * p.pack;
+    m.d = u * p.pack + TFIDF_COLD(first_doc);
     const uint32_t np = (uint32_t)min((uint64_t)p.pack, p.n_docs - m.d);
     const uint32_t j = lane < np ? lane : np - 1;
     // lane j < np: source of document d + j; lanes >= np: one past the last source
@@ -1537,7 +1537,8 @@ __device__ __forceinline__ bool uni_window_prose(uint8_t *text, uint32_t wl, uin
 }
 
 // Units: PACK = false, one document per unit (documents 0..n_docs-1, or the
-// doc_list entries); PACK = true, unit u = documents [u * pack, u * pack + pack)
+// doc_list entries: a pack's retries, or an incremental commit's new
+// documents); PACK = true, unit u = documents [first_doc + u * pack, + pack)
 // sharing one window.  A pack that cannot take the packed path (window or
 // token/term capacity, non-contiguous sources, an empty or non-ASCII document)
 // sends its documents to retry_list for a PACK = false pass.
@@ -1557,7 +1558,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) k_
   init_sel_table(sm.sel, lane);
   unsigned long long my_doc_count = 0, my_ttf = 0, my_nnz = 0;
   uint4 v[4] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
-  const uint64_t n_units = PACK ? (p.n_docs + p.pack - 1) / p.pack : (TFIDF_COLD(doc_list) ? *TFIDF_COLD(doc_list_count) : p.n_docs);
+  // (PACK, first_doc: an incremental commit's packs start at its first new document)
+  const uint64_t n_units = PACK ? (p.n_docs - TFIDF_COLD(first_doc) + p.pack - 1) / p.pack
+                                : (TFIDF_COLD(doc_list) ? *TFIDF_COLD(doc_list_count) : p.n_docs);
   // Units of this workgroup: XCD x (= workgroup mod 8, the dispatch order)
   // takes the contiguous eighth [x, x + 1) * n_units / 8 of the units, so
   // the documents running together on one XCD are neighbours and the CSR
@@ -3059,6 +3062,18 @@ static bool use_g4(const BuildParams &p) {
   uint32_t bits = TFIDF_G4_BITS;
   if (const char *e = knob("TFIDF_TEST_G4_BITS")) bits = (uint32_t)std::max(4, std::min(atoi(e), 32));
   return (uint64_t)p.cap_mask + 1 >= (1ull << bits);
+}
+
+// An incremental commit's new documents first .. first + n - 1 as a doc_list
+// (list[n], *count = n) for the one-document-per-wave pass.
+__global__ void __launch_bounds__(256) k_doc_range(uint32_t *list, uint32_t *count, uint32_t first, uint32_t n) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < n) list[i] = first + i;
+  if (i == 0) *count = n;
+}
+hipError_t launch_doc_range(uint32_t *list, uint32_t *count, uint32_t first, uint32_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_doc_range, dim3((n + 255) / 256 ? (n + 255) / 256 : 1), dim3(256), 0, s, list, count, first, n);
+  return hipGetLastError();
 }
 
 hipError_t launch_tokenize_wave(const BuildParams &p, int grid, hipStream_t s) {

@@ -25,6 +25,7 @@
 
 #include "../../include/tfidf.h"
 #include "analysis.h"
+#include "commit_plan.h"
 #include "compact_plan.h"
 #include "fuzzy_plan.h"
 #include "wildcard_plan.h"
@@ -309,6 +310,11 @@ struct Snapshot {
   std::vector<uint64_t> h_post_esc;    // block-major posting tf escapes, sorted (post_word)
   uint64_t hash_seed = 0;
   uint32_t hash_rebuilds = 0;
+  // incremental commits (commit_plan.h): the staged documents dict, csr,
+  // csr_esc, doc_len, doc_nuniq, doc_norm and rsplit cover, and what those
+  // depend on.  0 while a build is in progress and after one that failed.
+  uint64_t tok_docs = 0;
+  CommitSig sig;
   PinnedVec<uint64_t> h_dict;          // host mirrors for query analysis (pinned)
   PinnedVec<uint32_t> h_df;
   uint64_t doc_count = 0, sum_ttf = 0, nnz = 0, num_terms = 0, long_docs = 0;
@@ -430,6 +436,12 @@ struct tfidf_index {
   std::unordered_map<std::string, uint64_t> key_to_staged;
   uint64_t n_dead = 0;
   uint64_t dead_bytes = 0;             // staged text bytes of the dead documents
+  // bumped whenever a staged document's id, text position or liveness may have
+  // changed (clear, load, a compaction, live -> dead): rows a snapshot keeps
+  // across commits are valid for one epoch only (CommitSig)
+  uint64_t corpus_epoch = 0;
+  uint64_t last_tok_docs = 0;          // documents the last commit's build tokenized (tfidf_commit_tokenized_docs)
+  uint32_t last_tok_full = 1;          // ... and whether it was a full build
   uint64_t next_ord = 0;               // documents staged since create / clear / load: the next keyless key
   uint32_t compact_pct = 0;            // tfidf_set_compact_threshold (0 = commit never compacts)
   uint64_t compactions = 0;            // tfidf_compact calls that reclaimed something (index lifetime)
@@ -439,6 +451,7 @@ struct tfidf_index {
   DevBuf d_live_map;
   DevBuf long_list, uni_list, counters, post_tmp;
   DevBuf retry_list;                   // packed wave path: documents deferred to the single-document pass
+  DevBuf new_list;                     // incremental commit, one document per wave: [0] count, [1 ..] the new documents
   DevBuf bad_list;                     // documents that are not valid UTF-8 (indexed empty)
   uint64_t hash_seed = 0;              // KeyBuilder seed of the build (0 unless a collision was met)
   uint32_t hash_rebuilds = 0;          // builds redone for a hash collision in the last commit
@@ -604,7 +617,7 @@ extern "C" int tfidf_destroy(tfidf_index *ix) {
   ix->ctx_free.clear();
   ix->text.reset();
   ix->offsets.reset();
-  DevBuf *bufs[] = {&ix->d_live_map, &ix->long_list, &ix->uni_list, &ix->counters, &ix->retry_list, &ix->bad_list,
+  DevBuf *bufs[] = {&ix->d_live_map, &ix->long_list, &ix->uni_list, &ix->counters, &ix->retry_list, &ix->new_list, &ix->bad_list,
                     &ix->post_tmp, &ix->lt_keys, &ix->lt_cnt, &ix->lt_g, &ix->lt_pos, &ix->verify_defer, &ix->pairs,
                     &ix->pair_ub, &ix->chunk_list, &ix->chunk_docs, &ix->chunk_fail, &ix->uchunk, &ix->canon_of_slot,
                     &ix->tvals, &ix->term_tmp, &ix->term_esc, &ix->sent_slot, &ix->vcounts, &ix->vnu, &ix->vt_table,
@@ -647,11 +660,36 @@ static int grow_offsets(tfidf_index *ix, uint64_t extra_docs) {
   return grow_shared(ix, &ix->offsets, (ix->n_staged + extra_docs + 1) * 8, (ix->n_staged + 1) * 8, false);
 }
 
+// Grow a buffer a snapshot owns alone (the commit's build target) with its
+// first `keep` bytes kept: an incremental commit appends to the rows of the
+// documents it does not tokenize again.  Geometric, so a shard that commits
+// after every upload copies its rows rarely; keep == 0 is DevBuf::reserve.
+static int grow_keep(tfidf_index *ix, DevMem *buf, uint64_t need, uint64_t keep) {
+  if (!keep || !buf->p) {
+    HIP_TRY(buf->reserve(need));
+    return TFIDF_OK;
+  }
+  if (need <= buf->bytes) return TFIDF_OK;
+  uint64_t cap = buf->bytes;
+  while (cap < need) cap = cap + cap / 2 + (1ull << 20);
+  DevMem nb(buf->dev);
+  if (nb.reserve(cap) != hipSuccess) {          // no room for the slack: the exact size
+    hipGetLastError();
+    HIP_TRY(nb.reserve(need));
+  }
+  HIP_TRY(hipMemcpyAsync(nb.p, buf->p, std::min<uint64_t>(keep, buf->bytes), hipMemcpyDeviceToDevice, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  std::swap(buf->p, nb.p);
+  std::swap(buf->bytes, nb.bytes);
+  return TFIDF_OK;                              // (nb frees the old buffer)
+}
+
 // a staged document goes from live to dead (false: it was dead already)
 static bool kill_staged(tfidf_index *ix, uint64_t st) {
   if (!ix->staged_live[st]) return false;
   ix->staged_live[st] = 0;
   ix->n_dead++;
+  ix->corpus_epoch++;
   ix->dead_bytes += ix->h_offsets[st + 1] - ix->h_offsets[st];
   return true;
 }
@@ -737,6 +775,7 @@ extern "C" int tfidf_clear(tfidf_index *ix) {
   }
   ix->text_bytes = 0;
   ix->n_staged = 0;
+  ix->corpus_epoch++;
   ix->h_offsets.assign(1, 0);
   ix->keys = KeyTable();
   ix->staged_live.clear();
@@ -867,6 +906,7 @@ extern "C" int tfidf_load(tfidf_index *ix, const char *path) {
   {
     std::lock_guard<std::mutex> lk(ix->mu);
     if (ix->n_staged) return fail(TFIDF_E_STATE, "tfidf_load needs an empty index (tfidf_create / tfidf_clear)");
+    ix->corpus_epoch++;
   }
   FILE *f = fopen(path, "rb");
   if (!f) return fail(TFIDF_E_INVALID_ARG, "cannot open %s", path);
@@ -1133,6 +1173,7 @@ static int compact_locked(tfidf_index *ix, uint64_t *bytes_reclaimed, float *ms_
   ix->text_bytes = P.live_bytes;
   ix->n_dead = 0;
   ix->dead_bytes = 0;
+  ix->corpus_epoch++;                  // staged ids and text positions moved
   ix->text = std::move(nt);
   ix->offsets = std::move(no);
   ix->compactions++;
@@ -1218,8 +1259,14 @@ static void set_last_ms(tfidf_index *ix, float scoring, float total) {
 constexpr int kRcCollision = -1000;
 constexpr int kRcNoPublish = -1001;             // TFIDF_DEBUG_STOP (profiling): the rows are incomplete
 constexpr uint32_t kVerifyCap = 1u << 20;      // deferred hashed-key checks per build
-static int commit_once(tfidf_index *ix, Snapshot &S) {
+// may_keep: the first attempt of a commit, which may keep the target's rows
+// and dictionary and tokenize the documents behind them only (commit_plan.h);
+// a seed retry is a full build.
+static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   hipStream_t s = ix->stream;
+  // what the target covers; it covers nothing until this build has succeeded
+  const uint64_t kept_docs = S.tok_docs;
+  S.tok_docs = 0;
   // live documents
   S.n_docs = ix->n_staged - ix->n_dead;
   S.live_map.clear();
@@ -1258,19 +1305,51 @@ static int commit_once(tfidf_index *ix, Snapshot &S) {
   while ((1u << S.range_shift) < RS) S.range_shift++;
   S.R = C >> S.range_shift;
 
-  HIP_TRY(S.dict.reserve((size_t)3 * C * 8));          // lo, hi, reference occurrence (dict_device.h)
+  // Full or incremental.  A document's row sits at csr_row_base of its own
+  // staged id and offset, and its row, doc_len / doc_nuniq / doc_norm / rsplit
+  // words and dictionary entries depend on its text and the signature only:
+  // while the signature holds, the target keeps them and documents
+  // [d_first, N) alone are tokenized.  The inversion below always runs over
+  // all N documents.
+  CommitSig sig;
+  sig.epoch = ix->corpus_epoch;
+  sig.hash_seed = ix->hash_seed;
+  sig.n_dead = ix->n_dead;
+  sig.cap_log2 = ix->cap_log2;
+  sig.C = C;
+  sig.range_shift = S.range_shift;
+  sig.R = S.R;
+  sig.term_major = S.term_major;
+  for (int i = 0; i < kCommitKnobs; i++) sig.knobs[i] = knob_sig(knob(commit_knob_names()[i]));
+  const CommitPlan plan = commit_plan(S.sig, may_keep ? kept_docs : 0, sig, ix->n_staged,
+                                      knob(commit_knob_names()[kKnobFullCommit]));
+  const uint64_t d_first = plan.full ? 0 : plan.d_first;
+  const uint64_t kept_esc = plan.full ? 0 : S.h_esc.size();
+  ix->last_tok_docs = N - d_first;
+  ix->last_tok_full = plan.full ? 1u : 0u;
+  // the kept totals (the tokenizers' counters start at 0 and count the new documents)
+  struct { uint64_t doc_count, sum_ttf, nnz, long_docs, long_chunked, unicode_docs, unicode_wave_docs, pack_retried; } kept{};
+  if (!plan.full)
+    kept = {S.doc_count, S.sum_ttf, S.nnz, S.long_docs, S.long_chunked, S.unicode_docs, S.unicode_wave_docs,
+            S.pack_retried};
+  else
+    S.malformed.clear();
+
+  HIP_TRY(S.dict.reserve((size_t)3 * C * 8));          // lo, hi, reference occurrence (dict_device.h); its size is in the signature
   HIP_TRY(ix->verify_defer.reserve((size_t)kVerifyCap * 16));
   // + 16: the inversion reads row segments in 16-byte pieces, and the piece
   // that holds the last row's last entry may end up to 12 bytes past it
-  HIP_TRY(S.csr.reserve(row_cap * 4 + 16));
+  // (the kept prefixes: the rows, escapes and words of documents below d_first)
+  const uint64_t kept_rows = d_first ? ((ix->h_offsets[d_first] + d_first) >> 1) : 0;   // csr_row_base(d_first)
+  if (int rc = grow_keep(ix, &S.csr, row_cap * 4 + 16, kept_rows * 4)) return rc;
   // escapes: each needs tf >= the field's escape value, and a row holds at
   // most row_cap tokens in all, so this bounds their number
   const uint64_t esc_cap = row_cap / csr_esc_value(S.range_shift) + 64;
-  HIP_TRY(S.csr_esc.reserve(esc_cap * 8));
-  HIP_TRY(S.doc_len.reserve(N * 4 + 4));
-  HIP_TRY(S.doc_nuniq.reserve(N * 4 + 4));
-  HIP_TRY(S.doc_norm.reserve(N + 16));
-  HIP_TRY(S.rsplit.reserve(N * S.R * 4 + 4));
+  if (int rc = grow_keep(ix, &S.csr_esc, esc_cap * 8, kept_esc * 8)) return rc;
+  if (int rc = grow_keep(ix, &S.doc_len, N * 4 + 4, d_first * 4)) return rc;
+  if (int rc = grow_keep(ix, &S.doc_nuniq, N * 4 + 4, d_first * 4)) return rc;
+  if (int rc = grow_keep(ix, &S.doc_norm, N + 16, d_first)) return rc;
+  if (int rc = grow_keep(ix, &S.rsplit, N * S.R * 4 + 4, d_first * S.R * 4)) return rc;
   HIP_TRY(ix->long_list.reserve(N * 4 + 4));
   HIP_TRY(ix->uni_list.reserve(N * 4 + 4));
   HIP_TRY(ix->counters.reserve(128));
@@ -1303,7 +1382,9 @@ static int commit_once(tfidf_index *ix, Snapshot &S) {
   // the wave rules took (k_tokenize_wave<UNI>)
   uint64_t *ctr = ix->counters.as<uint64_t>();
   HIP_TRY(hipMemsetAsync(ix->counters.p, 0, 128, s));
-  HIP_TRY(hipMemsetAsync(S.dict.p, 0, (size_t)3 * C * 8, s));
+  if (plan.full) HIP_TRY(hipMemsetAsync(S.dict.p, 0, (size_t)3 * C * 8, s));
+  // incremental: the escape counter starts behind the kept sorted escapes, so new ones are appended
+  else if (kept_esc) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(ctr + 9), (int)(uint32_t)kept_esc, 1, s));
   // per-document Unicode flags.  UNI-first (the last commit's documents were
   // mostly non-ASCII, one document per wave): every document starts flagged
   // and k_tokenize_wave<UNI> takes ASCII ones as well, so the ASCII pass —
@@ -1312,8 +1393,10 @@ static int commit_once(tfidf_index *ix, Snapshot &S) {
   const char *nouw = knob("TFIDF_NO_UNIWAVE");
   const bool uni_on = !(nouw && *nouw && *nouw != '0');
   const bool uni_first = ix->uni_first && uni_on && pack == 1 && !knob("TFIDF_NO_UNIFIRST");
-  if (uni_first) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ix->uni_list.p, 1u, N, s));
-  else HIP_TRY(hipMemsetAsync(ix->uni_list.p, 0, (size_t)N * 4, s));
+  // (the flag scans read all N flags: those of the kept documents stay 0)
+  if (!uni_first || d_first) HIP_TRY(hipMemsetAsync(ix->uni_list.p, 0, (size_t)N * 4, s));
+  if (uni_first && N > d_first)
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(ix->uni_list.as<uint32_t>() + d_first), 1, N - d_first, s));
 
   BuildParams bp{};
   bp.text = ix->text->as<uint8_t>();
@@ -1351,20 +1434,32 @@ static int commit_once(tfidf_index *ix, Snapshot &S) {
   bp.retry_list = pack > 1 ? ix->retry_list.as<uint32_t>() : nullptr;
   bp.retry_count = reinterpret_cast<uint32_t *>(ctr + 5);
   S.pack_docs = pack;
-  S.pack_retried = 0;
+  S.pack_retried = kept.pack_retried;
 
   HIP_TRY(hipEventRecord(ix->ev[EV_START], s));
-  if (N) {
-    const uint64_t units = (N + pack - 1) / pack;
+  if (N > d_first) {                        // (nothing new: no tokenizer kernel runs)
+    const uint64_t n_new = N - d_first;
+    const uint64_t units = (n_new + pack - 1) / pack;
     uint64_t wpc = kWaveWGsPerCU;
     if (const char *e = knob("TFIDF_WAVE_WGS_PER_CU")) wpc = (uint64_t)std::max(1, atoi(e));   // profiling only
     const uint64_t grid = std::min<uint64_t>(units, (uint64_t)ix->num_cus * wpc);
-    if (!uni_first) HIP_TRY(launch_tokenize_wave(bp, (int)grid, s));
+    // incremental: the packs start at d_first (first_doc); the one-document
+    // pass takes the new documents as a doc_list, as the retry pass takes its
+    bp.first_doc = d_first;
+    if (d_first && pack == 1 && !uni_first) {
+      HIP_TRY(ix->new_list.reserve(n_new * 4 + 8));
+      uint32_t *nl = ix->new_list.as<uint32_t>();
+      HIP_TRY(launch_doc_range(nl + 1, nl, (uint32_t)d_first, (uint32_t)n_new, s));
+      BuildParams np = bp;
+      np.doc_list = nl + 1;
+      np.doc_list_count = nl;
+      HIP_TRY(launch_tokenize_wave(np, (int)grid, s));
+    } else if (!uni_first) HIP_TRY(launch_tokenize_wave(bp, (int)grid, s));
     if (pack > 1 && !bp.debug_stop) {       // documents the packs could not take: one per wave
       uint32_t n_retry = 0;
       HIP_TRY(hipMemcpyAsync(&n_retry, ctr + 5, 4, hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
-      S.pack_retried = n_retry;
+      S.pack_retried = kept.pack_retried + n_retry;
       if (n_retry) {
         BuildParams rp = bp;
         rp.pack = 1;
@@ -1410,10 +1505,10 @@ static int commit_once(tfidf_index *ix, Snapshot &S) {
   HIP_TRY(hipMemcpyAsync(hctr, ctr, 14 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   const uint32_t n_long = (uint32_t)hctr[4], n_uni = (uint32_t)hctr[6];
-  S.long_chunked = 0;
-  S.long_docs = n_long;
-  S.unicode_docs = n_uni + (uint32_t)hctr[13];
-  S.unicode_wave_docs = (uint32_t)hctr[13];
+  S.long_chunked = kept.long_chunked;
+  S.long_docs = kept.long_docs + n_long;
+  S.unicode_docs = kept.unicode_docs + n_uni + (uint32_t)hctr[13];
+  S.unicode_wave_docs = kept.unicode_wave_docs + (uint32_t)hctr[13];
   ix->uni_first = pack == 1 && (uint64_t)S.unicode_docs * 2 > N;
   if (n_long) {
     HIP_TRY(hipEventRecord(ix->ev[EV_L0], s));
@@ -1495,7 +1590,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S) {
     uint32_t n_fb = 0;
     HIP_TRY(hipMemcpyAsync(&n_fb, bp.long_count, 4, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    S.long_chunked = n_long - n_fb;
+    S.long_chunked = kept.long_chunked + n_long - n_fb;
     if (n_fb) {
       uint32_t lg = ix->cap_log2 + 1;
       // table size needed by the longest long document (2x its token bound)
@@ -1534,22 +1629,26 @@ static int commit_once(tfidf_index *ix, Snapshot &S) {
                   ix->cap_log2);
     return fail(TFIDF_E_UNSUPPORTED_INPUT, "index build error flags 0x%x (doc %u)", err, err_doc);
   }
-  S.doc_count = hctr[0];
-  S.sum_ttf = hctr[1];
-  S.nnz = hctr[2];
+  S.doc_count = kept.doc_count + hctr[0];
+  S.sum_ttf = kept.sum_ttf + hctr[1];
+  S.nnz = kept.nnz + hctr[2];
   S.NC = S.term_major ? 0u : (uint32_t)hctr[7];
   if (!S.term_major) HIP_TRY(S.blk.reserve((size_t)(S.n_blocks + 1) * S.NC * 4 + 16));
   // CSR tf escapes (rare: block-major only for tf >= 65 535, the all-ones
   // value of the 16-bit field, csr_esc_value(kRangeBits)): sorted by entry
   // index for the binary searches of the inversion and tfidf_doc_terms
   {
-    const uint64_t n_esc = (uint32_t)hctr[9];
-    if (n_esc > esc_cap) return fail(TFIDF_E_CAPACITY, "CSR escape list overflow");
+    // (incremental: the new escapes were appended behind the kept sorted
+    // ones, which S.h_esc still holds; without new ones the list stands)
+    const EscAppend ea = esc_append_bounds(kept_esc, (uint32_t)hctr[9], esc_cap);
+    if (ea.overflow) return fail(TFIDF_E_CAPACITY, "CSR escape list overflow");
+    const uint64_t n_esc = ea.first + ea.count;
     S.h_esc.resize(n_esc);
-    if (n_esc) {
-      HIP_TRY(hipMemcpyAsync(S.h_esc.data(), S.csr_esc.p, n_esc * 8, hipMemcpyDeviceToHost, s));
+    if (ea.count) {
+      HIP_TRY(hipMemcpyAsync(S.h_esc.data() + ea.first, S.csr_esc.as<uint64_t>() + ea.first, ea.count * 8,
+                             hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
-      std::sort(S.h_esc.begin(), S.h_esc.end());
+      esc_merge(&S.h_esc, ea.first);
       HIP_TRY(hipMemcpyAsync(S.csr_esc.p, S.h_esc.data(), n_esc * 8, hipMemcpyHostToDevice, s));
       HIP_TRY(hipStreamSynchronize(s));
     }
@@ -1730,10 +1829,10 @@ static int commit_once(tfidf_index *ix, Snapshot &S) {
       HIP_TRY(hipMemcpy(S.post_esc.p, S.h_post_esc.data(), n_pe * 8, hipMemcpyHostToDevice));
     }
   }
-  S.malformed.resize((uint32_t)tail[5]);
-  if (!S.malformed.empty()) {
-    HIP_TRY(hipMemcpy(S.malformed.data(), ix->bad_list.p, S.malformed.size() * 4, hipMemcpyDeviceToHost));
-    std::sort(S.malformed.begin(), S.malformed.end());
+  if (const uint32_t n_bad = (uint32_t)tail[5]) {   // (incremental: S.malformed holds the kept documents' ids)
+    std::vector<uint32_t> bad(n_bad);
+    HIP_TRY(hipMemcpy(bad.data(), ix->bad_list.p, (size_t)n_bad * 4, hipMemcpyDeviceToHost));
+    merge_malformed(&S.malformed, bad.data(), n_bad);
   }
   const uint32_t err2 = (uint32_t)tail[0];
   if (err2 & kErrCollision) { ix->collision_doc = (uint32_t)(tail[0] >> 32); return kRcCollision; }
@@ -1760,6 +1859,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S) {
   ix->keys.compact();
   S.keys = ix->keys;                 // shares the chunks; the builder appends to a new one
   S.hash_seed = ix->hash_seed;
+  S.sig = sig;
   {
     std::lock_guard<std::mutex> tl(S.term_mu);
     S.term_cache.clear();
@@ -1776,7 +1876,9 @@ static int commit_once(tfidf_index *ix, Snapshot &S) {
   V.gdf.clear();
   V.doc_count = S.doc_count;
   V.sum_ttf = S.sum_ttf;
-  return upload_cache(ix->cfg, V, s);
+  if (int rc = upload_cache(ix->cfg, V, s)) return rc;
+  S.tok_docs = ix->n_staged;           // the rows and the dictionary cover every staged document
+  return TFIDF_OK;
 }
 
 extern "C" int tfidf_commit(tfidf_index *ix) {
@@ -1804,7 +1906,7 @@ extern "C" int tfidf_commit(tfidf_index *ix) {
   ix->hash_seed = ix->hash_floor ? ix->hash_floor : ((weak && atoi(weak)) ? kWeakHashSeed : 0);
   ix->hash_rebuilds = ix->hash_floor;
   for (uint32_t attempt = ix->hash_floor;; attempt++) {
-    int rc = commit_once(ix, *S);
+    int rc = commit_once(ix, *S, attempt == ix->hash_floor);
     if (rc != TFIDF_OK) {
       hipStreamSynchronize(ix->stream);        // nothing of this build may still run on either stream
       hipStreamSynchronize(ix->copy_stream);
@@ -1838,6 +1940,14 @@ extern "C" int tfidf_set_hash_attempt(tfidf_index *ix, uint32_t attempt) {
   if (attempt > 3) return fail(TFIDF_E_INVALID_ARG, "hash seed attempt %u > 3", attempt);
   std::lock_guard<std::mutex> lk(ix->mu);
   ix->hash_floor = attempt;
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_commit_tokenized_docs(const tfidf_index *ix, uint64_t *docs, uint32_t *was_full) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->mu);
+  if (docs) *docs = ix->last_tok_docs;
+  if (was_full) *was_full = ix->last_tok_full;
   return TFIDF_OK;
 }
 

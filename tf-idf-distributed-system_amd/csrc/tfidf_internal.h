@@ -99,6 +99,11 @@ struct BuildParams {
   // k_tokenize_uchunk (nullptr: such a unit fails its document)
   uint32_t *uchunk_list;
   uint32_t *uchunk_count;
+  // incremental commit: the packed wave path's units start at this document
+  // (the rows and dictionary entries of documents below it are kept; 0 = a
+  // full build; the one-document pass takes a doc_list instead).  Last, so no
+  // other field's kernarg offset moves; read cold.
+  uint64_t first_doc;
 };
 
 __host__ __device__ inline uint64_t csr_row_base(const uint64_t *offsets, uint64_t src) {
@@ -248,6 +253,7 @@ inline void allow_dyn_lds(const void *fn, int bytes, std::atomic<uint64_t> &done
 
 // --- launch wrappers (kernels_index.hip) ---
 hipError_t launch_tokenize_wave(const BuildParams &p, int grid, hipStream_t s);
+hipError_t launch_doc_range(uint32_t *list, uint32_t *count, uint32_t first, uint32_t n, hipStream_t s);
 hipError_t launch_tokenize_wave_uni(const BuildParams &p, int grid, hipStream_t s);   // flagged non-ASCII documents
 hipError_t launch_tokenize_chunks_uni(const BuildParams &p, int grid, hipStream_t s);  // flagged non-ASCII book units
 constexpr uint32_t kWaveWGsPerCU = 8;       // 64-thread workgroups per CU (2 waves/SIMD: VGPR- and LDS-bound)

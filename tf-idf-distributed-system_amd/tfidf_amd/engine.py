@@ -846,6 +846,12 @@ class ShardIndex:
         L.check(L.load().tfidf_get_commit_timing(self._h, C.byref(t)))
         return {f: getattr(t, f) for f, _ in L.CommitTiming._fields_}
 
+    def commit_tokenized_docs(self):
+        """What the last commit tokenized: {"docs": n, "was_full": bool} (tfidf_commit_tokenized_docs)."""
+        n, full = C.c_uint64(), C.c_uint32()
+        L.check(L.load().tfidf_commit_tokenized_docs(self._h, C.byref(n), C.byref(full)))
+        return {"docs": n.value, "was_full": bool(full.value)}
+
     def stats(self):
         s = L.IndexStats()
         L.check(L.load().tfidf_stats(self._h, C.byref(s)))

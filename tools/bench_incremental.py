@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Commit cost when documents arrive, the shape of real use (the reference
+commits after every upload, Worker.java:136-139): bench.py's timed steps add
+nothing, so they show the limiting case only.
+
+Starts from the cfg-2 device corpus with --base documents committed twice (both
+snapshots built), then
+  one commit after adding --big documents, and
+  --small-commits commits adding --small documents each,
+and reports per commit the host wall time, the device phases
+(tfidf_get_commit_timing) and what the commit tokenized
+(tfidf_commit_tokenized_docs; null with a library that has no such call, which
+tokenizes everything every time).  Commits alternate between two snapshots, so
+every new document is tokenized once for each of them: a commit that adds n
+documents tokenizes about 2n (the n of the commit before, and its own).
+TFIDF_DEBUG=1 TFIDF_FULL_COMMIT=1 gives the full-build numbers on the same library.
+One JSON line on stdout; --out writes it to a file as well.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "tf-idf-distributed-system_amd"))
+
+from tfidf_amd import _lib as L  # noqa: E402
+from tfidf_amd import synth  # noqa: E402
+from tfidf_amd.engine import ShardIndex  # noqa: E402
+
+PHASES = ("ms_tokenize", "ms_long", "ms_df", "ms_blockscan", "ms_colscan", "ms_scatter", "ms_total")
+
+
+def load_library():
+    """False when the library predates tfidf_commit_tokenized_docs (A/B against an older build)."""
+    try:
+        L.load()
+        return True
+    except AttributeError:
+        L.SIGNATURES.pop("tfidf_commit_tokenized_docs")
+        L.load()
+        return False
+
+
+def commit(idx, has_accessor):
+    t0 = time.perf_counter()
+    idx.commit()
+    wall = (time.perf_counter() - t0) * 1e3
+    t = idx.commit_timing()
+    tok = idx.commit_tokenized_docs() if has_accessor else None
+    return {"wall_ms": wall, **{k: t[k] for k in PHASES},
+            "tokenized_docs": tok and tok["docs"], "was_full": tok and tok["was_full"]}
+
+
+def summary(rows):
+    out = {k: float(np.median([r[k] for r in rows])) for k in ("wall_ms",) + PHASES}
+    out["wall_ms_min_max"] = [float(min(r["wall_ms"] for r in rows)), float(max(r["wall_ms"] for r in rows))]
+    out["tokenized_docs"] = [r["tokenized_docs"] for r in rows]
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--base", type=int, default=990_000)
+    ap.add_argument("--big", type=int, default=10_000)
+    ap.add_argument("--small", type=int, default=200)
+    ap.add_argument("--small-commits", type=int, default=50)
+    ap.add_argument("--vocab", type=int, default=100_000)
+    ap.add_argument("--len-min", type=int, default=400)
+    ap.add_argument("--len-max", type=int, default=600)
+    ap.add_argument("--cap-log2", type=int, default=18)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    has_accessor = load_library()
+
+    def corpus(n, base):
+        return synth.DeviceCorpus(n, V=args.vocab, len_min=args.len_min, len_max=args.len_max, doc_base=base)
+
+    def add(idx, c):
+        idx.add_documents_device(c.d_text, c.d_offsets, c.n_docs, c.total_bytes)
+        c.free()
+
+    idx = ShardIndex(vocab_capacity_log2=args.cap_log2)
+    add(idx, corpus(args.base, 0))
+    first = [commit(idx, has_accessor) for _ in range(2)]
+    add(idx, corpus(args.big, args.base))
+    big = commit(idx, has_accessor)
+    small, at = [], args.base + args.big
+    for _ in range(args.small_commits):
+        add(idx, corpus(args.small, at))
+        at += args.small
+        small.append(commit(idx, has_accessor))
+    s = idx.stats()
+    res = {"bench": "incremental_commit", "library_has_accessor": has_accessor,
+           "full_commit_forced": bool(os.environ.get("TFIDF_DEBUG")) and os.environ.get("TFIDF_FULL_COMMIT", "0") not in ("", "0"),
+           "config": {k: v for k, v in vars(args).items() if k != "out"}, "num_docs": s["num_docs"], "nnz": s["nnz"], "text_bytes": s["text_bytes"],
+           "first_two_commits": first, "commit_after_big": big, "small_commits": summary(small),
+           "note": "each new document is tokenized once per snapshot, so by two successive commits"}
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    idx.close()
+
+
+if __name__ == "__main__":
+    main()
