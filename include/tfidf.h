@@ -208,17 +208,30 @@ int tfidf_add_docs_device(tfidf_index *ix, const void *d_utf8, const void *d_off
  *   cover.  When the snapshot a commit rebuilds was built from a prefix of the
  *   same staged corpus — no clear, load, delete, replace-by-key or compaction
  *   since, no dead document, the same layout, hash seed and debug knobs — the
- *   commit tokenizes the documents added since only, and rebuilds df, the
- *   count table and the postings from the rows of all documents.  Any other
- *   commit (the first build of a snapshot, a seed retry, the commit after a
- *   failed one) is a full build.  The published index is the same either way,
- *   bit for bit.  Commits alternate between two snapshots, so a new document is
- *   tokenized once for each (by two successive commits).
+ *   commit tokenizes the documents added since only.  A block-major snapshot
+ *   also keeps the count rows, bases and postings of every 8192-document
+ *   block whose documents were all present at its last inversion, and builds
+ *   those of the later blocks only (a partial last block is always built
+ *   again, also when nothing was added); df is summed over all blocks.  A
+ *   term-major snapshot rebuilds its postings from the rows of all documents.
+ *   Any other commit (the first build of a snapshot, a seed retry, the commit
+ *   after a failed one) is a full build.  The published index is the same
+ *   either way: equal through every call (the order of the postings inside a
+ *   block's segment of one term is not fixed).  Commits alternate between two
+ *   snapshots, so a new document is tokenized once for each (by two
+ *   successive commits).
  * tfidf_commit_tokenized_docs: what the last tfidf_commit tokenized: *docs
  *   (may be NULL) = documents, *was_full (may be NULL) = 1 for a full build.
- *   TFIDF_DEBUG=1 TFIDF_FULL_COMMIT=1 forces full builds (A/B runs). */
+ *   TFIDF_DEBUG=1 TFIDF_FULL_COMMIT=1 forces full builds (A/B runs).
+ * tfidf_commit_inverted_blocks: what the last tfidf_commit's inversion built:
+ *   blocks [*first_block, *n_blocks) (the blocks before were kept; 0 for
+ *   term-major and full builds), *remapped = 1 when the kept count rows moved
+ *   to a wider column layout because the vocabulary grew.  Each pointer may be
+ *   NULL.  TFIDF_DEBUG=1 TFIDF_FULL_INVERSION=1 inverts every block (A/B runs). */
 int tfidf_commit(tfidf_index *ix);
 int tfidf_commit_tokenized_docs(const tfidf_index *ix, uint64_t *docs, uint32_t *was_full);
+int tfidf_commit_inverted_blocks(const tfidf_index *ix, uint32_t *first_block, uint32_t *n_blocks,
+                                 uint32_t *remapped);
 
 /* ---- document lifecycle: delete, reclaim, read back ----
  * tfidf_delete_docs: IndexWriter.deleteDocuments(new Term("path", key)) for

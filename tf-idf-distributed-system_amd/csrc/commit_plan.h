@@ -107,4 +107,60 @@ inline void esc_merge(std::vector<uint64_t> *list, uint64_t kept) {
   std::inplace_merge(list->begin(), list->begin() + std::min<uint64_t>(kept, list->size()), list->end());
 }
 
+// ---------------------------------------------------------------------------
+// Incremental inversion (block-major): the blocks a snapshot's kept blk rows,
+// bbase and post cover, and how those rows move to a wider column layout.
+
+#if defined(__HIPCC__) || defined(__HIP__)
+#define TFIDF_PLAN_HD __host__ __device__ __forceinline__
+#else
+#define TFIDF_PLAN_HD inline
+#endif
+
+constexpr uint64_t kPlanBlockDocs = 8192;     // = kBlockDocs (tfidf_common.h; checked where both are seen)
+
+struct InversionPlan {
+  uint32_t first_block = 0;   // blocks [first_block, n_blocks) are inverted; [0, first_block) are kept
+  bool remap = false;         // the kept blk rows were laid out for another column count
+};
+
+// full: the commit plan's (a full build keeps nothing).  inv_docs / NC_inv:
+// the staged documents the target's blk / bbase / post were built from (0:
+// nothing kept) and the column count its blk rows were laid out for.  N, NC:
+// this commit's.  full_knob: the value of TFIDF_FULL_INVERSION (nullptr =
+// unset; an A/B switch outside the CommitSig: nothing kept depends on it).
+// Only blocks every document of which was inverted before are kept; a partial
+// tail block is inverted again even when no document was added.
+inline InversionPlan inversion_plan(bool full, bool term_major, uint64_t inv_docs, uint64_t N, uint32_t NC,
+                                    uint32_t NC_inv, const char *full_knob) {
+  InversionPlan p;
+  const bool forced = full_knob && *full_knob && !(full_knob[0] == '0' && !full_knob[1]);
+  if (full || term_major || forced || inv_docs > N) return p;
+  p.first_block = (uint32_t)(inv_docs / kPlanBlockDocs);
+  // under a kept signature the dictionary only gains slots: the occupied-slot
+  // set changed if and only if its size did
+  p.remap = p.first_block > 0 && NC != NC_inv;
+  return p;
+}
+
+// A kept row in the new column layout.  Slot s = 32 w + bit is occupied now
+// and is new column c; (old_bits, old_base) = the crank word w the row was
+// laid out by.  old = the occupied old slots below s: the slot's old column
+// when it was occupied then, else the old column that follows it.
+TFIDF_PLAN_HD uint32_t remap_old_col(uint32_t old_bits, uint32_t old_base, uint32_t bit) {
+  return old_base + (uint32_t)__builtin_popcount(old_bits & ((1u << bit) - 1u));
+}
+// ... and the row's value at c: the old offset, or for a slot behind the last
+// old column the block's posting total.  A column new to the block is an
+// empty segment at the offset of the next old column.
+TFIDF_PLAN_HD uint32_t remap_row_value(const uint32_t *old_row, uint32_t NC_inv, uint32_t block_total, uint32_t old) {
+  return old < NC_inv ? old_row[old] : block_total;
+}
+
+// Posting escapes ((posting index << 24) | tf, sorted): the entries of the
+// kept blocks are those with a posting index below post_base = bbase[first_block].
+inline uint64_t post_esc_keep(const std::vector<uint64_t> &sorted, uint64_t post_base) {
+  return (uint64_t)(std::lower_bound(sorted.begin(), sorted.end(), post_base << 24) - sorted.begin());
+}
+
 }  // namespace tfidf

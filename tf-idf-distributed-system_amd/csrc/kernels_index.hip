@@ -30,6 +30,7 @@
 #include "unicode_scan.h"
 #include "wave_ops.h"
 #include "tfidf_internal.h"
+#include "commit_plan.h"
 
 namespace tfidf {
 
@@ -2620,7 +2621,8 @@ static uint32_t tiles_grid(uint32_t n_blocks, uint32_t R) { return (n_blocks + 7
 __global__ void __launch_bounds__(1024) k_df_partial(PostingParams p) {
   extern __shared__ uint32_t hist[];
   uint32_t b, r;
-  if (!tile_of(blockIdx.x, p.n_blocks, p.n_ranges, &b, &r)) return;
+  if (!tile_of(blockIdx.x, p.n_blocks - p.first_block, p.n_ranges, &b, &r)) return;
+  b += p.first_block;                                             // (incremental: the blocks before are kept)
   const uint32_t RS = 1u << p.range_shift;
   for (uint32_t i = threadIdx.x; i < RS / 2; i += blockDim.x) hist[i] = 0;
   __syncthreads();
@@ -2675,13 +2677,58 @@ __global__ void __launch_bounds__(1024) k_df_partial(PostingParams p) {
   }
 }
 
-// per column: df = sum of the per-block counts (row n_blocks).
+// per column: df = sum of the per-block counts (row n_blocks).  The rows of
+// kept blocks (b < first_block) are in offset form: a column's count is the
+// distance to the next column's offset, the last column's to the block total.
 __global__ void __launch_bounds__(256) k_df_sum(PostingParams p) {
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= p.NC) return;
   uint32_t run = 0;
-  for (uint32_t b = 0; b < p.n_blocks; b++) run += p.blk[(size_t)b * p.NC + t];
+  if (p.first_block) {
+    // sum of (next - own) over the kept rows = (sum of next) - (sum of own);
+    // the last column's "next" is the block total, and those sum to
+    // bbase[first_block] - bbase[0].  Nobody touched the kept rows in this
+    // commit, so they come from HBM: eight rows' loads are issued together.
+    const bool last = t + 1 == p.NC;
+    const uint32_t *own = p.blk + t, *nxt = own + (last ? 0 : 1);
+    uint32_t lo = 0, hi = 0, b = 0;
+    for (; b + 8 <= p.first_block; b += 8) {
+      uint32_t x[8], y[8];
+#pragma unroll
+      for (int j = 0; j < 8; j++) {
+        x[j] = own[(size_t)(b + j) * p.NC];
+        y[j] = nxt[(size_t)(b + j) * p.NC];
+      }
+#pragma unroll
+      for (int j = 0; j < 8; j++) { lo += x[j]; hi += y[j]; }
+    }
+    for (; b < p.first_block; b++) {
+      lo += own[(size_t)b * p.NC];
+      hi += nxt[(size_t)b * p.NC];
+    }
+    run = (last ? (uint32_t)(p.bbase[p.first_block] - p.bbase[0]) : hi) - lo;
+  }
+  for (uint32_t b = p.first_block; b < p.n_blocks; b++) run += p.blk[(size_t)b * p.NC + t];
   p.blk[(size_t)p.n_blocks * p.NC + t] = run;
+}
+
+// Kept rows into a wider column layout (the dictionary gained slots since
+// they were laid out): thread per crank word, as k_df_partial's tail walks
+// them; grid.y = kept block.  Never in place: blk_old has stride NC_inv.
+__global__ void __launch_bounds__(256) k_blk_remap(PostingParams p, const uint32_t *blk_old, const uint2 *crank_inv,
+                                                   uint32_t NC_inv) {
+  const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  if (w >= (p.C >> 5)) return;
+  const uint2 e = p.crank[w], o = crank_inv[w];
+  const uint32_t *old_row = blk_old + (size_t)b * NC_inv;
+  uint32_t *row = p.blk + (size_t)b * p.NC;
+  const uint32_t total = (uint32_t)(p.bbase[b + 1] - p.bbase[b]);
+  uint32_t bits = e.x, col = e.y;
+  while (bits) {
+    const uint32_t bit = (uint32_t)__builtin_ctz(bits);
+    bits &= bits - 1;
+    row[col++] = remap_row_value(old_row, NC_inv, total, remap_old_col(o.x, o.y, bit));
+  }
 }
 
 // per block row: exclusive scan over columns in place (one workgroup per row);
@@ -2692,7 +2739,8 @@ __global__ void __launch_bounds__(256) k_df_sum(PostingParams p) {
 __global__ void __launch_bounds__(1024) k_row_scan(PostingParams p) {
   __shared__ uint32_t wsum[16];
   __shared__ uint32_t carry_sh;
-  uint32_t *row = p.blk + (size_t)blockIdx.x * p.NC;
+  const uint32_t b = blockIdx.x + p.first_block;
+  uint32_t *row = p.blk + (size_t)b * p.NC;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   if (tid == 0) carry_sh = 0;
   __syncthreads();
@@ -2745,7 +2793,7 @@ __global__ void __launch_bounds__(1024) k_row_scan(PostingParams p) {
     }
     __syncthreads();
   }
-  if (tid == 0) p.bbase[blockIdx.x + 1] = carry_sh;
+  if (tid == 0) p.bbase[b + 1] = carry_sh;
 }
 
 // Inversion in two passes so that every store stream stays L2-resident.
@@ -2809,7 +2857,8 @@ __global__ void __launch_bounds__(1024) k_scatter_part(PostingParams p) {
   const uint32_t lane = threadIdx.x & 63, nw = blockDim.x >> 6;
   const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   uint32_t b, r;
-  if (!tile_of(blockIdx.x, p.n_blocks, p.n_ranges, &b, &r)) return;
+  if (!tile_of(blockIdx.x, p.n_blocks - p.first_block, p.n_ranges, &b, &r)) return;
+  b += p.first_block;
   const uint32_t RS = 1u << p.range_shift, rmask = RS - 1;
   const uint32_t nsub = RS > kSubSlots ? RS / kSubSlots : 1u;
   const uint32_t *row = p.blk + (size_t)b * p.NC;
@@ -2913,7 +2962,7 @@ __global__ void __launch_bounds__(1024) k_scatter_sort(PostingParams p) {
   __shared__ uint8_t bnorm[kBlockDocs];                     // the block's norm bytes: an LDS read per entry
                                                             // instead of a global load that waits on the temp word
   __shared__ uint2 wk[kSortMaxSpw * (kSubSlots / 32) + 1];  // the streams' column ranks (col_rank)
-  const uint32_t b = blockIdx.x, r = blockIdx.y;
+  const uint32_t b = blockIdx.x + p.first_block, r = blockIdx.y;
   const uint32_t RS = 1u << p.range_shift;
   const uint32_t BS = RS < kSubSlots ? RS : kSubSlots;
   const uint32_t nsub = RS / BS;
@@ -2998,13 +3047,14 @@ __global__ void __launch_bounds__(1024) k_scatter_sort(PostingParams p) {
 }
 
 // block totals in bbase[b + 1] -> block bases, in place (one workgroup; every
-// total of a round is read before the barrier, written after it)
+// total of a round is read before the barrier, written after it).  The bases
+// up to bbase[first_block] are kept and the scan starts from that one.
 __global__ void __launch_bounds__(1024) k_block_scan(PostingParams p) {
   __shared__ uint64_t wsum[16];
   const uint32_t B = p.n_blocks;
   const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  uint64_t carry = 0;
-  for (uint32_t i0 = 0; i0 < B; i0 += 1024) {
+  uint64_t carry = p.first_block ? p.bbase[p.first_block] : 0ull;
+  for (uint32_t i0 = p.first_block; i0 < B; i0 += 1024) {
     const uint32_t i = i0 + tid;
     const uint64_t v = i < B ? p.bbase[i + 1] : 0ull;
     uint64_t x = v;
@@ -3025,7 +3075,7 @@ __global__ void __launch_bounds__(1024) k_block_scan(PostingParams p) {
     if (i < B) p.bbase[i + 1] = base + x;            // inclusive = the next block's base
     carry += all;
   }
-  if (tid == 0) p.bbase[0] = 0;
+  if (tid == 0 && p.first_block == 0) p.bbase[0] = 0;
 }
 
 // Hashed-key checks deferred by dict_verify (the slot's reference occurrence
@@ -3124,7 +3174,8 @@ static void allow_big_lds() {
 hipError_t launch_df_partial(const PostingParams &p, hipStream_t s) {
   allow_big_lds();
   const size_t lds = (size_t)2 << p.range_shift;             // 16-bit counters
-  hipLaunchKernelGGL(k_df_partial, dim3(tiles_grid(p.n_blocks, p.n_ranges)), dim3(1024), lds, s, p);
+  if (p.n_blocks == p.first_block) return hipSuccess;       // every block kept
+  hipLaunchKernelGGL(k_df_partial, dim3(tiles_grid(p.n_blocks - p.first_block, p.n_ranges)), dim3(1024), lds, s, p);
   return hipGetLastError();
 }
 hipError_t launch_df_sum(const PostingParams &p, hipStream_t s) {
@@ -3133,7 +3184,15 @@ hipError_t launch_df_sum(const PostingParams &p, hipStream_t s) {
   return hipGetLastError();
 }
 hipError_t launch_row_scan(const PostingParams &p, hipStream_t s) {
-  hipLaunchKernelGGL(k_row_scan, dim3(p.n_blocks), dim3(1024), 0, s, p);
+  if (p.n_blocks == p.first_block) return hipSuccess;
+  hipLaunchKernelGGL(k_row_scan, dim3(p.n_blocks - p.first_block), dim3(1024), 0, s, p);
+  return hipGetLastError();
+}
+hipError_t launch_blk_remap(const PostingParams &p, const uint32_t *blk_old, const uint2 *crank_inv, uint32_t NC_inv,
+                            hipStream_t s) {
+  if (!p.first_block || !(p.C >> 5)) return hipSuccess;
+  hipLaunchKernelGGL(k_blk_remap, dim3(((p.C >> 5) + 255) / 256, p.first_block), dim3(256), 0, s, p, blk_old, crank_inv,
+                     NC_inv);
   return hipGetLastError();
 }
 // number of nonzero entries of a[0, n) (occupied dictionary slots): one
@@ -3230,13 +3289,14 @@ hipError_t launch_block_base(const PostingParams &p, hipStream_t s) {
   return hipGetLastError();
 }
 hipError_t launch_scatter(const PostingParams &p, hipStream_t s) {
+  if (p.n_blocks == p.first_block) return hipSuccess;       // every block kept
   // launch-shape knobs, read per build (A/B and tests/test_gpu_inversion_shapes.py)
   const uint32_t pthreads = [] {
     const char *e = knob("TFIDF_PART_THREADS");
     const int t = e ? atoi(e) : 1024;
     return (uint32_t)(t == 256 || t == 512 ? t : 1024);
   }();
-  hipLaunchKernelGGL(k_scatter_part, dim3(tiles_grid(p.n_blocks, p.n_ranges)), dim3(pthreads), 0, s, p);
+  hipLaunchKernelGGL(k_scatter_part, dim3(tiles_grid(p.n_blocks - p.first_block, p.n_ranges)), dim3(pthreads), 0, s, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const uint32_t RS = 1u << p.range_shift;
@@ -3246,8 +3306,8 @@ hipError_t launch_scatter(const PostingParams &p, hipStream_t s) {
     const int t = e ? atoi(e) : 512;                             // 512: 2.89 -> 2.52 ms (cfg 2)
     return (uint32_t)(t == 256 || t == 512 ? t : 1024);
   }();
-  hipLaunchKernelGGL(k_scatter_sort, dim3(p.n_blocks, p.n_ranges, (nsub + p.sort_spw - 1) / p.sort_spw), dim3(threads),
-                     0, s, p);
+  hipLaunchKernelGGL(k_scatter_sort, dim3(p.n_blocks - p.first_block, p.n_ranges, (nsub + p.sort_spw - 1) / p.sort_spw),
+                     dim3(threads), 0, s, p);
   return hipGetLastError();
 }
 

@@ -315,6 +315,15 @@ struct Snapshot {
   // depend on.  0 while a build is in progress and after one that failed.
   uint64_t tok_docs = 0;
   CommitSig sig;
+  // ... and the staged documents blk / bbase / post / post_esc were inverted
+  // from (block-major; 0 as above), the column count blk's rows were laid out
+  // for, the crank they were laid out by (crank and crank_inv trade places
+  // before a commit's col_rank), a host copy of bbase, and the target a
+  // remap writes the kept rows to (then swapped with blk)
+  uint64_t inv_docs = 0;
+  uint32_t NC_inv = 0;
+  DevMem crank_inv, blk_alt;
+  PinnedVec<uint64_t> h_bbase;
   PinnedVec<uint64_t> h_dict;          // host mirrors for query analysis (pinned)
   PinnedVec<uint32_t> h_df;
   uint64_t doc_count = 0, sum_ttf = 0, nnz = 0, num_terms = 0, long_docs = 0;
@@ -330,7 +339,7 @@ struct Snapshot {
   std::mutex mlt_mu;
   explicit Snapshot(int d)
       : dev(d), dict(d), csr(d), csr_esc(d), post_esc(d), doc_len(d), doc_nuniq(d), doc_norm(d), rsplit(d), blk(d),
-        bbase(d), post(d), row_off(d), toff(d), tdf(d), crank(d), sdf(d), mlt_idf(d) {}
+        bbase(d), post(d), row_off(d), toff(d), tdf(d), crank(d), sdf(d), crank_inv(d), blk_alt(d), mlt_idf(d) {}
   const uint32_t *df_dev() const { return term_major ? tdf.as<uint32_t>() : sdf.as<uint32_t>(); }   // per slot
   // what the scorers index a term's postings by: its column (block-major) or
   // its dictionary slot (term-major); the scorers' C is the matching count
@@ -442,6 +451,9 @@ struct tfidf_index {
   uint64_t corpus_epoch = 0;
   uint64_t last_tok_docs = 0;          // documents the last commit's build tokenized (tfidf_commit_tokenized_docs)
   uint32_t last_tok_full = 1;          // ... and whether it was a full build
+  // ... and the blocks its inversion kept / the published index holds, and whether the kept rows
+  // were moved to another column layout (tfidf_commit_inverted_blocks)
+  uint32_t last_inv_first = 0, last_inv_blocks = 0, last_inv_remap = 0;
   uint64_t next_ord = 0;               // documents staged since create / clear / load: the next keyless key
   uint32_t compact_pct = 0;            // tfidf_set_compact_threshold (0 = commit never compacts)
   uint64_t compactions = 0;            // tfidf_compact calls that reclaimed something (index lifetime)
@@ -1265,8 +1277,9 @@ constexpr uint32_t kVerifyCap = 1u << 20;      // deferred hashed-key checks per
 static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   hipStream_t s = ix->stream;
   // what the target covers; it covers nothing until this build has succeeded
-  const uint64_t kept_docs = S.tok_docs;
+  const uint64_t kept_docs = S.tok_docs, kept_inv = S.inv_docs;
   S.tok_docs = 0;
+  S.inv_docs = 0;
   // live documents
   S.n_docs = ix->n_staged - ix->n_dead;
   S.live_map.clear();
@@ -1309,8 +1322,8 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   // staged id and offset, and its row, doc_len / doc_nuniq / doc_norm / rsplit
   // words and dictionary entries depend on its text and the signature only:
   // while the signature holds, the target keeps them and documents
-  // [d_first, N) alone are tokenized.  The inversion below always runs over
-  // all N documents.
+  // [d_first, N) alone are tokenized.  The block-major inversion below then
+  // keeps the blocks whose documents were all inverted before (inversion_plan).
   CommitSig sig;
   sig.epoch = ix->corpus_epoch;
   sig.hash_seed = ix->hash_seed;
@@ -1371,8 +1384,12 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     HIP_TRY(S.tdf.reserve((size_t)C * 4));
   } else {
     // (the count table blk is sized by the columns, known after the tokenizers)
-    HIP_TRY(S.bbase.reserve((size_t)(S.n_blocks + 2) * 8));
+    // (bbase is sized with blk below, once the kept blocks are known)
     HIP_TRY(S.crank.reserve(((size_t)C / 32 + 1) * 8));
+    HIP_TRY(S.crank_inv.reserve(((size_t)C / 32 + 1) * 8));
+    // the crank the kept blk rows were laid out by stays in crank_inv; col_rank writes the other buffer
+    std::swap(S.crank.p, S.crank_inv.p);
+    std::swap(S.crank.bytes, S.crank_inv.bytes);
     HIP_TRY(S.sdf.reserve((size_t)C * 4));
   }
 
@@ -1633,7 +1650,30 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   S.sum_ttf = kept.sum_ttf + hctr[1];
   S.nnz = kept.nnz + hctr[2];
   S.NC = S.term_major ? 0u : (uint32_t)hctr[7];
-  if (!S.term_major) HIP_TRY(S.blk.reserve((size_t)(S.n_blocks + 1) * S.NC * 4 + 16));
+  // Block-major: the blocks kept from the target's last inversion.  Their blk
+  // rows (offset form), bases and postings depend on their own documents' rows
+  // and norms and on the slot -> column map only; when the dictionary gained
+  // slots, the kept rows move to the new column layout (k_blk_remap).
+  const InversionPlan inv = inversion_plan(plan.full, S.term_major, kept_inv, N, S.NC, S.NC_inv,
+                                           knob("TFIDF_FULL_INVERSION"));
+  const uint32_t first_block = inv.first_block;
+  const uint64_t kept_post = first_block ? S.h_bbase[first_block] : 0;      // postings of the kept blocks
+  const uint64_t kept_pe = first_block ? post_esc_keep(S.h_post_esc, kept_post) : 0;
+  ix->last_inv_first = first_block;
+  ix->last_inv_blocks = S.n_blocks;
+  ix->last_inv_remap = inv.remap ? 1u : 0u;
+  const uint32_t *blk_old = nullptr;
+  if (!S.term_major) {
+    const uint64_t blk_need = (uint64_t)(S.n_blocks + 1) * S.NC * 4 + 16;
+    if (inv.remap) {
+      HIP_TRY(S.blk_alt.reserve(blk_need + blk_need / 8));   // (slack: a shard that keeps gaining terms remaps every commit)
+      std::swap(S.blk.p, S.blk_alt.p);
+      std::swap(S.blk.bytes, S.blk_alt.bytes);
+      blk_old = S.blk_alt.as<uint32_t>();
+    } else if (int rc = grow_keep(ix, &S.blk, blk_need, (uint64_t)first_block * S.NC * 4)) return rc;
+    if (int rc = grow_keep(ix, &S.bbase, (uint64_t)(S.n_blocks + 2) * 8, first_block ? (uint64_t)(first_block + 1) * 8 : 0))
+      return rc;
+  }
   // CSR tf escapes (rare: block-major only for tf >= 65 535, the all-ones
   // value of the 16-bit field, csr_esc_value(kRangeBits)): sorted by entry
   // index for the binary searches of the inversion and tfidf_doc_terms
@@ -1656,10 +1696,13 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   if (S.nnz >= 0xFFFFFFFFull) return fail(TFIDF_E_CAPACITY, "more than 2^32 postings per shard");
   // postings: block-major u32 (post_word), term-major u64; pass-1 temp words u32
   // (term-major: the sort's u64 value buffer)
-  HIP_TRY(S.post.reserve(S.nnz * (S.term_major ? 8 : 4) + 8));
+  if (int rc = grow_keep(ix, &S.post, S.nnz * (S.term_major ? 8 : 4) + 8, kept_post * 4)) return rc;
   HIP_TRY(ix->post_tmp.reserve(S.nnz * (S.term_major ? 8 : 4) + 8));
   const uint64_t post_esc_cap = row_cap / kPostTfEsc + 64;       // each needs tf >= 2047 tokens of one doc
-  if (!S.term_major) HIP_TRY(S.post_esc.reserve(post_esc_cap * 8));
+  // (the kept blocks' escapes are the first kept_pe of the sorted list; new ones are appended behind them)
+  if (!S.term_major)
+    if (int rc = grow_keep(ix, &S.post_esc, post_esc_cap * 8, kept_pe * 8)) return rc;
+  if (kept_pe) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(ctr + 10), (int)(uint32_t)kept_pe, 1, s));
 
   // the dictionary is final here (wave, Unicode and long paths done): its host
   // mirror, the deferred identity checks and the occupied-slot count run on the
@@ -1703,6 +1746,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   pp.sort_spw = 4;
   if (const char *e = knob("TFIDF_SORT_SPW")) pp.sort_spw = (uint32_t)std::max(1, std::min(8, atoi(e)));   // A/B only (<= kSortMaxSpw)
   pp.err = bp.err;
+  pp.first_block = first_block;
   HIP_TRY(hipEventRecord(ix->ev[EV_D0], s));
   if (S.term_major) {
     TermParams tp{};
@@ -1761,8 +1805,9 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     HIP_TRY(launch_term_sort(tp, s));
     HIP_TRY(hipEventRecord(ix->ev[EV_SCAT], s));
   } else {
+    if (inv.remap) HIP_TRY(launch_blk_remap(pp, blk_old, S.crank_inv.as<uint2>(), S.NC_inv, s));
     if (S.n_blocks) {
-      HIP_TRY(launch_df_partial(pp, s));
+      HIP_TRY(launch_df_partial(pp, s));                  // blocks [first_block, n_blocks)
     } else {
       HIP_TRY(hipMemsetAsync(S.blk.p, 0, (size_t)S.NC * 4, s));
     }
@@ -1818,14 +1863,22 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   }
   uint64_t tail[8];              // ctr[3] error flags .. ctr[7] occupied slots, [8] malformed, [10] posting escapes
   HIP_TRY(hipMemcpyAsync(tail, ctr + 3, sizeof tail, hipMemcpyDeviceToHost, s));
+  if (!S.term_major) {           // the block bases: the next commit's kept postings and escapes are found by them
+    HIP_TRY(S.h_bbase.resize((size_t)S.n_blocks + 2));
+    HIP_TRY(hipMemcpyAsync(S.h_bbase.data(), S.bbase.p, ((size_t)S.n_blocks + 1) * 8, hipMemcpyDeviceToHost, s));
+  }
   HIP_TRY(hipStreamSynchronize(s));
   {
-    const uint64_t n_pe = S.term_major ? 0 : (uint32_t)tail[7];
-    if (n_pe > post_esc_cap) return fail(TFIDF_E_CAPACITY, "posting escape list overflow");
+    // rare (tf >= 2047): sorted for the scorer's binary search.  The kept
+    // blocks' entries stand; the new ones were appended behind them.
+    const EscAppend pe = esc_append_bounds(kept_pe, S.term_major ? 0 : (uint32_t)tail[7], post_esc_cap);
+    if (pe.overflow) return fail(TFIDF_E_CAPACITY, "posting escape list overflow");
+    const uint64_t n_pe = pe.first + pe.count;
     S.h_post_esc.resize(n_pe);
-    if (n_pe) {                                // rare (tf >= 2047): sorted for the scorer's binary search
-      HIP_TRY(hipMemcpy(S.h_post_esc.data(), S.post_esc.p, n_pe * 8, hipMemcpyDeviceToHost));
-      std::sort(S.h_post_esc.begin(), S.h_post_esc.end());
+    if (pe.count) {
+      HIP_TRY(hipMemcpy(S.h_post_esc.data() + pe.first, S.post_esc.as<uint64_t>() + pe.first, pe.count * 8,
+                        hipMemcpyDeviceToHost));
+      esc_merge(&S.h_post_esc, pe.first);
       HIP_TRY(hipMemcpy(S.post_esc.p, S.h_post_esc.data(), n_pe * 8, hipMemcpyHostToDevice));
     }
   }
@@ -1878,6 +1931,10 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   V.sum_ttf = S.sum_ttf;
   if (int rc = upload_cache(ix->cfg, V, s)) return rc;
   S.tok_docs = ix->n_staged;           // the rows and the dictionary cover every staged document
+  if (!S.term_major) {                 // ... and so do blk (laid out by crank, NC columns), bbase and post
+    S.inv_docs = ix->n_staged;
+    S.NC_inv = S.NC;
+  }
   return TFIDF_OK;
 }
 
@@ -1951,6 +2008,16 @@ extern "C" int tfidf_commit_tokenized_docs(const tfidf_index *ix, uint64_t *docs
   return TFIDF_OK;
 }
 
+extern "C" int tfidf_commit_inverted_blocks(const tfidf_index *ix, uint32_t *first_block, uint32_t *n_blocks,
+                                            uint32_t *remapped) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->mu);
+  if (first_block) *first_block = ix->last_inv_first;
+  if (n_blocks) *n_blocks = ix->last_inv_blocks;
+  if (remapped) *remapped = ix->last_inv_remap;
+  return TFIDF_OK;
+}
+
 extern "C" int tfidf_get_commit_timing(const tfidf_index *ix, tfidf_commit_timing *out) {
   if (!ix || !out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
   *out = ix->timing;
@@ -2001,7 +2068,8 @@ extern "C" int tfidf_stats(const tfidf_index *ix, tfidf_index_stats *out) {
   uint64_t tot = staged_bytes;
   if (S) {
     const DevBuf *bufs[] = {&S->dict, &S->csr, &S->csr_esc, &S->doc_len, &S->doc_nuniq, &S->doc_norm,
-                            &S->rsplit, &S->blk, &S->bbase, &S->post, &S->toff, &S->tdf, &S->crank, &S->sdf};
+                            &S->rsplit, &S->blk, &S->bbase, &S->post, &S->toff, &S->tdf, &S->crank, &S->sdf,
+                            &S->crank_inv, &S->blk_alt};
     for (const DevBuf *b : bufs) tot += b->bytes;
   }
   out->device_bytes = tot;

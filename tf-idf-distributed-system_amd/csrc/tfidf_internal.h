@@ -236,6 +236,8 @@ struct PostingParams {
   uint32_t *err;
   uint32_t *post_tmp;         // [nnz] scatter pass 1 output (sub-range streams, same regions)
   uint32_t sort_spw;          // scatter pass 2: sub-range streams per workgroup
+  uint32_t first_block;       // incremental inversion (commit_plan.h): blocks [first_block, n_blocks) are built;
+                              // the rows of blk (offset form), bbase and post of the blocks before are kept
 };
 
 // Raise a kernel's dynamic-LDS limit on the current device, once per device:
@@ -299,6 +301,9 @@ hipError_t launch_count_nonzero(const uint64_t *a, uint32_t n, unsigned long lon
 hipError_t launch_col_rank(const uint64_t *dict_lo, uint32_t C, uint2 *crank, unsigned long long *n_cols, hipStream_t s);
 hipError_t launch_df_slots(const uint2 *crank, const uint32_t *df_col, uint32_t C, uint32_t *df_slot, hipStream_t s);
 hipError_t launch_scatter(const PostingParams &p, hipStream_t s);
+// kept blk rows [0, rows) from the column layout of crank_inv (stride NC_inv) to that of p.crank (p.blk, stride p.NC)
+hipError_t launch_blk_remap(const PostingParams &p, const uint32_t *blk_old, const uint2 *crank_inv, uint32_t NC_inv,
+                            hipStream_t s);
 
 // --- term-major inversion for large vocabularies (kernels_term.hip) ---
 // (hand-written LSD radix sort of packed words slot | doc | tf | norm)

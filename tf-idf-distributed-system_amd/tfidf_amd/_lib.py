@@ -210,6 +210,7 @@ SIGNATURES = {
     "tfidf_set_hash_attempt": (C.c_int, [VP, C.c_uint32]),
     "tfidf_get_commit_timing": (C.c_int, [VP, C.POINTER(CommitTiming)]),
     "tfidf_commit_tokenized_docs": (C.c_int, [VP, U64P, U32P]),
+    "tfidf_commit_inverted_blocks": (C.c_int, [VP, U32P, U32P, U32P]),
     "tfidf_stats": (C.c_int, [VP, C.POINTER(IndexStats)]),
     "tfidf_search": (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, U32P, F32P, C.c_uint64, U64P]),
     "tfidf_search_coalesced": (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, U32P, F32P, C.c_uint64, U64P,

@@ -852,6 +852,13 @@ class ShardIndex:
         L.check(L.load().tfidf_commit_tokenized_docs(self._h, C.byref(n), C.byref(full)))
         return {"docs": n.value, "was_full": bool(full.value)}
 
+    def commit_inverted_blocks(self):
+        """What the last commit's inversion built: blocks [first_block, n_blocks); remapped: the kept
+        count rows moved to a wider column layout (tfidf_commit_inverted_blocks)."""
+        f, n, r = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        L.check(L.load().tfidf_commit_inverted_blocks(self._h, C.byref(f), C.byref(n), C.byref(r)))
+        return {"first_block": f.value, "n_blocks": n.value, "remapped": r.value}
+
     def stats(self):
         s = L.IndexStats()
         L.check(L.load().tfidf_stats(self._h, C.byref(s)))

@@ -10,10 +10,13 @@ snapshots built), then
 and reports per commit the host wall time, the device phases
 (tfidf_get_commit_timing) and what the commit tokenized
 (tfidf_commit_tokenized_docs; null with a library that has no such call, which
-tokenizes everything every time).  Commits alternate between two snapshots, so
+tokenizes everything every time) and which blocks its inversion built
+(tfidf_commit_inverted_blocks: first_block, n_blocks, remapped; null with a
+library that has no such call, which inverts every block every time).  Commits alternate between two snapshots, so
 every new document is tokenized once for each of them: a commit that adds n
 documents tokenizes about 2n (the n of the commit before, and its own).
-TFIDF_DEBUG=1 TFIDF_FULL_COMMIT=1 gives the full-build numbers on the same library.
+TFIDF_DEBUG=1 TFIDF_FULL_COMMIT=1 gives the full-build numbers on the same library,
+TFIDF_DEBUG=1 TFIDF_FULL_INVERSION=1 those of incremental tokenizing with every block inverted.
 One JSON line on stdout; --out writes it to a file as well.
 """
 import argparse
@@ -34,31 +37,40 @@ from tfidf_amd.engine import ShardIndex  # noqa: E402
 PHASES = ("ms_tokenize", "ms_long", "ms_df", "ms_blockscan", "ms_colscan", "ms_scatter", "ms_total")
 
 
+ACCESSORS = ("tfidf_commit_inverted_blocks", "tfidf_commit_tokenized_docs")   # newest first
+
+
 def load_library():
-    """False when the library predates tfidf_commit_tokenized_docs (A/B against an older build)."""
-    try:
-        L.load()
-        return True
-    except AttributeError:
-        L.SIGNATURES.pop("tfidf_commit_tokenized_docs")
-        L.load()
-        return False
+    """The accessors the library has (A/B against an older build: it may predate either)."""
+    have = list(ACCESSORS)
+    while True:
+        try:
+            L.load()
+            return set(have)
+        except AttributeError:
+            if not have:
+                raise
+            L.SIGNATURES.pop(have.pop(0))
 
 
-def commit(idx, has_accessor):
+def commit(idx, have):
     t0 = time.perf_counter()
     idx.commit()
     wall = (time.perf_counter() - t0) * 1e3
     t = idx.commit_timing()
-    tok = idx.commit_tokenized_docs() if has_accessor else None
+    tok = idx.commit_tokenized_docs() if "tfidf_commit_tokenized_docs" in have else None
+    inv = idx.commit_inverted_blocks() if "tfidf_commit_inverted_blocks" in have else {}
     return {"wall_ms": wall, **{k: t[k] for k in PHASES},
-            "tokenized_docs": tok and tok["docs"], "was_full": tok and tok["was_full"]}
+            "tokenized_docs": tok and tok["docs"], "was_full": tok and tok["was_full"],
+            "first_block": inv.get("first_block"), "n_blocks": inv.get("n_blocks"), "remapped": inv.get("remapped")}
 
 
 def summary(rows):
     out = {k: float(np.median([r[k] for r in rows])) for k in ("wall_ms",) + PHASES}
     out["wall_ms_min_max"] = [float(min(r["wall_ms"] for r in rows)), float(max(r["wall_ms"] for r in rows))]
     out["tokenized_docs"] = [r["tokenized_docs"] for r in rows]
+    for k in ("first_block", "n_blocks", "remapped"):
+        out[k] = [r[k] for r in rows]
     return out
 
 
@@ -74,7 +86,7 @@ def main():
     ap.add_argument("--cap-log2", type=int, default=18)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    has_accessor = load_library()
+    has_accessor = load_library()           # (the set of accessors the library has)
 
     def corpus(n, base):
         return synth.DeviceCorpus(n, V=args.vocab, len_min=args.len_min, len_max=args.len_max, doc_base=base)
@@ -94,7 +106,9 @@ def main():
         at += args.small
         small.append(commit(idx, has_accessor))
     s = idx.stats()
-    res = {"bench": "incremental_commit", "library_has_accessor": has_accessor,
+    res = {"bench": "incremental_commit", "library_has_accessor": "tfidf_commit_tokenized_docs" in has_accessor,
+           "library_reports_inverted_blocks": "tfidf_commit_inverted_blocks" in has_accessor,
+           "full_inversion_forced": bool(os.environ.get("TFIDF_DEBUG")) and os.environ.get("TFIDF_FULL_INVERSION", "0") not in ("", "0"),
            "full_commit_forced": bool(os.environ.get("TFIDF_DEBUG")) and os.environ.get("TFIDF_FULL_COMMIT", "0") not in ("", "0"),
            "config": {k: v for k, v in vars(args).items() if k != "out"}, "num_docs": s["num_docs"], "nnz": s["nnz"], "text_bytes": s["text_bytes"],
            "first_two_commits": first, "commit_after_big": big, "small_commits": summary(small),
