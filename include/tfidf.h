@@ -158,6 +158,27 @@ typedef struct tfidf_commit_timing {
   uint64_t nnz;
 } tfidf_commit_timing;
 
+/* Host side of the last tfidf_commit (std::chrono::steady_clock; no GPU work
+ * is added to take it).  The ms_* points are host times since the call began;
+ * with seed retries they are those of the last attempt, while the counts and
+ * bytes sum over all attempts.  A mirror form is how the snapshot's host copy
+ * of the dictionary, the per-slot df or the slot -> column words was brought
+ * up to date: not copied (nothing changed), a list of the changed slots, or
+ * the whole array (see tfidf_commit). */
+enum { TFIDF_MIRROR_NONE = 0, TFIDF_MIRROR_DELTA = 1, TFIDF_MIRROR_WHOLE = 2 };
+typedef struct tfidf_host_profile {
+  double ms_wall;          /* the whole call */
+  double ms_counters;      /* the first read of the build counters returned */
+  double ms_enqueued;      /* every kernel and copy of the inversion is enqueued */
+  double ms_synced;        /* the final stream synchronisation returned */
+  double ms_published;     /* the snapshot is published (0: the commit failed) */
+  uint32_t stream_syncs;   /* host waits for the stream (blocking copies included) */
+  uint32_t col_rank_runs;  /* times the slot -> column words were recomputed */
+  uint32_t mirror_dict, mirror_df, mirror_crank;        /* TFIDF_MIRROR_* */
+  uint32_t dict_delta_entries, df_delta_entries;        /* list lengths of the delta forms */
+  uint64_t bytes_dict, bytes_df, bytes_crank;           /* copied device -> host */
+} tfidf_host_profile;
+
 const char *tfidf_version(void);
 const char *tfidf_last_error(void);
 int tfidf_config_init(tfidf_config *cfg);
@@ -227,11 +248,26 @@ int tfidf_add_docs_device(tfidf_index *ix, const void *d_utf8, const void *d_off
  *   blocks [*first_block, *n_blocks) (the blocks before were kept; 0 for
  *   term-major and full builds), *remapped = 1 when the kept count rows moved
  *   to a wider column layout because the vocabulary grew.  Each pointer may be
- *   NULL.  TFIDF_DEBUG=1 TFIDF_FULL_INVERSION=1 inverts every block (A/B runs). */
+ *   NULL.  TFIDF_DEBUG=1 TFIDF_FULL_INVERSION=1 inverts every block (A/B runs).
+ * Host mirrors: df lookups, the vocabulary export, query analysis and the
+ *   GLOBAL setters read pinned host copies of a snapshot's dictionary keys,
+ *   per-slot df and slot -> column words.  An incremental block-major commit
+ *   whose target's last build succeeded brings them up to date with the new
+ *   slots' keys and the changed df alone, or copies nothing when nothing
+ *   changed; every other commit copies them whole.  The published index is
+ *   the same either way.  TFIDF_DEBUG=1 TFIDF_FULL_MIRROR=1 copies them whole
+ *   always (A/B runs).
+ * tfidf_commit_host_profile: the host side of the last tfidf_commit (see
+ *   tfidf_host_profile above): where the host's time went, how often it
+ *   waited for the stream (2 for an incremental commit without new documents,
+ *   3 for one that adds documents, plus the waits of the tokenizer's packed
+ *   and long-document paths where they run), and per mirror the form it took
+ *   and the bytes copied device -> host.  It costs nothing on the device. */
 int tfidf_commit(tfidf_index *ix);
 int tfidf_commit_tokenized_docs(const tfidf_index *ix, uint64_t *docs, uint32_t *was_full);
 int tfidf_commit_inverted_blocks(const tfidf_index *ix, uint32_t *first_block, uint32_t *n_blocks,
                                  uint32_t *remapped);
+int tfidf_commit_host_profile(const tfidf_index *ix, tfidf_host_profile *out);
 
 /* ---- document lifecycle: delete, reclaim, read back ----
  * tfidf_delete_docs: IndexWriter.deleteDocuments(new Term("path", key)) for

@@ -1,8 +1,9 @@
 // commit_plan.h — the host side of an incremental tfidf_commit: whether the
 // build target's rows and dictionary can be kept (and from which document the
-// tokenizers then start), and how the kept host lists take the new entries.
-// Plain C++ (no HIP), so the decision is tested on its own
-// (tests/commit_plan_check.cpp).
+// tokenizers then start), how the kept host lists take the new entries, and
+// how the host mirrors of the dictionary and df follow.  Plain C++ (no HIP),
+// so the decisions are tested on their own (tests/commit_plan_check.cpp,
+// tests/mirror_plan_check.cpp).
 #pragma once
 
 #include <stdint.h>
@@ -161,6 +162,98 @@ TFIDF_PLAN_HD uint32_t remap_row_value(const uint32_t *old_row, uint32_t NC_inv,
 // kept blocks are those with a posting index below post_base = bbase[first_block].
 inline uint64_t post_esc_keep(const std::vector<uint64_t> &sorted, uint64_t post_base) {
   return (uint64_t)(std::lower_bound(sorted.begin(), sorted.end(), post_base << 24) - sorted.begin());
+}
+
+// ---------------------------------------------------------------------------
+// Host mirrors of a block-major snapshot (h_dict: the dictionary's two key
+// planes, h_df: df per slot, h_crank: the slot -> column words): how a commit
+// brings each up to date.  A snapshot's mirrors match its device dictionary
+// and per-slot df as of its last successful build (Snapshot::mir_ok); under a
+// kept signature the dictionary only gains slots and df changes only for
+// terms of the newly tokenized documents, so an incremental commit can move
+// the changed slots alone.
+
+enum MirrorForm : uint32_t { kMirrorNone = 0, kMirrorDelta = 1, kMirrorWhole = 2 };   // = TFIDF_MIRROR_* (tfidf.h)
+
+// Dictionary: a delta entry is 24 bytes against 16 per slot of the whole
+// copy, and the host writes each entry into two planes (apply_dict_delta:
+// 5-9 ns per entry measured at 2^18 .. 2^21 slots, list in the kernel's
+// nearly ascending order) where the whole copy moves a slot in ~0.3 ns (16
+// bytes at the ~50 GB/s of a pinned copy).  The two meet near C / 20 new
+// slots; the delta is taken up to C / 32.  A list of up to kDictDeltaMin
+// entries (12 KB, < 4 us of host writes) costs less than the fixed latency of
+// any copy, so it is taken whatever C is.  A commit that adds more (3 % of the
+// slots, 12 % of a dictionary at its design load of 1/4) is a bulk load, and
+// the whole copy is the right form.
+constexpr uint32_t kDictDeltaDiv = 32;
+constexpr uint32_t kDictDeltaMin = 512;
+inline uint32_t dict_delta_max(uint32_t C) { return std::min(C, std::max(C / kDictDeltaDiv, kDictDeltaMin)); }
+// df: an entry costs 8 bytes of copy and a near-sequential store (2-4 ns
+// measured), and the list is copied after the commit's last synchronisation
+// (its length is known only then): one more round trip, ~15 us, where the
+// whole copy runs beside the scatter.  The whole copy of the smallest
+// dictionary the benchmarks use (2^18 slots, 1 MB) takes ~20 us, so the list
+// must stay short to win there: 4096 entries are 32 KB and ~10 us of host
+// writes.  The cap also sizes the list buffer.
+constexpr uint32_t kDfDeltaCap = 1u << 12;
+// The changed-slot count is known only after the inversion, but it is at most
+// the postings of the newly tokenized documents (new_nnz: each changes one
+// slot's df, and postings of one term share a slot; Zipf text shares
+// heavily).  The delta is tried up to 4 x cap postings; beyond that the list
+// would likely overflow, and the whole copy is queued beside the inversion
+// from the start, as in a full build.
+constexpr uint32_t kDfDeltaTry = 4;
+
+struct DictDelta {                 // one new dictionary slot and its key
+  uint64_t slot, lo, hi;
+};
+struct DfDelta {                   // one slot whose df changed, and the new value
+  uint32_t slot, df;
+};
+
+struct MirrorPlan {
+  bool delta = false;              // the preconditions of a delta hold (else every mirror is copied whole)
+  MirrorForm dict = kMirrorWhole, crank = kMirrorWhole, df = kMirrorWhole;
+  uint32_t n_new = 0;              // new dictionary slots (dict == kMirrorDelta: the list's length)
+};
+
+// full / term_major / kept_inv: as for inversion_plan (kept_inv != 0: the
+// target's last inversion succeeded, so crank_inv is the occupancy its
+// mirrors were taken at).  mir_ok: the target's mirrors matched its device
+// arrays when this commit began.  NC / NC_inv: occupied slots now and then.
+// new_nnz: postings of the documents this commit tokenized.  df_cap: the df
+// list's capacity (kDfDeltaCap unless a test lowers it).  full_knob:
+// TFIDF_FULL_MIRROR (an A/B switch outside the CommitSig, as TFIDF_FULL_INVERSION).
+inline MirrorPlan mirror_plan(bool full, bool term_major, uint64_t kept_inv, bool mir_ok, uint32_t C, uint32_t NC,
+                              uint32_t NC_inv, uint64_t new_nnz, uint32_t df_cap, const char *full_knob) {
+  MirrorPlan p;
+  const bool forced = full_knob && *full_knob && !(full_knob[0] == '0' && !full_knob[1]);
+  if (full || term_major || kept_inv == 0 || !mir_ok || forced || NC < NC_inv) return p;
+  p.delta = true;
+  p.n_new = NC - NC_inv;
+  if (p.n_new == 0) p.dict = p.crank = kMirrorNone;
+  else if (p.n_new <= dict_delta_max(C)) p.dict = kMirrorDelta;     // (crank: 8 bytes per 32 slots, whole)
+  if (new_nnz == 0) p.df = kMirrorNone;                             // nothing tokenized: no df moved
+  else if (new_nnz <= (uint64_t)df_cap * kDfDeltaTry) p.df = kMirrorDelta;
+  return p;
+}
+
+// The lists applied to the mirrors (after the commit's error checks).  false:
+// an entry names a slot >= C; nothing was written.
+inline bool apply_dict_delta(uint64_t *h_dict, uint32_t C, const DictDelta *list, uint64_t n) {
+  for (uint64_t i = 0; i < n; i++)
+    if (list[i].slot >= C) return false;
+  for (uint64_t i = 0; i < n; i++) {
+    h_dict[list[i].slot] = list[i].lo;
+    h_dict[(size_t)C + list[i].slot] = list[i].hi;
+  }
+  return true;
+}
+inline bool apply_df_delta(uint32_t *h_df, uint32_t C, const DfDelta *list, uint64_t n) {
+  for (uint64_t i = 0; i < n; i++)
+    if (list[i].slot >= C) return false;
+  for (uint64_t i = 0; i < n; i++) h_df[list[i].slot] = list[i].df;
+  return true;
 }
 
 }  // namespace tfidf

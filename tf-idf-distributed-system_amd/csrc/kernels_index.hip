@@ -3283,6 +3283,40 @@ hipError_t launch_df_slots(const uint2 *crank, const uint32_t *df_col, uint32_t 
   hipLaunchKernelGGL(k_df_slots, dim3((C + 255) / 256), dim3(256), 0, s, crank, df_col, C, df_slot);
   return hipGetLastError();
 }
+// k_df_slots for an incremental commit whose host mirrors take deltas
+// (commit_plan.h mirror_plan): df_slot still holds the values of the
+// snapshot's last build, so a slot whose df differs goes to df_list, and a
+// slot occupied now but not in crank_inv (the occupancy of that build) goes to
+// dict_list with its key.  One thread per slot, so both lists are a ballot,
+// one atomicAdd per wave and plain stores; each counter counts past its cap,
+// nothing is stored past it.  A null list is not built.
+__global__ void __launch_bounds__(256) k_df_slots_delta(MirrorDeltaParams p) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
+  const bool in = t < p.C;                                    // (no early exit: the ballots take whole waves)
+  uint32_t df = 0, old = 0;
+  bool fresh = false;
+  if (in) {
+    const uint2 e = p.crank[t >> 5];
+    const uint32_t bit = 1u << (t & 31u);
+    df = (e.x & bit) ? p.df_col[e.y + __popc(e.x & (bit - 1u))] : 0u;
+    old = p.df_slot[t];
+    p.df_slot[t] = df;
+    fresh = p.dict_list && (e.x & bit) && !(p.crank_inv[t >> 5].x & bit);
+  }
+  if (p.df_list) {
+    const bool ch = in && df != old;
+    const uint32_t i = wc_wave_pos(p.df_count, ch, lane);
+    if (ch && i < p.df_cap) p.df_list[i] = DfDelta{t, df};
+  }
+  if (p.dict_list) {
+    const uint32_t i = wc_wave_pos(p.dict_count, fresh, lane);
+    if (fresh && i < p.dict_cap) p.dict_list[i] = DictDelta{t, p.dict[t], p.dict[(size_t)p.C + t]};
+  }
+}
+hipError_t launch_df_slots_delta(const MirrorDeltaParams &p, hipStream_t s) {
+  hipLaunchKernelGGL(k_df_slots_delta, dim3((p.C + 255) / 256), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
 
 hipError_t launch_block_base(const PostingParams &p, hipStream_t s) {
   hipLaunchKernelGGL(k_block_scan, dim3(1), dim3(1024), 0, s, p);   // (serial k_block_base: 15 us at 123 blocks)

@@ -87,6 +87,15 @@ struct DevBuf {
     if (e == hipSuccess) bytes = n;
     return e;
   }
+  // scratch sized by the documents or postings of a shard that grows with every commit: an exact
+  // reserve would free and allocate it again each time (hipFree waits for the device); 1/16 + 1 MiB
+  // of slack makes that rare
+  hipError_t reserve_slack(size_t n) {
+    if (n <= bytes && p) return hipSuccess;
+    if (reserve(n + n / 16 + (1u << 20)) == hipSuccess) return hipSuccess;
+    hipGetLastError();                           // no room for the slack: the exact size
+    return reserve(n);
+  }
   void release() {
     if (p) hipFree(p);
     p = nullptr;
@@ -326,6 +335,10 @@ struct Snapshot {
   PinnedVec<uint64_t> h_bbase;
   PinnedVec<uint64_t> h_dict;          // host mirrors for query analysis (pinned)
   PinnedVec<uint32_t> h_df;
+  // h_dict, h_df and h_crank match dict, sdf and crank as of the last
+  // successful build of this snapshot: cleared when a build begins, set at its
+  // successful end.  Only then may the next build move deltas (mirror_plan).
+  bool mir_ok = false;
   uint64_t doc_count = 0, sum_ttf = 0, nnz = 0, num_terms = 0, long_docs = 0;
   uint32_t pack_docs = 1;
   uint64_t pack_retried = 0, unicode_docs = 0, unicode_wave_docs = 0, long_chunked = 0;
@@ -454,6 +467,9 @@ struct tfidf_index {
   // ... and the blocks its inversion kept / the published index holds, and whether the kept rows
   // were moved to another column layout (tfidf_commit_inverted_blocks)
   uint32_t last_inv_first = 0, last_inv_blocks = 0, last_inv_remap = 0;
+  // host side of the last commit (tfidf_commit_host_profile): points since prof_t0
+  tfidf_host_profile prof{};
+  std::chrono::steady_clock::time_point prof_t0;
   uint64_t next_ord = 0;               // documents staged since create / clear / load: the next keyless key
   uint32_t compact_pct = 0;            // tfidf_set_compact_threshold (0 = commit never compacts)
   uint64_t compactions = 0;            // tfidf_compact calls that reclaimed something (index lifetime)
@@ -464,6 +480,11 @@ struct tfidf_index {
   DevBuf long_list, uni_list, counters, post_tmp;
   DevBuf retry_list;                   // packed wave path: documents deferred to the single-document pass
   DevBuf new_list;                     // incremental commit, one document per wave: [0] count, [1 ..] the new documents
+  // delta mirrors (commit_plan.h): the device lists of new dictionary slots and of slots whose df changed, and
+  // their pinned host copies (sized once for the largest list, so no commit reallocates pinned memory)
+  DevBuf mir_dict_list, mir_df_list;
+  PinnedVec<DictDelta> h_dict_delta;
+  PinnedVec<DfDelta> h_df_delta;
   DevBuf bad_list;                     // documents that are not valid UTF-8 (indexed empty)
   uint64_t hash_seed = 0;              // KeyBuilder seed of the build (0 unless a collision was met)
   uint32_t hash_rebuilds = 0;          // builds redone for a hash collision in the last commit
@@ -630,6 +651,7 @@ extern "C" int tfidf_destroy(tfidf_index *ix) {
   ix->text.reset();
   ix->offsets.reset();
   DevBuf *bufs[] = {&ix->d_live_map, &ix->long_list, &ix->uni_list, &ix->counters, &ix->retry_list, &ix->new_list, &ix->bad_list,
+                    &ix->mir_dict_list, &ix->mir_df_list,
                     &ix->post_tmp, &ix->lt_keys, &ix->lt_cnt, &ix->lt_g, &ix->lt_pos, &ix->verify_defer, &ix->pairs,
                     &ix->pair_ub, &ix->chunk_list, &ix->chunk_docs, &ix->chunk_fail, &ix->uchunk, &ix->canon_of_slot,
                     &ix->tvals, &ix->term_tmp, &ix->term_esc, &ix->sent_slot, &ix->vcounts, &ix->vnu, &ix->vt_table,
@@ -1266,6 +1288,16 @@ static void set_last_ms(tfidf_index *ix, float scoring, float total) {
   ix->last_ms_total = total;
 }
 
+// host time since tfidf_commit began (tfidf_commit_host_profile)
+static double prof_ms(const tfidf_index *ix) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ix->prof_t0).count();
+}
+// a host wait of the commit for its stream, counted for tfidf_commit_host_profile
+static hipError_t commit_sync(tfidf_index *ix, hipStream_t s) {
+  ix->prof.stream_syncs++;
+  return hipStreamSynchronize(s);
+}
+
 // One index build with ix->hash_seed; kRcCollision when two different terms
 // met under one hashed key (tfidf_commit then rebuilds with another seed).
 constexpr int kRcCollision = -1000;
@@ -1278,8 +1310,10 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   hipStream_t s = ix->stream;
   // what the target covers; it covers nothing until this build has succeeded
   const uint64_t kept_docs = S.tok_docs, kept_inv = S.inv_docs;
+  const bool mir_was_ok = S.mir_ok;
   S.tok_docs = 0;
   S.inv_docs = 0;
+  S.mir_ok = false;
   // live documents
   S.n_docs = ix->n_staged - ix->n_dead;
   S.live_map.clear();
@@ -1338,6 +1372,9 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
                                       knob(commit_knob_names()[kKnobFullCommit]));
   const uint64_t d_first = plan.full ? 0 : plan.d_first;
   const uint64_t kept_esc = plan.full ? 0 : S.h_esc.size();
+  // an incremental block-major commit without new documents over a valid crank: the columns are those of
+  // the target's last inversion
+  const bool keep_rank = !plan.full && !S.term_major && kept_inv != 0 && N == d_first;
   ix->last_tok_docs = N - d_first;
   ix->last_tok_full = plan.full ? 1u : 0u;
   // the kept totals (the tokenizers' counters start at 0 and count the new documents)
@@ -1363,10 +1400,10 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   if (int rc = grow_keep(ix, &S.doc_nuniq, N * 4 + 4, d_first * 4)) return rc;
   if (int rc = grow_keep(ix, &S.doc_norm, N + 16, d_first)) return rc;
   if (int rc = grow_keep(ix, &S.rsplit, N * S.R * 4 + 4, d_first * S.R * 4)) return rc;
-  HIP_TRY(ix->long_list.reserve(N * 4 + 4));
-  HIP_TRY(ix->uni_list.reserve(N * 4 + 4));
+  HIP_TRY(ix->long_list.reserve_slack(N * 4 + 4));
+  HIP_TRY(ix->uni_list.reserve_slack(N * 4 + 4));
   HIP_TRY(ix->counters.reserve(128));
-  HIP_TRY(ix->bad_list.reserve(N * 4 + 4));
+  HIP_TRY(ix->bad_list.reserve_slack(N * 4 + 4));
   // Short-document corpora: the wave path indexes packs of consecutive
   // documents per window (about kPackBytes of text per pack; SURVEY cfg 5
   // shape: 6 documents of ~330 B).  TFIDF_PACK_DOCS overrides (tests).
@@ -1377,7 +1414,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     if (const char *e = knob("TFIDF_PACK_DOCS")) pack = (uint32_t)std::max(1, std::min(atoi(e), (int)kPackMaxDocs));
     pack = std::min(pack, std::max(1u, kWaveGroups / S.R));   // (document, range) groups per unit
   }
-  if (pack > 1) HIP_TRY(ix->retry_list.reserve(N * 4 + 4));
+  if (pack > 1) HIP_TRY(ix->retry_list.reserve_slack(N * 4 + 4));
   if (S.term_major) {
     HIP_TRY(S.row_off.reserve(N * 4 + 4));
     HIP_TRY(S.toff.reserve(((size_t)C + 1) * 8));
@@ -1388,8 +1425,11 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     HIP_TRY(S.crank.reserve(((size_t)C / 32 + 1) * 8));
     HIP_TRY(S.crank_inv.reserve(((size_t)C / 32 + 1) * 8));
     // the crank the kept blk rows were laid out by stays in crank_inv; col_rank writes the other buffer
-    std::swap(S.crank.p, S.crank_inv.p);
-    std::swap(S.crank.bytes, S.crank_inv.bytes);
+    // (nothing tokenized: no kernel touches the dictionary, crank and NC stand and col_rank does not run)
+    if (!keep_rank) {
+      std::swap(S.crank.p, S.crank_inv.p);
+      std::swap(S.crank.bytes, S.crank_inv.bytes);
+    }
     HIP_TRY(S.sdf.reserve((size_t)C * 4));
   }
 
@@ -1410,8 +1450,8 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   const char *nouw = knob("TFIDF_NO_UNIWAVE");
   const bool uni_on = !(nouw && *nouw && *nouw != '0');
   const bool uni_first = ix->uni_first && uni_on && pack == 1 && !knob("TFIDF_NO_UNIFIRST");
-  // (the flag scans read all N flags: those of the kept documents stay 0)
-  if (!uni_first || d_first) HIP_TRY(hipMemsetAsync(ix->uni_list.p, 0, (size_t)N * 4, s));
+  // (the flag scans read all N flags: those of the kept documents stay 0; without new documents none runs)
+  if ((!uni_first || d_first) && N > d_first) HIP_TRY(hipMemsetAsync(ix->uni_list.p, 0, (size_t)N * 4, s));
   if (uni_first && N > d_first)
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(ix->uni_list.as<uint32_t>() + d_first), 1, N - d_first, s));
 
@@ -1475,7 +1515,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     if (pack > 1 && !bp.debug_stop) {       // documents the packs could not take: one per wave
       uint32_t n_retry = 0;
       HIP_TRY(hipMemcpyAsync(&n_retry, ctr + 5, 4, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
+      HIP_TRY(commit_sync(ix, s));
       S.pack_retried = kept.pack_retried + n_retry;
       if (n_retry) {
         BuildParams rp = bp;
@@ -1497,7 +1537,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   }
   HIP_TRY(hipEventRecord(ix->ev[EV_TOK], s));
   if (bp.debug_stop) {                      // profiling only: rows are incomplete, stop here
-    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(commit_sync(ix, s));
     ix->timing = tfidf_commit_timing{};
     ix->timing.ms_tokenize = ev_ms(ix, EV_START, EV_TOK);
     ix->timing.ms_total = ix->timing.ms_tokenize;
@@ -1508,9 +1548,11 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   // block-major: columns of the dictionary as it stands (final unless the
   // long path runs below, which recomputes them); their count lands in ctr[7]
   auto col_rank = [&]() -> int {
-    if (!S.term_major)
+    if (!S.term_major && !keep_rank) {
       HIP_TRY(launch_col_rank(S.dict.as<uint64_t>(), C, S.crank.as<uint2>(),
                               reinterpret_cast<unsigned long long *>(ctr + 7), s));
+      ix->prof.col_rank_runs++;
+    }
     return TFIDF_OK;
   };
   if (int rc = col_rank()) return rc;
@@ -1520,7 +1562,8 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   HIP_TRY(ix->hctr_h.resize(14));                      // pinned: a pageable read is staged by the runtime
   uint64_t *hctr = ix->hctr_h.data();
   HIP_TRY(hipMemcpyAsync(hctr, ctr, 14 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(commit_sync(ix, s));
+  ix->prof.ms_counters = prof_ms(ix);
   const uint32_t n_long = (uint32_t)hctr[4], n_uni = (uint32_t)hctr[6];
   S.long_chunked = kept.long_chunked;
   S.long_docs = kept.long_docs + n_long;
@@ -1536,7 +1579,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     PinnedVec<uint32_t> &ldocs = ix->ldocs_h;
     HIP_TRY(ldocs.resize(n_long));
     HIP_TRY(hipMemcpyAsync(ldocs.data(), ix->long_list.p, (size_t)n_long * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(commit_sync(ix, s));
     // pair buckets: at most 64, each a whole number of k_long_rows' LDS windows
     const uint32_t wlog = std::min<uint32_t>(ix->cap_log2, kLrWinBits);
     const uint32_t bsh = std::max<uint32_t>(wlog, ix->cap_log2 > 6 ? ix->cap_log2 - 6 : 0);
@@ -1606,7 +1649,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     }
     uint32_t n_fb = 0;
     HIP_TRY(hipMemcpyAsync(&n_fb, bp.long_count, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(commit_sync(ix, s));
     S.long_chunked = kept.long_chunked + n_long - n_fb;
     if (n_fb) {
       uint32_t lg = ix->cap_log2 + 1;
@@ -1636,7 +1679,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     HIP_TRY(hipEventRecord(ix->ev[EV_LONG], s));
     if (int rc = col_rank()) return rc;
     HIP_TRY(hipMemcpyAsync(hctr, ctr, 10 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(commit_sync(ix, s));
   }
   const uint32_t err = (uint32_t)(hctr[3] & 0xFFFFFFFFu), err_doc = (uint32_t)(hctr[3] >> 32);
   if (err & kErrCollision) { ix->collision_doc = err_doc; return kRcCollision; }
@@ -1649,7 +1692,25 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   S.doc_count = kept.doc_count + hctr[0];
   S.sum_ttf = kept.sum_ttf + hctr[1];
   S.nnz = kept.nnz + hctr[2];
-  S.NC = S.term_major ? 0u : (uint32_t)hctr[7];
+  S.NC = S.term_major ? 0u : keep_rank ? S.NC_inv : (uint32_t)hctr[7];
+  // Statistics in force: the shard's own (a GLOBAL exchange publishes another
+  // view).  doc_count and sum_ttf are final here, so the BM25 norm cache is
+  // uploaded ahead of the inversion and the commit's last synchronisation
+  // covers it.  The stream was synchronised by the counter read just above, so
+  // no earlier upload out of the view's staging array is pending (wait_gdf:
+  // nor one behind a GLOBAL setter's event), and the view's first use follows
+  // the publish.  A build that fails below leaves a target that covers
+  // nothing; its private view is never seen by a search.
+  if (!S.stats || S.stats.use_count() > 1) S.stats = std::make_shared<StatsView>(ix->cfg.device);
+  {
+    StatsView &V = *S.stats;
+    if (int rc = V.wait_gdf()) return rc;
+    V.global = false;
+    V.gdf.clear();
+    V.doc_count = S.doc_count;
+    V.sum_ttf = S.sum_ttf;
+    if (int rc = upload_cache(ix->cfg, V, s, false)) return rc;
+  }
   // Block-major: the blocks kept from the target's last inversion.  Their blk
   // rows (offset form), bases and postings depend on their own documents' rows
   // and norms and on the slot -> column map only; when the dictionary gained
@@ -1657,6 +1718,22 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   const InversionPlan inv = inversion_plan(plan.full, S.term_major, kept_inv, N, S.NC, S.NC_inv,
                                            knob("TFIDF_FULL_INVERSION"));
   const uint32_t first_block = inv.first_block;
+  // ... and how the host mirrors follow (commit_plan.h): whole, or the new slots and changed df alone
+  uint32_t df_cap = kDfDeltaCap;
+  if (const char *e = knob("TFIDF_TEST_DF_DELTA_CAP")) df_cap = (uint32_t)std::max(1, std::min(atoi(e), (int)kDfDeltaCap));
+  const MirrorPlan mp = mirror_plan(plan.full, S.term_major, kept_inv, mir_was_ok, C, S.NC, S.NC_inv, hctr[2], df_cap,
+                                    knob("TFIDF_FULL_MIRROR"));
+  // the fused delta kernel builds either list; it replaces k_df_slots only when one is wanted
+  const bool dict_delta = mp.dict == kMirrorDelta, df_delta = mp.df == kMirrorDelta;
+  const bool dict_whole = mp.dict == kMirrorWhole, df_whole = mp.df == kMirrorWhole, crank_whole = mp.crank == kMirrorWhole;
+  if (dict_delta) {
+    HIP_TRY(ix->mir_dict_list.reserve((size_t)dict_delta_max(C) * sizeof(DictDelta)));
+    HIP_TRY(ix->h_dict_delta.resize(dict_delta_max(C)));
+  }
+  if (df_delta) {
+    HIP_TRY(ix->mir_df_list.reserve((size_t)kDfDeltaCap * sizeof(DfDelta)));
+    HIP_TRY(ix->h_df_delta.resize(kDfDeltaCap));
+  }
   const uint64_t kept_post = first_block ? S.h_bbase[first_block] : 0;      // postings of the kept blocks
   const uint64_t kept_pe = first_block ? post_esc_keep(S.h_post_esc, kept_post) : 0;
   ix->last_inv_first = first_block;
@@ -1687,17 +1764,17 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     if (ea.count) {
       HIP_TRY(hipMemcpyAsync(S.h_esc.data() + ea.first, S.csr_esc.as<uint64_t>() + ea.first, ea.count * 8,
                              hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
+      HIP_TRY(commit_sync(ix, s));
       esc_merge(&S.h_esc, ea.first);
       HIP_TRY(hipMemcpyAsync(S.csr_esc.p, S.h_esc.data(), n_esc * 8, hipMemcpyHostToDevice, s));
-      HIP_TRY(hipStreamSynchronize(s));
+      HIP_TRY(commit_sync(ix, s));
     }
   }
   if (S.nnz >= 0xFFFFFFFFull) return fail(TFIDF_E_CAPACITY, "more than 2^32 postings per shard");
   // postings: block-major u32 (post_word), term-major u64; pass-1 temp words u32
   // (term-major: the sort's u64 value buffer)
   if (int rc = grow_keep(ix, &S.post, S.nnz * (S.term_major ? 8 : 4) + 8, kept_post * 4)) return rc;
-  HIP_TRY(ix->post_tmp.reserve(S.nnz * (S.term_major ? 8 : 4) + 8));
+  HIP_TRY(ix->post_tmp.reserve_slack(S.nnz * (S.term_major ? 8 : 4) + 8));
   const uint64_t post_esc_cap = row_cap / kPostTfEsc + 64;       // each needs tf >= 2047 tokens of one doc
   // (the kept blocks' escapes are the first kept_pe of the sorted list; new ones are appended behind them)
   if (!S.term_major)
@@ -1719,7 +1796,9 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   const bool mirror_side = (!mirror_main && s == ix->own_stream) || (size_t)2 * C * 8 >= (32u << 20);
   // (the side-stream work is enqueued after the inversion's launches, so the
   // host's enqueue time does not delay the first inversion kernel)
-  if (mirror_side) HIP_TRY(hipEventRecord(ix->mir_ev[0], s));
+  // (delta mirrors without new documents: nothing to copy, no deferred check was queued: no side-stream work)
+  const bool side_work = mirror_side && !(mp.delta && N == d_first);
+  if (side_work) HIP_TRY(hipEventRecord(ix->mir_ev[0], s));
 
   PostingParams pp{};
   pp.offsets = bp.offsets;
@@ -1771,7 +1850,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     tp.doc_nuniq = bp.doc_nuniq;
     tp.doc_norm = bp.doc_norm;
     tp.row_off = S.row_off.as<uint32_t>();
-    HIP_TRY(ix->tvals.reserve(S.nnz * 8 + 16));
+    HIP_TRY(ix->tvals.reserve_slack(S.nnz * 8 + 16));
     tp.keys = ix->post_tmp.as<uint64_t>();
     tp.keys_alt = ix->tvals.as<uint64_t>();
     tp.post = S.post.as<uint64_t>();
@@ -1792,10 +1871,11 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     {   // tf >= 4095 (rare): the escape list sorted for the postings pass's binary search
       uint32_t ne = 0;
       HIP_TRY(hipMemcpyAsync(&ne, tp.tesc_count, 4, hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
+      HIP_TRY(commit_sync(ix, s));
       if (ne > tp.tesc_cap) return fail(TFIDF_E_CAPACITY, "term-major escape list overflow");
       if (ne) {
         std::vector<std::pair<uint64_t, uint64_t>> h(ne);
+        ix->prof.stream_syncs++;
         HIP_TRY(hipMemcpy(h.data(), tp.tesc, ne * 16, hipMemcpyDeviceToHost));
         std::sort(h.begin(), h.end());
         HIP_TRY(hipMemcpy(tp.tesc, h.data(), ne * 16, hipMemcpyHostToDevice));
@@ -1813,9 +1893,28 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     }
     HIP_TRY(hipEventRecord(ix->ev[EV_DF], s));
     HIP_TRY(launch_df_sum(pp, s));
-    HIP_TRY(launch_df_slots(S.crank.as<uint2>(), S.blk.as<uint32_t>() + (size_t)S.n_blocks * S.NC, C,
-                            S.sdf.as<uint32_t>(), s));
-    if (mirror_side) HIP_TRY(hipEventRecord(ix->mir_ev[2], s));   // df final: its host mirror copies beside the scatter
+    if (dict_delta || df_delta) {
+      // sdf still holds the df of this snapshot's last build, crank_inv its occupancy: the slots that
+      // differ are listed while sdf is rewritten (counts: ctr[14] df, ctr[15] dictionary)
+      MirrorDeltaParams dp{};
+      dp.crank = S.crank.as<uint2>();
+      dp.crank_inv = S.crank_inv.as<uint2>();
+      dp.df_col = S.blk.as<uint32_t>() + (size_t)S.n_blocks * S.NC;
+      dp.C = C;
+      dp.df_slot = S.sdf.as<uint32_t>();
+      dp.dict = S.dict.as<uint64_t>();
+      dp.dict_list = dict_delta ? ix->mir_dict_list.as<DictDelta>() : nullptr;
+      dp.dict_cap = mp.n_new;
+      dp.dict_count = reinterpret_cast<uint32_t *>(ctr + 15);
+      dp.df_list = df_delta ? ix->mir_df_list.as<DfDelta>() : nullptr;
+      dp.df_cap = df_cap;
+      dp.df_count = reinterpret_cast<uint32_t *>(ctr + 14);
+      HIP_TRY(launch_df_slots_delta(dp, s));
+    } else {
+      HIP_TRY(launch_df_slots(S.crank.as<uint2>(), S.blk.as<uint32_t>() + (size_t)S.n_blocks * S.NC, C,
+                              S.sdf.as<uint32_t>(), s));
+    }
+    if (side_work) HIP_TRY(hipEventRecord(ix->mir_ev[2], s));   // df final: its host mirror copies beside the scatter
     if (S.n_blocks) HIP_TRY(launch_row_scan(pp, s));
     HIP_TRY(hipEventRecord(ix->ev[EV_BSCAN], s));
     HIP_TRY(launch_block_base(pp, s));
@@ -1823,9 +1922,10 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     if (S.n_blocks) HIP_TRY(launch_scatter(pp, s));
     HIP_TRY(hipEventRecord(ix->ev[EV_SCAT], s));
   }
-  if (mirror_side) {
+  if (side_work) {
     HIP_TRY(hipStreamWaitEvent(ix->copy_stream, ix->mir_ev[0], 0));
-    HIP_TRY(hipMemcpyAsync(S.h_dict.data(), S.dict.p, (size_t)2 * C * 8, hipMemcpyDeviceToHost, ix->copy_stream));
+    if (dict_whole)
+      HIP_TRY(hipMemcpyAsync(S.h_dict.data(), S.dict.p, (size_t)2 * C * 8, hipMemcpyDeviceToHost, ix->copy_stream));
     HIP_TRY(launch_verify_deferred(bp, ix->copy_stream));
     if (S.term_major)       // (block-major: col_rank counted the columns)
       HIP_TRY(launch_count_nonzero(S.dict.as<uint64_t>(), C, reinterpret_cast<unsigned long long *>(ctr + 7),
@@ -1835,25 +1935,47 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
       // scatter, so their host mirrors copy while it runs (on the main stream
       // after it they cost ~0.1 ms of the cfg-2 step)
       HIP_TRY(hipStreamWaitEvent(ix->copy_stream, ix->mir_ev[2], 0));
-      HIP_TRY(hipMemcpyAsync(S.h_df.data(), S.df_dev(), (size_t)C * 4, hipMemcpyDeviceToHost, ix->copy_stream));
+      if (df_whole)
+        HIP_TRY(hipMemcpyAsync(S.h_df.data(), S.df_dev(), (size_t)C * 4, hipMemcpyDeviceToHost, ix->copy_stream));
       HIP_TRY(S.h_crank.resize((size_t)C / 32 + 1));
-      HIP_TRY(hipMemcpyAsync(S.h_crank.data(), S.crank.p, ((size_t)C / 32 + 1) * 8, hipMemcpyDeviceToHost,
-                             ix->copy_stream));
+      if (crank_whole)
+        HIP_TRY(hipMemcpyAsync(S.h_crank.data(), S.crank.p, ((size_t)C / 32 + 1) * 8, hipMemcpyDeviceToHost,
+                               ix->copy_stream));
+      // the new slots' keys: the list's length is known (n_new), so it is copied here and checked below
+      if (dict_delta)
+        HIP_TRY(hipMemcpyAsync(ix->h_dict_delta.data(), ix->mir_dict_list.p, (size_t)mp.n_new * sizeof(DictDelta),
+                               hipMemcpyDeviceToHost, ix->copy_stream));
     }
     HIP_TRY(hipEventRecord(ix->mir_ev[1], ix->copy_stream));
   }
+  {
+    tfidf_host_profile &pf = ix->prof;
+    pf.mirror_dict = mp.dict;
+    pf.mirror_df = mp.df;
+    pf.mirror_crank = S.term_major ? (uint32_t)TFIDF_MIRROR_NONE : (uint32_t)mp.crank;
+    if (dict_whole) pf.bytes_dict += (uint64_t)2 * C * 8;
+    if (dict_delta) pf.bytes_dict += (uint64_t)mp.n_new * sizeof(DictDelta);
+    if (df_whole) pf.bytes_df += (uint64_t)C * 4;
+    if (crank_whole && !S.term_major) pf.bytes_crank += ((uint64_t)C / 32 + 1) * 8;
+    pf.dict_delta_entries = dict_delta ? mp.n_new : 0;
+    pf.df_delta_entries = 0;
+  }
   // host mirrors for query analysis: dictionary keys + df
-  if (!mirror_side)
+  if (!mirror_side && dict_whole)
     HIP_TRY(hipMemcpyAsync(S.h_dict.data(), S.dict.p, (size_t)2 * C * 8, hipMemcpyDeviceToHost, s));
-  if (!mirror_side || S.term_major)
+  if ((!mirror_side || S.term_major) && df_whole)
     HIP_TRY(hipMemcpyAsync(S.h_df.data(), S.df_dev(), (size_t)C * 4, hipMemcpyDeviceToHost, s));
   if (!S.term_major && !mirror_side) {                 // slot -> column for query preparation
     HIP_TRY(S.h_crank.resize((size_t)C / 32 + 1));
-    HIP_TRY(hipMemcpyAsync(S.h_crank.data(), S.crank.p, ((size_t)C / 32 + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (crank_whole)
+      HIP_TRY(hipMemcpyAsync(S.h_crank.data(), S.crank.p, ((size_t)C / 32 + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (dict_delta)
+      HIP_TRY(hipMemcpyAsync(ix->h_dict_delta.data(), ix->mir_dict_list.p, (size_t)mp.n_new * sizeof(DictDelta),
+                             hipMemcpyDeviceToHost, s));
   }
-  if (mirror_side) {
+  if (side_work) {
     HIP_TRY(hipStreamWaitEvent(s, ix->mir_ev[1], 0));   // mirror, checks and count (side stream)
-  } else {
+  } else if (!mirror_side) {
     // hashed-key identity checks the tokenizers had to defer
     HIP_TRY(launch_verify_deferred(bp, s));
     // occupied dictionary slots counted on the device (ctr[7]) instead of a host
@@ -1861,13 +1983,16 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     if (S.term_major)
       HIP_TRY(launch_count_nonzero(S.dict.as<uint64_t>(), C, reinterpret_cast<unsigned long long *>(ctr + 7), s));
   }
-  uint64_t tail[8];              // ctr[3] error flags .. ctr[7] occupied slots, [8] malformed, [10] posting escapes
+  // ctr[3] error flags .. ctr[7] occupied slots, [8] malformed, [10] posting escapes, [14] / [15] delta list counts
+  uint64_t tail[13];
   HIP_TRY(hipMemcpyAsync(tail, ctr + 3, sizeof tail, hipMemcpyDeviceToHost, s));
   if (!S.term_major) {           // the block bases: the next commit's kept postings and escapes are found by them
     HIP_TRY(S.h_bbase.resize((size_t)S.n_blocks + 2));
     HIP_TRY(hipMemcpyAsync(S.h_bbase.data(), S.bbase.p, ((size_t)S.n_blocks + 1) * 8, hipMemcpyDeviceToHost, s));
   }
-  HIP_TRY(hipStreamSynchronize(s));
+  ix->prof.ms_enqueued = prof_ms(ix);
+  HIP_TRY(commit_sync(ix, s));
+  ix->prof.ms_synced = prof_ms(ix);
   {
     // rare (tf >= 2047): sorted for the scorer's binary search.  The kept
     // blocks' entries stand; the new ones were appended behind them.
@@ -1876,6 +2001,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     const uint64_t n_pe = pe.first + pe.count;
     S.h_post_esc.resize(n_pe);
     if (pe.count) {
+      ix->prof.stream_syncs++;
       HIP_TRY(hipMemcpy(S.h_post_esc.data() + pe.first, S.post_esc.as<uint64_t>() + pe.first, pe.count * 8,
                         hipMemcpyDeviceToHost));
       esc_merge(&S.h_post_esc, pe.first);
@@ -1884,13 +2010,43 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   }
   if (const uint32_t n_bad = (uint32_t)tail[5]) {   // (incremental: S.malformed holds the kept documents' ids)
     std::vector<uint32_t> bad(n_bad);
+    ix->prof.stream_syncs++;
     HIP_TRY(hipMemcpy(bad.data(), ix->bad_list.p, (size_t)n_bad * 4, hipMemcpyDeviceToHost));
     merge_malformed(&S.malformed, bad.data(), n_bad);
   }
   const uint32_t err2 = (uint32_t)tail[0];
   if (err2 & kErrCollision) { ix->collision_doc = (uint32_t)(tail[0] >> 32); return kRcCollision; }
   if (err2 & kErrTfTooLarge) return fail(TFIDF_E_UNSUPPORTED_INPUT, "a term frequency exceeds 2^24 - 1");
-  S.num_terms = tail[4];
+  // The mirrors' deltas, now that the build is known good (a failed one leaves
+  // mir_ok false, and the next build copies whole).  The dictionary list's
+  // length was known in advance; the device must have found exactly as many.
+  if (dict_delta) {
+    if ((uint32_t)tail[12] != mp.n_new)
+      return fail(TFIDF_E_STATE, "dictionary mirror delta: %u new slots listed, %u expected", (uint32_t)tail[12],
+                  mp.n_new);
+    if (!apply_dict_delta(S.h_dict.data(), C, ix->h_dict_delta.data(), mp.n_new))
+      return fail(TFIDF_E_STATE, "dictionary mirror delta names a slot past the dictionary");
+  }
+  if (df_delta) {
+    const uint32_t n_df = (uint32_t)tail[11];
+    if (n_df > df_cap) {               // the list overflowed (entries past the cap were counted, not stored)
+      ix->prof.stream_syncs++;
+      HIP_TRY(hipMemcpy(S.h_df.data(), S.df_dev(), (size_t)C * 4, hipMemcpyDeviceToHost));
+      ix->prof.mirror_df = TFIDF_MIRROR_WHOLE;
+      ix->prof.bytes_df += (uint64_t)C * 4;
+    } else {
+      if (n_df) {
+        HIP_TRY(hipMemcpyAsync(ix->h_df_delta.data(), ix->mir_df_list.p, (size_t)n_df * sizeof(DfDelta),
+                               hipMemcpyDeviceToHost, s));
+        HIP_TRY(commit_sync(ix, s));
+        if (!apply_df_delta(S.h_df.data(), C, ix->h_df_delta.data(), n_df))
+          return fail(TFIDF_E_STATE, "df mirror delta names a slot past the dictionary");
+      }
+      ix->prof.bytes_df += (uint64_t)n_df * sizeof(DfDelta);
+      ix->prof.df_delta_entries = n_df;
+    }
+  }
+  S.num_terms = keep_rank ? S.NC : tail[4];     // (col_rank counts the occupied slots into ctr[7]; it did not run)
 
   tfidf_commit_timing &t = ix->timing;
   t.ms_tokenize = ev_ms(ix, EV_START, EV_TOK);
@@ -1921,15 +2077,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     std::lock_guard<std::mutex> ml(S.mlt_mu);
     S.mlt_ready = false;
   }
-  // statistics in force: the shard's own (a GLOBAL exchange publishes another view)
-  if (!S.stats || S.stats.use_count() > 1) S.stats = std::make_shared<StatsView>(ix->cfg.device);
-  StatsView &V = *S.stats;
-  if (int rc = V.wait_gdf()) return rc;
-  V.global = false;
-  V.gdf.clear();
-  V.doc_count = S.doc_count;
-  V.sum_ttf = S.sum_ttf;
-  if (int rc = upload_cache(ix->cfg, V, s)) return rc;
+  S.mir_ok = true;                     // the mirrors match dict, sdf / tdf and crank
   S.tok_docs = ix->n_staged;           // the rows and the dictionary cover every staged document
   if (!S.term_major) {                 // ... and so do blk (laid out by crank, NC columns), bbase and post
     S.inv_docs = ix->n_staged;
@@ -1942,6 +2090,12 @@ extern "C" int tfidf_commit(tfidf_index *ix) {
   if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
   std::lock_guard<std::mutex> lk(ix->mu);
   DeviceGuard g(ix->cfg.device);
+  ix->prof = tfidf_host_profile{};
+  ix->prof_t0 = std::chrono::steady_clock::now();
+  struct Wall {                                // (every return below)
+    tfidf_index *ix;
+    ~Wall() { ix->prof.ms_wall = prof_ms(ix); }
+  } wall{ix};
   // tfidf_set_compact_threshold: reclaim the dead documents first.  A
   // compaction that cannot get its memory leaves the index as it was, and the
   // commit builds through live_map as it always has.
@@ -1987,6 +2141,7 @@ extern "C" int tfidf_commit(tfidf_index *ix) {
       std::lock_guard<std::mutex> sl(ix->snap_mu);
       std::swap(ix->cur, S);                   // published; S = the previous snapshot
     }
+    ix->prof.ms_published = prof_ms(ix);
     ix->spare = std::move(S);                  // rebuilt in place next time if no search holds it
     return TFIDF_OK;
   }
@@ -2005,6 +2160,13 @@ extern "C" int tfidf_commit_tokenized_docs(const tfidf_index *ix, uint64_t *docs
   std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->mu);
   if (docs) *docs = ix->last_tok_docs;
   if (was_full) *was_full = ix->last_tok_full;
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_commit_host_profile(const tfidf_index *ix, tfidf_host_profile *out) {
+  if (!ix || !out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->mu);
+  *out = ix->prof;
   return TFIDF_OK;
 }
 

@@ -300,6 +300,23 @@ hipError_t launch_count_nonzero(const uint64_t *a, uint32_t n, unsigned long lon
 // block-major columns: crank over the final dictionary (total -> *n_cols), per-slot df from the column df
 hipError_t launch_col_rank(const uint64_t *dict_lo, uint32_t C, uint2 *crank, unsigned long long *n_cols, hipStream_t s);
 hipError_t launch_df_slots(const uint2 *crank, const uint32_t *df_col, uint32_t C, uint32_t *df_slot, hipStream_t s);
+// ... and, for the host mirrors' deltas (commit_plan.h), the slots whose df changed and the new slots' keys
+struct DictDelta;
+struct DfDelta;
+struct MirrorDeltaParams {
+  const uint2 *crank, *crank_inv;      // now / at the snapshot's last build (crank_inv: read for dict_list only)
+  const uint32_t *df_col;
+  uint32_t C;
+  uint32_t *df_slot;                   // read (the last build's values), then written
+  const uint64_t *dict;                // lo plane [0, C), hi plane [C, 2 C)
+  DictDelta *dict_list;                // nullptr: not built
+  uint32_t dict_cap;
+  uint32_t *dict_count;
+  DfDelta *df_list;                    // nullptr: not built
+  uint32_t df_cap;
+  uint32_t *df_count;
+};
+hipError_t launch_df_slots_delta(const MirrorDeltaParams &p, hipStream_t s);
 hipError_t launch_scatter(const PostingParams &p, hipStream_t s);
 // kept blk rows [0, rows) from the column layout of crank_inv (stride NC_inv) to that of p.crank (p.blk, stride p.NC)
 hipError_t launch_blk_remap(const PostingParams &p, const uint32_t *blk_old, const uint2 *crank_inv, uint32_t NC_inv,

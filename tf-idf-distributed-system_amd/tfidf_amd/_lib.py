@@ -53,6 +53,17 @@ class CommitTiming(C.Structure):
                [(n, C.c_uint64) for n in ("text_bytes", "num_docs", "nnz")]
 
 
+class HostProfile(C.Structure):
+    """tfidf_host_profile: the host side of the last commit."""
+    _fields_ = [(n, C.c_double) for n in ("ms_wall", "ms_counters", "ms_enqueued", "ms_synced", "ms_published")] + \
+               [(n, C.c_uint32) for n in ("stream_syncs", "col_rank_runs", "mirror_dict", "mirror_df", "mirror_crank",
+                                          "dict_delta_entries", "df_delta_entries")] + \
+               [(n, C.c_uint64) for n in ("bytes_dict", "bytes_df", "bytes_crank")]
+
+
+MIRROR_FORMS = ("none", "delta", "whole")        # TFIDF_MIRROR_*
+
+
 class TfidfError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libtfidf error %d: %s" % (code, msg))
@@ -211,6 +222,7 @@ SIGNATURES = {
     "tfidf_get_commit_timing": (C.c_int, [VP, C.POINTER(CommitTiming)]),
     "tfidf_commit_tokenized_docs": (C.c_int, [VP, U64P, U32P]),
     "tfidf_commit_inverted_blocks": (C.c_int, [VP, U32P, U32P, U32P]),
+    "tfidf_commit_host_profile": (C.c_int, [VP, C.POINTER(HostProfile)]),
     "tfidf_stats": (C.c_int, [VP, C.POINTER(IndexStats)]),
     "tfidf_search": (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, U32P, F32P, C.c_uint64, U64P]),
     "tfidf_search_coalesced": (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, U32P, F32P, C.c_uint64, U64P,

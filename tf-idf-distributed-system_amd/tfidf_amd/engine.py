@@ -859,6 +859,17 @@ class ShardIndex:
         L.check(L.load().tfidf_commit_inverted_blocks(self._h, C.byref(f), C.byref(n), C.byref(r)))
         return {"first_block": f.value, "n_blocks": n.value, "remapped": r.value}
 
+    def commit_host_profile(self):
+        """The host side of the last commit (tfidf_commit_host_profile): host times in ms since the call
+        began, stream synchronisations, and per mirror (dict, df, crank) its form ("none" / "delta" /
+        "whole") and the bytes copied device -> host."""
+        p = L.HostProfile()
+        L.check(L.load().tfidf_commit_host_profile(self._h, C.byref(p)))
+        out = {f: getattr(p, f) for f, _ in L.HostProfile._fields_}
+        for m in ("mirror_dict", "mirror_df", "mirror_crank"):
+            out[m] = L.MIRROR_FORMS[out[m]]
+        return out
+
     def stats(self):
         s = L.IndexStats()
         L.check(L.load().tfidf_stats(self._h, C.byref(s)))

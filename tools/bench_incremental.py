@@ -12,11 +12,14 @@ and reports per commit the host wall time, the device phases
 (tfidf_commit_tokenized_docs; null with a library that has no such call, which
 tokenizes everything every time) and which blocks its inversion built
 (tfidf_commit_inverted_blocks: first_block, n_blocks, remapped; null with a
-library that has no such call, which inverts every block every time).  Commits alternate between two snapshots, so
+library that has no such call, which inverts every block every time), and the host
+side (tfidf_commit_host_profile: host times, stream synchronisations, the form and
+bytes of each mirror; null with a library that has no such call).  Commits alternate between two snapshots, so
 every new document is tokenized once for each of them: a commit that adds n
 documents tokenizes about 2n (the n of the commit before, and its own).
 TFIDF_DEBUG=1 TFIDF_FULL_COMMIT=1 gives the full-build numbers on the same library,
 TFIDF_DEBUG=1 TFIDF_FULL_INVERSION=1 those of incremental tokenizing with every block inverted.
+TFIDF_DEBUG=1 TFIDF_FULL_MIRROR=1 those with the host mirrors copied whole by every commit.
 One JSON line on stdout; --out writes it to a file as well.
 """
 import argparse
@@ -37,7 +40,8 @@ from tfidf_amd.engine import ShardIndex  # noqa: E402
 PHASES = ("ms_tokenize", "ms_long", "ms_df", "ms_blockscan", "ms_colscan", "ms_scatter", "ms_total")
 
 
-ACCESSORS = ("tfidf_commit_inverted_blocks", "tfidf_commit_tokenized_docs")   # newest first
+ACCESSORS = ("tfidf_commit_host_profile", "tfidf_commit_inverted_blocks", "tfidf_commit_tokenized_docs")   # newest first
+HOST_MS = ("ms_wall", "ms_counters", "ms_enqueued", "ms_synced", "ms_published")
 
 
 def load_library():
@@ -60,7 +64,8 @@ def commit(idx, have):
     t = idx.commit_timing()
     tok = idx.commit_tokenized_docs() if "tfidf_commit_tokenized_docs" in have else None
     inv = idx.commit_inverted_blocks() if "tfidf_commit_inverted_blocks" in have else {}
-    return {"wall_ms": wall, **{k: t[k] for k in PHASES},
+    host = idx.commit_host_profile() if "tfidf_commit_host_profile" in have else None
+    return {"wall_ms": wall, **{k: t[k] for k in PHASES}, "host": host,
             "tokenized_docs": tok and tok["docs"], "was_full": tok and tok["was_full"],
             "first_block": inv.get("first_block"), "n_blocks": inv.get("n_blocks"), "remapped": inv.get("remapped")}
 
@@ -71,6 +76,20 @@ def summary(rows):
     out["tokenized_docs"] = [r["tokenized_docs"] for r in rows]
     for k in ("first_block", "n_blocks", "remapped"):
         out[k] = [r[k] for r in rows]
+    # the host side (tfidf_commit_host_profile; null with a library that has no such call): medians of the
+    # points and of the bytes mirrored, the synchronisation counts and how often each mirror took which form
+    hosts = [r["host"] for r in rows]
+    if all(hosts):
+        h = {k: float(np.median([x[k] for x in hosts])) for k in HOST_MS}
+        for k in ("bytes_dict", "bytes_df", "bytes_crank", "dict_delta_entries", "df_delta_entries"):
+            h[k] = float(np.median([x[k] for x in hosts]))
+        h["stream_syncs"] = sorted(set(x["stream_syncs"] for x in hosts))
+        h["col_rank_runs"] = sorted(set(x["col_rank_runs"] for x in hosts))
+        for m in ("mirror_dict", "mirror_df", "mirror_crank"):
+            h[m] = {f: sum(x[m] == f for x in hosts) for f in ("none", "delta", "whole")}
+        out["host"] = h
+    else:
+        out["host"] = None
     return out
 
 
@@ -108,6 +127,8 @@ def main():
     s = idx.stats()
     res = {"bench": "incremental_commit", "library_has_accessor": "tfidf_commit_tokenized_docs" in has_accessor,
            "library_reports_inverted_blocks": "tfidf_commit_inverted_blocks" in has_accessor,
+           "library_reports_host_profile": "tfidf_commit_host_profile" in has_accessor,
+           "full_mirror_forced": bool(os.environ.get("TFIDF_DEBUG")) and os.environ.get("TFIDF_FULL_MIRROR", "0") not in ("", "0"),
            "full_inversion_forced": bool(os.environ.get("TFIDF_DEBUG")) and os.environ.get("TFIDF_FULL_INVERSION", "0") not in ("", "0"),
            "full_commit_forced": bool(os.environ.get("TFIDF_DEBUG")) and os.environ.get("TFIDF_FULL_COMMIT", "0") not in ("", "0"),
            "config": {k: v for k, v in vars(args).items() if k != "out"}, "num_docs": s["num_docs"], "nnz": s["nnz"], "text_bytes": s["text_bytes"],
