@@ -563,6 +563,71 @@ int tfidf_reader_fuzzy_terms(tfidf_reader *rd, const uint8_t *term, uint64_t len
  * chunks filled and sorted (1, 1 when everything fitted; 0, 0 when no input
  * term could have candidates). */
 int tfidf_last_fuzzy_chunks(const tfidf_index *ix, uint64_t *scan_chunks, uint64_t *cand_chunks);
+/* ---- fuzzy search: the documents holding any near spelling of a term ----
+ * (Lucene 9.8 FuzzyQuery(term, maxEdits, prefixLength, maxExpansions,
+ * transpositions = true) under its default rewrite,
+ * TopTermsBlendedFreqScoringRewrite, restated: DESIGN.md section 2, "Fuzzy
+ * search"; parity with Lucene is not pinned by a fixture.)
+ * Input, distance, prefix rule and vocabulary: those of tfidf_fuzzy_terms_batch.
+ * Candidates of a term: the lookup's candidates with one more condition.  With
+ *   ed the distance and m = min(code points of the candidate, code points of
+ *   the term), a candidate needs m > ed (Lucene's boost would be 0 or negative
+ *   otherwise; this restatement drops such terms).  n_within[i] counts them.
+ * Boost: 1 when ed == 0, else 1 - (float) ed / (float) m in float arithmetic.
+ * Expansion of a term: its first max_expansions (1..64; Lucene's default is
+ *   50) candidates in (boost descending, lower-cased UTF-8 bytes ascending as
+ *   unsigned bytes) order, selected and ordered on the device.
+ * tfidf_fuzzy_expand_batch: the expansions in that order, in the CSR layout and
+ *   with the size-query / TFIDF_E_BUFFER protocol of tfidf_fuzzy_terms_batch;
+ *   boosts[j] is candidate j's boost, df[j] the shard's own df.
+ * tfidf_search_fuzzy_batch: every hit of every term's expansion, as
+ *   tfidf_search_batch_all writes hits (hit_offsets[n_terms + 1] and *n_out
+ *   always, doc_ids / scores when *n_out <= cap, else TFIDF_E_BUFFER);
+ *   n_expanded[i] is the size of term i's expansion.  The expansion is a flat
+ *   disjunction of SHOULD term clauses, each weighted boost * idf(max df,
+ *   docCount) where max df is the largest df among the expansion's terms
+ *   (blended frequency) under the statistics tfidf_search would use on that
+ *   snapshot; clause scores are BM25 as in tfidf_search, a document's score is
+ *   their sum, the order is (score descending, doc ascending).  An expansion of
+ *   the input term alone gives exactly tfidf_search(term, k = 0).
+ * TFIDF_E_INVALID_ARG, nothing written: max_edits > 2, max_expansions outside
+ *   1..64, n_terms > 65536, decreasing t_offsets.  TFIDF_E_STATE before the
+ *   first commit.  tfidf_last_fuzzy_chunks reports for these calls too;
+ *   tfidf_last_search_ms holds the last all-hits chunk's scoring and, as the
+ *   total, the whole call's device time (*ms_device, may be NULL).
+ * The single forms are the batch of one. */
+int tfidf_fuzzy_expand_batch(tfidf_index *ix, const uint8_t *t_utf8, const uint64_t *t_offsets, uint32_t n_terms,
+                             uint32_t max_edits, uint32_t prefix_len, uint32_t max_expansions, uint64_t *cand_offsets,
+                             uint64_t *n_within, uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap,
+                             uint32_t *df, uint8_t *dist, float *boosts, uint64_t cand_cap, uint64_t *n_cands,
+                             uint64_t *n_term_bytes, float *ms_device);
+int tfidf_reader_fuzzy_expand_batch(tfidf_reader *rd, const uint8_t *t_utf8, const uint64_t *t_offsets,
+                                    uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len, uint32_t max_expansions,
+                                    uint64_t *cand_offsets, uint64_t *n_within, uint64_t *term_offsets, uint8_t *terms,
+                                    uint64_t terms_cap, uint32_t *df, uint8_t *dist, float *boosts, uint64_t cand_cap,
+                                    uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device);
+int tfidf_fuzzy_expand(tfidf_index *ix, const uint8_t *term, uint64_t len, uint32_t max_edits, uint32_t prefix_len,
+                       uint32_t max_expansions, uint64_t *n_within, uint64_t *term_offsets, uint8_t *terms,
+                       uint64_t terms_cap, uint32_t *df, uint8_t *dist, float *boosts, uint64_t cand_cap,
+                       uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device);
+int tfidf_reader_fuzzy_expand(tfidf_reader *rd, const uint8_t *term, uint64_t len, uint32_t max_edits,
+                              uint32_t prefix_len, uint32_t max_expansions, uint64_t *n_within, uint64_t *term_offsets,
+                              uint8_t *terms, uint64_t terms_cap, uint32_t *df, uint8_t *dist, float *boosts,
+                              uint64_t cand_cap, uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device);
+int tfidf_search_fuzzy_batch(tfidf_index *ix, const uint8_t *t_utf8, const uint64_t *t_offsets, uint32_t n_terms,
+                             uint32_t max_edits, uint32_t prefix_len, uint32_t max_expansions, uint32_t *doc_ids,
+                             float *scores, uint64_t cap, uint64_t *hit_offsets, uint32_t *n_expanded, uint64_t *n_out,
+                             float *ms_device);
+int tfidf_reader_search_fuzzy_batch(tfidf_reader *rd, const uint8_t *t_utf8, const uint64_t *t_offsets,
+                                    uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len, uint32_t max_expansions,
+                                    uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                                    uint32_t *n_expanded, uint64_t *n_out, float *ms_device);
+int tfidf_search_fuzzy(tfidf_index *ix, const uint8_t *term, uint64_t len, uint32_t max_edits, uint32_t prefix_len,
+                       uint32_t max_expansions, uint32_t *doc_ids, float *scores, uint64_t cap, uint32_t *n_expanded,
+                       uint64_t *n_out, float *ms_device);
+int tfidf_reader_search_fuzzy(tfidf_reader *rd, const uint8_t *term, uint64_t len, uint32_t max_edits,
+                              uint32_t prefix_len, uint32_t max_expansions, uint32_t *doc_ids, float *scores,
+                              uint64_t cap, uint32_t *n_expanded, uint64_t *n_out, float *ms_device);
 /* ---- wildcard and prefix search (Lucene's WildcardQuery / PrefixQuery; the
  * reference has no counterpart: QueryParser.escape neutralises '*' and '?';
  * DESIGN.md section 2, "Wildcard search") ----
@@ -1196,6 +1261,18 @@ int tfidf_node_fuzzy_terms_batch(tfidf_node *n, const uint8_t *t_utf8, const uin
                                  uint64_t *n_within, uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap,
                                  uint64_t *df, uint8_t *dist, uint64_t cand_cap, uint64_t *n_cands,
                                  uint64_t *n_term_bytes, float *ms_device);
+/* tfidf_search_fuzzy_batch over the node, after tfidf_node_commit, in both
+ * statistics modes: every shard with documents expands each term over its own
+ * vocabulary (as a searcher per shard would), blends with the df of the
+ * statistics in force and returns its hits; ids become global by the shard's
+ * doc_base (u64 here) and the host merges each term's lists by (score
+ * descending, global id ascending).  n_expanded[i] is the sum of the shards'
+ * expansion sizes.  A shard's failure fails the call with that shard's code.
+ * *ms_device is the largest of the shards' device times. */
+int tfidf_node_search_fuzzy_batch(tfidf_node *n, const uint8_t *t_utf8, const uint64_t *t_offsets, uint32_t n_terms,
+                                  uint32_t max_edits, uint32_t prefix_len, uint32_t max_expansions, uint64_t *doc_ids,
+                                  float *scores, uint64_t cap, uint64_t *hit_offsets, uint32_t *n_expanded,
+                                  uint64_t *n_out, float *ms_device);
 /* The wildcard calls over the node, after tfidf_node_commit, in both
  * statistics modes: every shard with documents runs the batch at once on its
  * own device.  Terms are merged as tfidf_node_fuzzy_terms_batch merges them

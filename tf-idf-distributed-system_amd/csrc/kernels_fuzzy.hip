@@ -11,7 +11,9 @@
 //                  flushed once per workgroup) and compacts the numbers of the
 //                  hashed slots it passes; <true> appends (sort key, slot) at
 //                  positions taken from one wave-aggregated atomic per wave and
-//                  term, never past the capacity the counts gave
+//                  term, never past the capacity the counts gave.  For the
+//                  fuzzy search (FzScan::search) a candidate also needs
+//                  fzs_keep and the key is fzs_sort_key (fuzzy_search_plan.h)
 //   k_fz_hashed    the same test for the compacted hashed slots (long terms):
 //                  a lane reads its slot's reference occurrence from the corpus
 //                  and lower-cases it on the way
@@ -26,6 +28,7 @@
 #include <stdint.h>
 
 #include "fuzzy_plan.h"
+#include "fuzzy_search_plan.h"
 #include "tfidf_internal.h"
 
 namespace tfidf {
@@ -79,11 +82,13 @@ __device__ __forceinline__ void fz_test_terms(const FzScan &a, FzLds &L, bool ha
     uint32_t d = kFzFar;
     if (have && fz_sig_ok(L.sig[t], sig, a.max_edits))
       d = fz_match(L.cps + o, n, c, n_cand, a.max_edits, a.prefix_len);
+    const uint32_t m = fzs_min_len(n, n_cand);
+    if (a.search && d != kFzFar && !fzs_keep(d, m)) d = kFzFar;     // fuzzy search: a boost of 0 or less is no candidate
     const bool hit = d != kFzFar;
     if (FILL) {
       const uint32_t pos = fz_wave_pos(a.cursor, hit, lane);
       if (hit && pos < a.cap) {
-        a.keys[pos] = fz_sort_key(t, d, df);
+        a.keys[pos] = a.search ? fzs_sort_key(t, d, m) : fz_sort_key(t, d, df);
         a.slots[pos] = slot;
       }
     } else if (hit) {

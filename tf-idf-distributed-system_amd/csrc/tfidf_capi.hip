@@ -28,6 +28,7 @@
 #include "commit_plan.h"
 #include "compact_plan.h"
 #include "fuzzy_plan.h"
+#include "fuzzy_search_plan.h"
 #include "wildcard_plan.h"
 #include "regex_plan.h"
 #include "mlt_plan.h"
@@ -380,6 +381,7 @@ struct SearchCtx {
   DevMem q_in, q_out, cand, cand_n, out_doc, out_score, hits, hits_n, hits_c, hits_s, hits_P, ovf;
   DevMem hl_in, hl_cnt, hl_m, hl_s, hl_o;   // hit highlighting: plan, slice counts, matches, per-row ranges, packed output
   DevMem fz_in, fz_hs, fz_c, fz_tmp;        // fuzzy lookup: staged terms + counters, hashed slots, candidates, sort scratch
+  DevMem fz_o;                              // fuzzy search: the selected expansions of a candidate chunk
   DevMem ph_in, ph_s, ph_o, ph_tmp;         // phrase search: phrases' keys / sequences / weights, per-row arrays, ordered hits, sort scratch
   DevMem ml_in, ml_c, ml_tmp;               // more-like-this: staged seeds + row extents + counters, candidates, sort scratch
   DevMem wc_bits, wc_cnt, wc_out, wc_len;   // wildcard union: pattern bitmaps, (pattern, block) counts, doc ids, matched rows' lengths
@@ -392,7 +394,7 @@ struct SearchCtx {
   explicit SearchCtx(int d)
       : dev(d), q_in(d), q_out(d), cand(d), cand_n(d), out_doc(d), out_score(d), hits(d), hits_n(d), hits_c(d),
         hits_s(d), hits_P(d), ovf(d), hl_in(d), hl_cnt(d), hl_m(d), hl_s(d), hl_o(d), fz_in(d), fz_hs(d), fz_c(d),
-        fz_tmp(d), ph_in(d), ph_s(d), ph_o(d), ph_tmp(d), ml_in(d), ml_c(d), ml_tmp(d), wc_bits(d),
+        fz_tmp(d), fz_o(d), ph_in(d), ph_s(d), ph_o(d), ph_tmp(d), ml_in(d), ml_c(d), ml_tmp(d), wc_bits(d),
         wc_cnt(d), wc_out(d), wc_len(d), rx_tab(d) {}
   int init() {
     DeviceGuard g(dev);
@@ -3360,10 +3362,23 @@ extern "C" int tfidf_last_highlight_chunks(const tfidf_index *ix, uint64_t *item
 constexpr uint64_t kFzCandBudget = 1ull << 22;   // candidates per fill: 96 MiB of keys and slots, both sort buffers
 constexpr uint32_t kFzHashedInit = 1u << 16;     // hashed slots listed before the list is grown and the scan redone
 
+// One entry of a fuzzy search's expansion, and the expansions of a call's input
+// terms in selection order (fuzzy_search_plan.h).
+struct FzsEntry {
+  uint32_t slot, dist, boost_bits;
+};
+typedef std::vector<std::vector<FzsEntry>> FuzzyExpansions;
+
+// ex != nullptr: the fuzzy search's expansion instead of the lookup's lists:
+// candidates by fzs_keep, sorted by fzs_sort_key, the first max_out <=
+// kFzsMaxExpansions of each term selected and ordered on the device
+// (k_fzs_select); out then carries n_within and the device time only.
 static int fuzzy_on(tfidf_index *ix, Snapshot &S, const uint8_t *t_utf8, const uint64_t *t_offsets, uint32_t n_terms,
-                    uint32_t max_edits, uint32_t prefix_len, uint32_t max_out, FuzzyLists *out) {
+                    uint32_t max_edits, uint32_t prefix_len, uint32_t max_out, FuzzyLists *out,
+                    FuzzyExpansions *ex = nullptr) {
   out->ms_device = 0.0f;
   out->cands.assign(n_terms, {});
+  if (ex) ex->assign(n_terms, {});
   out->n_within.assign(n_terms, 0);
   // input terms -> lower-cased code points (none: a term without candidates)
   std::vector<std::vector<uint32_t>> cps(n_terms);
@@ -3416,6 +3431,7 @@ static int fuzzy_on(tfidf_index *ix, Snapshot &S, const uint8_t *t_utf8, const u
   a.t_cps = d_cps;
   a.max_edits = max_edits;
   a.prefix_len = prefix_len;
+  a.search = ex ? 1u : 0u;
   a.counts = d_cnt;
   a.cursor = d_cur;
   const uint8_t *d_text = S.text->as<uint8_t>();
@@ -3425,6 +3441,7 @@ static int fuzzy_on(tfidf_index *ix, Snapshot &S, const uint8_t *t_utf8, const u
   FzStage st;
   std::vector<uint32_t> counts, seg, take, oo, h_slots;
   std::vector<uint64_t> sub, h_keys;
+  std::vector<uint8_t> h_sel;
   std::string ts;
   for (size_t ci = 0; ci + 1 < cuts.size(); ci++) {
     const uint64_t t0 = cuts[ci], nt = cuts[ci + 1] - t0;
@@ -3505,6 +3522,49 @@ static int fuzzy_on(tfidf_index *ix, Snapshot &S, const uint8_t *t_utf8, const u
       HIP_TRY(X.fz_tmp.reserve(tmp_bytes));
       tmp_bytes = X.fz_tmp.bytes;
       HIP_TRY(fz_sort(X.fz_tmp.p, &tmp_bytes, k_in, k_out, s_in, s_out, (uint32_t)T, s));
+      if (ex) {
+        // the expansions, selected and ordered on the device: counts [na], keys and slots [na][kFzsMaxExpansions]
+        const size_t o_keys = up16(na * 4), o_slots = o_keys + na * kFzsMaxExpansions * 8,
+                     o_end = o_slots + na * kFzsMaxExpansions * 4;
+        HIP_TRY(X.fz_o.reserve(o_end));
+        uint8_t *ob = X.fz_o.as<uint8_t>();
+        HIP_TRY(hipMemcpyAsync(d_seg, seg.data(), (na + 1) * 4, hipMemcpyHostToDevice, s));
+        FzsSelect q{};
+        q.keys = k_out;
+        q.slots = s_out;
+        q.seg = d_seg;
+        q.n_terms = (uint32_t)na;
+        q.E = max_out;
+        q.dict = a.dict;
+        q.C = S.C;
+        q.text = d_text;
+        q.text_bytes = S.text_bytes;
+        q.out_n = reinterpret_cast<uint32_t *>(ob);
+        q.out_keys = reinterpret_cast<uint64_t *>(ob + o_keys);
+        q.out_slots = reinterpret_cast<uint32_t *>(ob + o_slots);
+        HIP_TRY(launch_fzs_select(q, s));
+        h_sel.resize(o_end);
+        HIP_TRY(hipMemcpyAsync(h_sel.data(), ob, o_end, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        const uint32_t *h_n = reinterpret_cast<const uint32_t *>(h_sel.data());
+        const uint64_t *h_k = reinterpret_cast<const uint64_t *>(h_sel.data() + o_keys);
+        const uint32_t *h_s = reinterpret_cast<const uint32_t *>(h_sel.data() + o_slots);
+        for (uint64_t t = 0; t < na; t++) {
+          if (h_n[t] != std::min<uint32_t>(seg[t + 1] - seg[t], max_out))
+            return fail(TFIDF_E_STATE, "fuzzy expansion of term %llu has %u entries", (unsigned long long)t, h_n[t]);
+          std::vector<FzsEntry> &L = (*ex)[t0 + a0 + t];
+          L.reserve(h_n[t]);
+          for (uint32_t i = 0; i < h_n[t]; i++) {
+            const uint64_t k = h_k[t * kFzsMaxExpansions + i];
+            const uint32_t slot = h_s[t * kFzsMaxExpansions + i];
+            if (fzs_key_term(k) != t || slot >= S.C || fzs_key_dist(k) > max_edits)
+              return fail(TFIDF_E_STATE, "fuzzy expansion entry %u of term %llu is out of place", i,
+                          (unsigned long long)t);
+            L.push_back(FzsEntry{slot, fzs_key_dist(k), fzs_key_boost_bits(k)});
+          }
+        }
+        continue;
+      }
       // what the host orders: everything (max_out == 0), or the selection packed into the sort's input buffers
       uint64_t n_take = T;
       oo = seg;
@@ -4550,19 +4610,14 @@ static int all_hits_score_chunk(tfidf_index *ix, Snapshot &S, StatsView &V, Sear
   return TFIDF_OK;
 }
 
-static int batch_all_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *q_utf8, const uint64_t *q_offsets,
-                        uint32_t n_q, uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
-                        uint64_t *n_out) {
-  for (uint32_t i = 0; i <= n_q; i++) hit_offsets[i] = 0;
-  *n_out = 0;
-  if (n_q == 0 || S.n_docs == 0) return TFIDF_OK;
-  CtxLease lease(ix);
-  if (lease.rc) return lease.rc;
-  SearchCtx &X = *lease.c;
-  const hipStream_t s = lease.stream();
-  DeviceGuard g(ix->cfg.device);
-  QueryBatch qb;
-  if (int e = prepare_batch(ix, S, V, q_utf8, q_offsets, n_q, &qb)) return e;
+// Every hit of each of a prepared batch's n_q queries, chunk by chunk, into the
+// caller's arrays (hit_offsets zeroed by the caller).  ms_before: device time the
+// call spent ahead of the scoring, added to the total of tfidf_last_search_ms
+// (*ms_total, when non-null, receives that total).
+static int batch_all_prepared(tfidf_index *ix, Snapshot &S, StatsView &V, SearchCtx &X, hipStream_t s,
+                              const QueryBatch &qb, uint32_t n_q, uint32_t *doc_ids, float *scores, uint64_t cap,
+                              uint64_t *hit_offsets, uint64_t *n_out, float ms_before = 0.0f,
+                              float *ms_total = nullptr) {
   const uint32_t fixed = all_hits_fixed_chunk();
   std::vector<uint64_t> qoff_h;
   uint64_t total = 0;
@@ -4590,9 +4645,27 @@ static int batch_all_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_
     a = z;
   }
   *n_out = total;
-  set_last_ms(ix, any ? qev_ms(X, QEV_0, QEV_1) : 0.0f, any ? qev_ms(X, QEV_0, QEV_2) : 0.0f);
+  const float ms_all = ms_before + (any ? qev_ms(X, QEV_0, QEV_2) : 0.0f);
+  set_last_ms(ix, any ? qev_ms(X, QEV_0, QEV_1) : 0.0f, ms_all);
+  if (ms_total) *ms_total = ms_all;
   if (!fits) return fail(TFIDF_E_BUFFER, "need %llu result slots", (unsigned long long)total);
   return TFIDF_OK;
+}
+
+static int batch_all_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *q_utf8, const uint64_t *q_offsets,
+                        uint32_t n_q, uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                        uint64_t *n_out) {
+  for (uint32_t i = 0; i <= n_q; i++) hit_offsets[i] = 0;
+  *n_out = 0;
+  if (n_q == 0 || S.n_docs == 0) return TFIDF_OK;
+  CtxLease lease(ix);
+  if (lease.rc) return lease.rc;
+  SearchCtx &X = *lease.c;
+  const hipStream_t s = lease.stream();
+  DeviceGuard g(ix->cfg.device);
+  QueryBatch qb;
+  if (int e = prepare_batch(ix, S, V, q_utf8, q_offsets, n_q, &qb)) return e;
+  return batch_all_prepared(ix, S, V, X, s, qb, n_q, doc_ids, scores, cap, hit_offsets, n_out);
 }
 
 extern "C" int tfidf_search_batch_all(tfidf_index *ix, const uint8_t *q_utf8, const uint64_t *q_offsets, uint32_t n_q,
@@ -4612,6 +4685,215 @@ extern "C" int tfidf_reader_search_batch_all(tfidf_reader *rd, const uint8_t *q_
   if (!rd || !hit_offsets || !n_out || (n_q && !q_offsets) || (cap && (!doc_ids || !scores)))
     return fail(TFIDF_E_INVALID_ARG, "NULL argument");
   return batch_all_on(rd->ix, *rd->S, *rd->V, q_utf8, q_offsets, n_q, doc_ids, scores, cap, hit_offsets, n_out);
+}
+
+// ---------------------------------------------------------------------------
+// fuzzy search (fuzzy_search_plan.h, kernels_fuzzy_search.hip): FuzzyQuery's
+// top-terms blended-frequency rewrite.  The expansion of every input term comes
+// from the term lookup's scans with the search's key and candidate rule and the
+// device selection (fuzzy_on with ex); nothing but the expansions' slots, boosts
+// and distances reaches the host.  The search then weights every term of an
+// expansion with boost * idf(largest df of the expansion) and hands one
+// all-SHOULD prepared query per input term to the batched all-hits path; the
+// expand call resolves the strings (exact keys from the host mirror).
+
+static int fuzzy_search_check_args(const uint8_t *t_utf8, const uint64_t *t_offsets, uint32_t n_terms,
+                                   uint32_t max_edits, uint32_t max_exp) {
+  if (max_exp < 1 || max_exp > kFzsMaxExpansions)
+    return fail(TFIDF_E_INVALID_ARG, "max_expansions %u outside 1..%u", max_exp, kFzsMaxExpansions);
+  return fuzzy_check_args(t_utf8, t_offsets, n_terms, max_edits, 0, true);
+}
+
+static int fuzzy_expand_on(tfidf_index *ix, Snapshot &S, const uint8_t *t_utf8, const uint64_t *t_offsets,
+                           uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len, uint32_t max_exp,
+                           uint64_t *cand_offsets, uint64_t *n_within, uint64_t *term_offsets, uint8_t *terms,
+                           uint64_t terms_cap, uint32_t *df, uint8_t *dist, float *boosts, uint64_t cand_cap,
+                           uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device) {
+  if (int rc = fuzzy_search_check_args(t_utf8, t_offsets, n_terms, max_edits, max_exp)) return rc;
+  if (!cand_offsets || (n_terms && !n_within) || !n_cands || !n_term_bytes)
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (ms_device) *ms_device = 0.0f;
+  FuzzyLists fl;
+  FuzzyExpansions ex;
+  if (int rc = fuzzy_on(ix, S, t_utf8, t_offsets, n_terms, max_edits, prefix_len, max_exp, &fl, &ex)) return rc;
+  if (ms_device) *ms_device = fl.ms_device;
+  set_last_ms(ix, 0.0f, fl.ms_device);
+  DeviceGuard g(ix->cfg.device);                       // slot_term may read a reference occurrence
+  std::vector<std::string> strs;
+  std::string ts;
+  uint64_t nc = 0, nb = 0;
+  cand_offsets[0] = 0;
+  for (uint32_t i = 0; i < n_terms; i++) {
+    n_within[i] = fl.n_within[i];
+    for (const FzsEntry &e : ex[i]) {
+      if (int rc = slot_term(S, e.slot, &ts)) return rc;
+      nb += ts.size();
+      strs.push_back(ts);
+    }
+    nc += ex[i].size();
+    cand_offsets[i + 1] = nc;
+  }
+  *n_cands = nc;
+  *n_term_bytes = nb;
+  if (nc > cand_cap || nb > terms_cap || (nc && (!term_offsets || !df || !dist || !boosts)) || (nb && !terms))
+    return fail(TFIDF_E_BUFFER, "need %llu candidate slots and %llu term bytes", (unsigned long long)nc,
+                (unsigned long long)nb);
+  uint64_t at = 0, b = 0;
+  if (term_offsets) term_offsets[0] = 0;
+  for (uint32_t i = 0; i < n_terms; i++)
+    for (const FzsEntry &e : ex[i]) {
+      const std::string &t = strs[at];
+      memcpy(terms + b, t.data(), t.size());
+      b += t.size();
+      df[at] = S.h_df[e.slot];
+      dist[at] = (uint8_t)e.dist;
+      boosts[at] = fzs_bits_float(e.boost_bits);
+      term_offsets[++at] = b;
+    }
+  return TFIDF_OK;
+}
+
+static int fuzzy_search_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *t_utf8,
+                           const uint64_t *t_offsets, uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len,
+                           uint32_t max_exp, uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                           uint32_t *n_expanded, uint64_t *n_out, float *ms_device) {
+  if (int rc = fuzzy_search_check_args(t_utf8, t_offsets, n_terms, max_edits, max_exp)) return rc;
+  if (!hit_offsets || !n_out || (n_terms && !n_expanded) || (cap && (!doc_ids || !scores)))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (ms_device) *ms_device = 0.0f;
+  for (uint32_t i = 0; i <= n_terms; i++) hit_offsets[i] = 0;
+  *n_out = 0;
+  FuzzyLists fl;
+  FuzzyExpansions ex;
+  if (int rc = fuzzy_on(ix, S, t_utf8, t_offsets, n_terms, max_edits, prefix_len, max_exp, &fl, &ex)) return rc;
+  if (ms_device) *ms_device = fl.ms_device;
+  set_last_ms(ix, 0.0f, fl.ms_device);
+  for (uint32_t i = 0; i < n_terms; i++) n_expanded[i] = (uint32_t)ex[i].size();
+  if (n_terms == 0 || S.n_docs == 0) return TFIDF_OK;
+  if (int e = V.wait_gdf()) return e;
+  // one flat disjunction per input term: SHOULD clauses in selection order, all weighted with the expansion's largest df
+  QueryBatch qb;
+  for (uint32_t i = 0; i < n_terms; i++) {
+    PreparedQuery pq;
+    if (V.doc_count) {
+      uint64_t max_df = 0;
+      for (const FzsEntry &e : ex[i]) max_df = std::max<uint64_t>(max_df, V.global ? V.gdf[e.slot] : S.h_df[e.slot]);
+      const float idf = bm25_idf(max_df, V.doc_count);
+      for (const FzsEntry &e : ex[i]) {
+        volatile float w = fzs_bits_float(e.boost_bits) * idf;         // BM25Scorer: weight = boost * idf
+        const float wv = w;
+        pq.slot.push_back(S.col_of(e.slot));
+        pq.ldf.push_back(S.h_df[e.slot]);
+        pq.w.push_back(wv);
+        pq.role.push_back(kRoleShould << 24);
+      }
+    }
+    qb.add(pq);
+  }
+  CtxLease lease(ix);
+  if (lease.rc) return lease.rc;
+  DeviceGuard g(ix->cfg.device);
+  return batch_all_prepared(ix, S, V, *lease.c, lease.stream(), qb, n_terms, doc_ids, scores, cap, hit_offsets, n_out,
+                            fl.ms_device, ms_device);
+}
+
+extern "C" int tfidf_fuzzy_expand_batch(tfidf_index *ix, const uint8_t *t_utf8, const uint64_t *t_offsets,
+                                        uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len,
+                                        uint32_t max_expansions, uint64_t *cand_offsets, uint64_t *n_within,
+                                        uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *df,
+                                        uint8_t *dist, float *boosts, uint64_t cand_cap, uint64_t *n_cands,
+                                        uint64_t *n_term_bytes, float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  if (int rc = fuzzy_search_check_args(t_utf8, t_offsets, n_terms, max_edits, max_expansions)) return rc;
+  const std::shared_ptr<Snapshot> snap = current(ix);
+  if (!snap) return fail(TFIDF_E_STATE, "fuzzy expansion before commit");
+  return fuzzy_expand_on(ix, *snap, t_utf8, t_offsets, n_terms, max_edits, prefix_len, max_expansions, cand_offsets,
+                         n_within, term_offsets, terms, terms_cap, df, dist, boosts, cand_cap, n_cands, n_term_bytes,
+                         ms_device);
+}
+
+extern "C" int tfidf_reader_fuzzy_expand_batch(tfidf_reader *rd, const uint8_t *t_utf8, const uint64_t *t_offsets,
+                                               uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len,
+                                               uint32_t max_expansions, uint64_t *cand_offsets, uint64_t *n_within,
+                                               uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap,
+                                               uint32_t *df, uint8_t *dist, float *boosts, uint64_t cand_cap,
+                                               uint64_t *n_cands, uint64_t *n_term_bytes, float *ms_device) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  return fuzzy_expand_on(rd->ix, *rd->S, t_utf8, t_offsets, n_terms, max_edits, prefix_len, max_expansions,
+                         cand_offsets, n_within, term_offsets, terms, terms_cap, df, dist, boosts, cand_cap, n_cands,
+                         n_term_bytes, ms_device);
+}
+
+// the batch of one, without the offsets arrays of the input and of the terms' candidates
+extern "C" int tfidf_fuzzy_expand(tfidf_index *ix, const uint8_t *term, uint64_t len, uint32_t max_edits,
+                                  uint32_t prefix_len, uint32_t max_expansions, uint64_t *n_within,
+                                  uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *df,
+                                  uint8_t *dist, float *boosts, uint64_t cand_cap, uint64_t *n_cands,
+                                  uint64_t *n_term_bytes, float *ms_device) {
+  if (!n_within || (!term && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t t_off[2] = {0, len};
+  uint64_t c_off[2];
+  return tfidf_fuzzy_expand_batch(ix, term, t_off, 1, max_edits, prefix_len, max_expansions, c_off, n_within,
+                                  term_offsets, terms, terms_cap, df, dist, boosts, cand_cap, n_cands, n_term_bytes,
+                                  ms_device);
+}
+
+extern "C" int tfidf_reader_fuzzy_expand(tfidf_reader *rd, const uint8_t *term, uint64_t len, uint32_t max_edits,
+                                         uint32_t prefix_len, uint32_t max_expansions, uint64_t *n_within,
+                                         uint64_t *term_offsets, uint8_t *terms, uint64_t terms_cap, uint32_t *df,
+                                         uint8_t *dist, float *boosts, uint64_t cand_cap, uint64_t *n_cands,
+                                         uint64_t *n_term_bytes, float *ms_device) {
+  if (!n_within || (!term && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t t_off[2] = {0, len};
+  uint64_t c_off[2];
+  return tfidf_reader_fuzzy_expand_batch(rd, term, t_off, 1, max_edits, prefix_len, max_expansions, c_off, n_within,
+                                         term_offsets, terms, terms_cap, df, dist, boosts, cand_cap, n_cands,
+                                         n_term_bytes, ms_device);
+}
+
+extern "C" int tfidf_search_fuzzy_batch(tfidf_index *ix, const uint8_t *t_utf8, const uint64_t *t_offsets,
+                                        uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len,
+                                        uint32_t max_expansions, uint32_t *doc_ids, float *scores, uint64_t cap,
+                                        uint64_t *hit_offsets, uint32_t *n_expanded, uint64_t *n_out,
+                                        float *ms_device) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  if (int rc = fuzzy_search_check_args(t_utf8, t_offsets, n_terms, max_edits, max_expansions)) return rc;
+  std::shared_ptr<StatsView> view;
+  const std::shared_ptr<Snapshot> snap = current(ix, &view);
+  if (!snap) return fail(TFIDF_E_STATE, "fuzzy search before commit");
+  return fuzzy_search_on(ix, *snap, *view, t_utf8, t_offsets, n_terms, max_edits, prefix_len, max_expansions, doc_ids,
+                         scores, cap, hit_offsets, n_expanded, n_out, ms_device);
+}
+
+extern "C" int tfidf_reader_search_fuzzy_batch(tfidf_reader *rd, const uint8_t *t_utf8, const uint64_t *t_offsets,
+                                               uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len,
+                                               uint32_t max_expansions, uint32_t *doc_ids, float *scores, uint64_t cap,
+                                               uint64_t *hit_offsets, uint32_t *n_expanded, uint64_t *n_out,
+                                               float *ms_device) {
+  if (!rd) return fail(TFIDF_E_INVALID_ARG, "NULL reader");
+  return fuzzy_search_on(rd->ix, *rd->S, *rd->V, t_utf8, t_offsets, n_terms, max_edits, prefix_len, max_expansions,
+                         doc_ids, scores, cap, hit_offsets, n_expanded, n_out, ms_device);
+}
+
+extern "C" int tfidf_search_fuzzy(tfidf_index *ix, const uint8_t *term, uint64_t len, uint32_t max_edits,
+                                  uint32_t prefix_len, uint32_t max_expansions, uint32_t *doc_ids, float *scores,
+                                  uint64_t cap, uint32_t *n_expanded, uint64_t *n_out, float *ms_device) {
+  if (!n_expanded || (!term && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t t_off[2] = {0, len};
+  uint64_t h_off[2];
+  return tfidf_search_fuzzy_batch(ix, term, t_off, 1, max_edits, prefix_len, max_expansions, doc_ids, scores, cap,
+                                  h_off, n_expanded, n_out, ms_device);
+}
+
+extern "C" int tfidf_reader_search_fuzzy(tfidf_reader *rd, const uint8_t *term, uint64_t len, uint32_t max_edits,
+                                         uint32_t prefix_len, uint32_t max_expansions, uint32_t *doc_ids,
+                                         float *scores, uint64_t cap, uint32_t *n_expanded, uint64_t *n_out,
+                                         float *ms_device) {
+  if (!n_expanded || (!term && len)) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t t_off[2] = {0, len};
+  uint64_t h_off[2];
+  return tfidf_reader_search_fuzzy_batch(rd, term, t_off, 1, max_edits, prefix_len, max_expansions, doc_ids, scores,
+                                         cap, h_off, n_expanded, n_out, ms_device);
 }
 
 // ---------------------------------------------------------------------------

@@ -2543,6 +2543,90 @@ extern "C" int tfidf_node_search_phrase_slop_batch(tfidf_node *n, const uint8_t 
 }
 
 // ---------------------------------------------------------------------------
+// fuzzy search over the node: every shard with documents expands each term over
+// its own vocabulary and scores it under the statistics in force
+// (tfidf_search_fuzzy_batch); the host merges each term's lists as the phrase
+// search merges them.
+
+extern "C" int tfidf_node_search_fuzzy_batch(tfidf_node *n, const uint8_t *t_utf8, const uint64_t *t_offsets,
+                                             uint32_t n_terms, uint32_t max_edits, uint32_t prefix_len,
+                                             uint32_t max_expansions, uint64_t *doc_ids, float *scores, uint64_t cap,
+                                             uint64_t *hit_offsets, uint32_t *n_expanded, uint64_t *n_out,
+                                             float *ms_device) {
+  if (!n || !hit_offsets || !n_out || (n_terms && (!t_offsets || !n_expanded || (!t_utf8 && t_offsets[n_terms]))) ||
+      (cap && (!doc_ids || !scores)))
+    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (max_edits > 2) return errf(TFIDF_E_INVALID_ARG, "max_edits %u above 2", max_edits);
+  if (max_expansions < 1 || max_expansions > 64)
+    return errf(TFIDF_E_INVALID_ARG, "max_expansions %u outside 1..64", max_expansions);
+  std::lock_guard<std::mutex> lk(n->mu);
+  if (ms_device) *ms_device = 0.0f;
+  if (!n->committed) return errf(TFIDF_E_STATE, "fuzzy search before tfidf_node_commit");
+  struct ShardHits {
+    std::vector<uint32_t> docs, n_exp;
+    std::vector<float> scores;
+    std::vector<uint64_t> off;
+    float ms = 0.0f;
+    bool ran = false;
+  };
+  const size_t G = n->shards.size();
+  std::vector<ShardHits> sh(G);
+  // one shard's batch: once with a guessed payload size, once more with the size it reports
+  if (int rc = n->pool->run([&](uint32_t g) {
+        tfidf_index *ix = n->shards[g];
+        ShardHits &b = sh[g];
+        if (!index_committed(ix) || index_num_docs(ix) == 0) return (int)TFIDF_OK;
+        b.off.assign((size_t)n_terms + 1, 0);
+        b.n_exp.assign((size_t)n_terms + 1, 0);
+        uint64_t total = 0, guess = std::min<uint64_t>(64ull * n_terms + 4096, 1ull << 24);
+        int rc = TFIDF_OK;
+        for (int attempt = 0; attempt < 2; attempt++) {
+          b.docs.resize(guess);
+          b.scores.resize(guess);
+          rc = tfidf_search_fuzzy_batch(ix, t_utf8, t_offsets, n_terms, max_edits, prefix_len, max_expansions,
+                                        b.docs.data(), b.scores.data(), guess, b.off.data(), b.n_exp.data(), &total,
+                                        &b.ms);
+          if (rc != TFIDF_E_BUFFER) break;
+          guess = total;
+        }
+        b.ran = rc == TFIDF_OK;
+        return rc;
+      }))
+    return rc;
+  uint64_t total = 0;
+  hit_offsets[0] = 0;
+  for (uint32_t i = 0; i < n_terms; i++) {
+    n_expanded[i] = 0;
+    for (size_t g = 0; g < G; g++)
+      if (sh[g].ran) {
+        total += sh[g].off[i + 1] - sh[g].off[i];
+        n_expanded[i] += sh[g].n_exp[i];
+      }
+    hit_offsets[i + 1] = total;
+  }
+  *n_out = total;
+  if (ms_device)
+    for (const ShardHits &b : sh) *ms_device = std::max(*ms_device, b.ms);
+  if (total > cap) return errf(TFIDF_E_BUFFER, "need %llu result slots", (unsigned long long)total);
+  // the shards' lists of a term are ordered, and ascending shard = ascending global id among equal scores
+  std::vector<uint64_t> at(G);
+  for (uint32_t i = 0; i < n_terms; i++) {
+    for (size_t g = 0; g < G; g++) at[g] = sh[g].ran ? sh[g].off[i] : 0;
+    for (uint64_t o = hit_offsets[i]; o < hit_offsets[i + 1]; o++) {
+      size_t best = G;
+      for (size_t g = 0; g < G; g++) {
+        if (!sh[g].ran || at[g] >= sh[g].off[i + 1]) continue;
+        if (best == G || sh[g].scores[at[g]] > sh[best].scores[at[best]]) best = g;
+      }
+      const uint64_t j = at[best]++;
+      doc_ids[o] = n->doc_base[best] + sh[best].docs[j];
+      scores[o] = sh[best].scores[j];
+    }
+  }
+  return TFIDF_OK;
+}
+
+// ---------------------------------------------------------------------------
 // more-like-this over the node: the owning shard selects a seed's terms, every
 // shard with documents scores the term strings on its own dictionary and
 // statistics, the host merges per seed by (score descending, global id ascending)

@@ -484,6 +484,7 @@ struct FzScan {
   uint32_t C;
   const uint32_t *t_off, *t_cps;
   uint32_t n_terms, max_edits, prefix_len;
+  uint32_t search;            // fuzzy search: candidates need fzs_keep, keys are fzs_sort_key (fuzzy_search_plan.h)
   uint32_t *counts;           // count pass: survivors per staged term (zeroed before)
   uint64_t *keys;             // fill pass: fz_sort_key per survivor, its slot, the append cursor (zeroed
   uint32_t *slots;            // before) and the capacity the counts gave
@@ -502,6 +503,25 @@ hipError_t launch_fz_select(const uint64_t *keys, const uint32_t *seg, uint32_t 
                             uint32_t *take, hipStream_t s);
 hipError_t launch_fz_gather(const uint64_t *keys, const uint32_t *slots, const uint32_t *seg, const uint32_t *out_off,
                             uint32_t n_terms, uint64_t *o_keys, uint32_t *o_slots, hipStream_t s);
+
+// --- fuzzy search (kernels_fuzzy_search.hip; rules in fuzzy_search_plan.h) ---
+// The expansion of each of n_terms input terms from its sorted candidates
+// (keys / slots of term t: [seg[t], seg[t + 1]), fzs_sort_key order): the first
+// E <= kFzsMaxExpansions in (boost descending, term bytes ascending) order, in
+// that order: out_n[t] entries at out_keys / out_slots [t * kFzsMaxExpansions].
+struct FzsSelect {
+  const uint64_t *keys;
+  const uint32_t *slots, *seg;
+  uint32_t n_terms, E;
+  const uint64_t *dict;       // lo[C], hi[C], ref[C]
+  uint32_t C;
+  const uint8_t *text;        // the corpus: a hashed key is read from its reference occurrence
+  uint64_t text_bytes;
+  uint32_t *out_n;
+  uint64_t *out_keys;
+  uint32_t *out_slots;
+};
+hipError_t launch_fzs_select(const FzsSelect &a, hipStream_t s);
 
 // --- wildcard and prefix search (kernels_wildcard.hip; rules in wildcard_plan.h) ---
 // The scan takes an FzScan: t_cps holds pattern elements (wc_parse), n_terms <=

@@ -100,6 +100,23 @@ _FUZZY_SINGLE_SIG = (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint3
                                C.c_uint64, U32P, U8P, C.c_uint64, U64P, U64P, F32P])
 
 
+# tfidf_[reader_]fuzzy_expand[_batch]: the lookup's layout with the float boosts after dist
+_FUZZY_EXPAND_BATCH_SIG = (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, U64P, U64P,
+                                     U64P, VP, C.c_uint64, U32P, U8P, F32P, C.c_uint64, U64P, U64P, F32P])
+_FUZZY_EXPAND_SINGLE_SIG = (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, U64P, U64P, VP,
+                                      C.c_uint64, U32P, U8P, F32P, C.c_uint64, U64P, U64P, F32P])
+
+
+def _fuzzy_search_batch_sig(doc):
+    """tfidf_[reader_|node_]search_fuzzy_batch; doc ids are u32 per shard, u64 over a node."""
+    return (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, doc, F32P, C.c_uint64,
+                      U64P, U32P, U64P, F32P])
+
+
+_FUZZY_SEARCH_SINGLE_SIG = (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, U32P, F32P,
+                                      C.c_uint64, U32P, U64P, F32P])
+
+
 def _wildcard_terms_sig(df):
     """tfidf_[reader_|node_]wildcard_terms_batch; df is u32 per shard, u64 over a node."""
     return (C.c_int, [VP, C.c_char_p, U64P, C.c_uint32, C.c_uint32, U64P, U64P, U64P, VP, C.c_uint64, df, C.c_uint64,
@@ -168,6 +185,15 @@ SIGNATURES = {
     "tfidf_fuzzy_terms": _FUZZY_SINGLE_SIG,
     "tfidf_reader_fuzzy_terms": _FUZZY_SINGLE_SIG,
     "tfidf_last_fuzzy_chunks": (C.c_int, [VP, U64P, U64P]),
+    "tfidf_fuzzy_expand_batch": _FUZZY_EXPAND_BATCH_SIG,
+    "tfidf_reader_fuzzy_expand_batch": _FUZZY_EXPAND_BATCH_SIG,
+    "tfidf_fuzzy_expand": _FUZZY_EXPAND_SINGLE_SIG,
+    "tfidf_reader_fuzzy_expand": _FUZZY_EXPAND_SINGLE_SIG,
+    "tfidf_search_fuzzy_batch": _fuzzy_search_batch_sig(U32P),
+    "tfidf_reader_search_fuzzy_batch": _fuzzy_search_batch_sig(U32P),
+    "tfidf_node_search_fuzzy_batch": _fuzzy_search_batch_sig(U64P),
+    "tfidf_search_fuzzy": _FUZZY_SEARCH_SINGLE_SIG,
+    "tfidf_reader_search_fuzzy": _FUZZY_SEARCH_SINGLE_SIG,
     "tfidf_wildcard_terms_batch": _wildcard_terms_sig(U32P),
     "tfidf_reader_wildcard_terms_batch": _wildcard_terms_sig(U32P),
     "tfidf_node_wildcard_terms_batch": _wildcard_terms_sig(U64P),

@@ -485,6 +485,21 @@ class Node:
         return E._fuzzy_lists(E._fuzzy_batch_arrays(L.load().tfidf_node_fuzzy_terms_batch, self._h, terms, max_edits,
                                                     prefix_len, max_out, df_dtype=np.uint64))
 
+    def search_fuzzy_batch_arrays(self, terms, max_edits=2, prefix_len=0, max_expansions=50):
+        """(global docs uint64[], scores float32[], hit offsets uint64[n + 1], n_expanded uint32[n], ms_device) of
+        tfidf_node_search_fuzzy_batch."""
+        from . import engine as E
+        return E._fuzzy_search_arrays(L.load().tfidf_node_search_fuzzy_batch, self._h, terms, max_edits, prefix_len,
+                                      max_expansions, dtype=np.uint64)
+
+    def search_fuzzy_batch(self, terms, max_edits=2, prefix_len=0, max_expansions=50):
+        """ShardIndex.search_fuzzy_batch over the node: [[(global doc, score)]];
+        every shard expands each term over its own vocabulary and weights it
+        under the statistics in force, the lists are merged per term by (score
+        desc, global id asc) (tfidf_node_search_fuzzy_batch)."""
+        from . import engine as E
+        return E._fuzzy_search_lists(self.search_fuzzy_batch_arrays(terms, max_edits, prefix_len, max_expansions))
+
     def wildcard_terms_batch(self, patterns, max_out=10):
         """ShardIndex.wildcard_terms_batch over the node's vocabulary: df is
         summed over the shards and n_matched counts distinct terms

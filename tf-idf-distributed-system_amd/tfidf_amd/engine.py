@@ -278,6 +278,116 @@ def _fuzzy_single(fn, handle, term, max_edits, prefix_len, max_out):
     return [(raw[t[j]:t[j + 1]], int(df[j]), int(dist[j])) for j in range(nc.value)], within.value
 
 
+def _fuzzy_expand_arrays(fn, handle, terms, max_edits, prefix_len, max_expansions):
+    """tfidf_[reader_]fuzzy_expand_batch, sized as _fuzzy_batch_arrays sizes the
+    lookup.  -> (cand offsets uint64[n + 1], n_within uint64[n], term offsets
+    uint64[m + 1], term blob bytes, df uint32[m], dist uint8[m], boosts
+    float32[m], ms_device)."""
+    terms = list(terms)
+    blob, t_offs = _key_arrays(terms)
+    n = len(terms)
+    c_offs = np.zeros(n + 1, np.uint64)
+    within = np.zeros(max(n, 1), np.uint64)
+    nc, nb, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+    m_cap = min(n * min(max(int(max_expansions), 0), 64), 1 << 20)
+    b_cap = 32 * m_cap
+    for _ in range(2):
+        t_out = np.zeros(m_cap + 1, np.uint64)
+        text = np.empty(max(b_cap, 1), np.uint8)
+        df = np.zeros(max(m_cap, 1), np.uint32)
+        dist = np.zeros(max(m_cap, 1), np.uint8)
+        boosts = np.zeros(max(m_cap, 1), np.float32)
+        rc = fn(handle, blob, L.ptr(t_offs, C.c_uint64), n, max_edits, prefix_len, max_expansions,
+                L.ptr(c_offs, C.c_uint64), L.ptr(within, C.c_uint64), L.ptr(t_out, C.c_uint64),
+                text.ctypes.data_as(C.c_void_p), b_cap, L.ptr(df, C.c_uint32), L.ptr(dist, C.c_uint8),
+                L.ptr(boosts, C.c_float), m_cap, C.byref(nc), C.byref(nb), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        m_cap, b_cap = nc.value, nb.value
+    L.check(rc)
+    m, b = nc.value, nb.value
+    return c_offs, within[:n], t_out[:m + 1], text[:b].tobytes(), df[:m], dist[:m], boosts[:m], ms.value
+
+
+def _fuzzy_expand_lists(arrays):
+    """-> per input term ([(term bytes, df, dist, boost)], n_within); boost is a Python float holding the float32."""
+    c_offs, within, t_out, text, df, dist, boosts, _ = arrays
+    c, t, f, d, bo = c_offs.tolist(), t_out.tolist(), df.tolist(), dist.tolist(), boosts.tolist()
+    cands = [(text[t[j]:t[j + 1]], f[j], d[j], bo[j]) for j in range(len(t) - 1)]
+    return [(cands[c[i]:c[i + 1]], int(within[i])) for i in range(len(c) - 1)]
+
+
+def _fuzzy_expand_single(fn, handle, term, max_edits, prefix_len, max_expansions):
+    """tfidf_fuzzy_expand / tfidf_reader_fuzzy_expand -> ([(term bytes, df, dist, boost)], n_within)."""
+    within, nc, nb, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+    m_cap = min(max(int(max_expansions), 0), 64)
+    b_cap = 32 * m_cap
+    for _ in range(2):
+        t_out = np.zeros(m_cap + 1, np.uint64)
+        text = np.empty(max(b_cap, 1), np.uint8)
+        df = np.zeros(max(m_cap, 1), np.uint32)
+        dist = np.zeros(max(m_cap, 1), np.uint8)
+        boosts = np.zeros(max(m_cap, 1), np.float32)
+        rc = fn(handle, term, len(term), max_edits, prefix_len, max_expansions, C.byref(within),
+                L.ptr(t_out, C.c_uint64), text.ctypes.data_as(C.c_void_p), b_cap, L.ptr(df, C.c_uint32),
+                L.ptr(dist, C.c_uint8), L.ptr(boosts, C.c_float), m_cap, C.byref(nc), C.byref(nb), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        m_cap, b_cap = nc.value, nb.value
+    L.check(rc)
+    raw, t = text[:nb.value].tobytes(), t_out.tolist()
+    return ([(raw[t[j]:t[j + 1]], int(df[j]), int(dist[j]), float(boosts[j])) for j in range(nc.value)],
+            within.value)
+
+
+def _fuzzy_search_arrays(fn, handle, terms, max_edits, prefix_len, max_expansions, cap=None, dtype=np.uint32):
+    """tfidf_[reader_|node_]search_fuzzy_batch: one call with ``cap`` hit slots,
+    once more with the size the library reports when that was too small.  ->
+    (docs, scores float32[], hit offsets uint64[n + 1], n_expanded uint32[n], ms_device)."""
+    terms = list(terms)
+    blob, t_offs = _key_arrays(terms)
+    n = len(terms)
+    offs = np.zeros(n + 1, np.uint64)
+    n_exp = np.zeros(max(n, 1), np.uint32)
+    total, ms = C.c_uint64(), C.c_float()
+    cap = min(4096 * max(n, 1), 1 << 24) if cap is None else cap
+    for _ in range(2):
+        docs = np.empty(max(cap, 1), dtype)
+        scores = np.empty(max(cap, 1), np.float32)
+        rc = fn(handle, blob, L.ptr(t_offs, C.c_uint64), n, max_edits, prefix_len, max_expansions,
+                L.ptr(docs, np.ctypeslib.as_ctypes_type(dtype)), L.ptr(scores, C.c_float), cap,
+                L.ptr(offs, C.c_uint64), L.ptr(n_exp, C.c_uint32), C.byref(total), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        cap = total.value
+    L.check(rc)
+    m = total.value
+    return docs[:m], scores[:m], offs, n_exp[:n], ms.value
+
+
+def _fuzzy_search_lists(arrays):
+    """-> per input term [(doc, score)]."""
+    docs, scores, offs, _, _ = arrays
+    d, s, o = docs.tolist(), scores.tolist(), offs.tolist()
+    return [list(zip(d[o[i]:o[i + 1]], s[o[i]:o[i + 1]])) for i in range(len(o) - 1)]
+
+
+def _fuzzy_search_single(fn, handle, term, max_edits, prefix_len, max_expansions):
+    """tfidf_search_fuzzy / tfidf_reader_search_fuzzy -> (docs uint32[], scores float32[], n_expanded)."""
+    total, ms, n_exp = C.c_uint64(), C.c_float(), C.c_uint32()
+    cap = 4096
+    for _ in range(2):
+        docs = np.empty(max(cap, 1), np.uint32)
+        scores = np.empty(max(cap, 1), np.float32)
+        rc = fn(handle, term, len(term), max_edits, prefix_len, max_expansions, L.ptr(docs, C.c_uint32),
+                L.ptr(scores, C.c_float), cap, C.byref(n_exp), C.byref(total), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        cap = total.value
+    L.check(rc)
+    return docs[:total.value], scores[:total.value], n_exp.value
+
+
 def _wildcard_terms_arrays(fn, handle, patterns, max_out, df_dtype=np.uint32):
     """tfidf_[reader_|node_]wildcard_terms_batch, sized as _fuzzy_batch_arrays
     sizes the fuzzy batch.  -> (cand offsets uint64[n + 1], n_matched
@@ -671,6 +781,45 @@ class ShardIndex:
         empty, not UTF-8 or longer than 255 UTF-16 units gives ([], 0)."""
         return _fuzzy_lists(_fuzzy_batch_arrays(L.load().tfidf_fuzzy_terms_batch, self._h, terms, max_edits,
                                                 prefix_len, max_out))
+
+    def fuzzy_expand(self, term: bytes, max_edits=2, prefix_len=0, max_expansions=50):
+        """([(term bytes, df, dist, boost)], n_within): the expansion of
+        Lucene's FuzzyQuery(term, max_edits, prefix_len, max_expansions) under
+        its top-terms rewrite (tfidf_fuzzy_expand): the candidates of
+        fuzzy_terms with m = min(code points of the candidate, of the term) >
+        dist, boost 1 - dist / m in float32, the first max_expansions (1..64)
+        in (boost descending, term bytes ascending) order."""
+        return _fuzzy_expand_single(L.load().tfidf_fuzzy_expand, self._h, term, max_edits, prefix_len, max_expansions)
+
+    def fuzzy_expand_batch_arrays(self, terms, max_edits=2, prefix_len=0, max_expansions=50):
+        """(cand offsets, n_within, term offsets, term blob, df, dist, boosts, ms_device) of tfidf_fuzzy_expand_batch."""
+        return _fuzzy_expand_arrays(L.load().tfidf_fuzzy_expand_batch, self._h, terms, max_edits, prefix_len,
+                                    max_expansions)
+
+    def fuzzy_expand_batch(self, terms, max_edits=2, prefix_len=0, max_expansions=50):
+        """[fuzzy_expand(t, ...) for t in terms] in one call."""
+        return _fuzzy_expand_lists(self.fuzzy_expand_batch_arrays(terms, max_edits, prefix_len, max_expansions))
+
+    def search_fuzzy_arrays(self, term: bytes, max_edits=2, prefix_len=0, max_expansions=50):
+        """(docs uint32[], scores float32[], n_expanded) of tfidf_search_fuzzy."""
+        return _fuzzy_search_single(L.load().tfidf_search_fuzzy, self._h, term, max_edits, prefix_len, max_expansions)
+
+    def search_fuzzy(self, term: bytes, max_edits=2, prefix_len=0, max_expansions=50):
+        """[(doc, score)]: every document holding a term of fuzzy_expand(term,
+        ...), scored as the disjunction of the expansion's terms, each weighted
+        boost * idf(largest df of the expansion); (score desc, doc asc)."""
+        d, s, _ = self.search_fuzzy_arrays(term, max_edits, prefix_len, max_expansions)
+        return list(zip(d.tolist(), s.tolist()))
+
+    def search_fuzzy_batch_arrays(self, terms, max_edits=2, prefix_len=0, max_expansions=50, cap=None):
+        """(docs uint32[], scores float32[], hit offsets uint64[n + 1], n_expanded uint32[n], ms_device) of
+        tfidf_search_fuzzy_batch; term i's hits are [offsets[i], offsets[i + 1])."""
+        return _fuzzy_search_arrays(L.load().tfidf_search_fuzzy_batch, self._h, terms, max_edits, prefix_len,
+                                    max_expansions, cap)
+
+    def search_fuzzy_batch(self, terms, max_edits=2, prefix_len=0, max_expansions=50):
+        """[search_fuzzy(t, ...) for t in terms] in one pass."""
+        return _fuzzy_search_lists(self.search_fuzzy_batch_arrays(terms, max_edits, prefix_len, max_expansions))
 
     def wildcard_terms(self, pattern: bytes, max_out=10):
         """([(term bytes, df)], n_matched): the vocabulary terms matching the
@@ -1266,6 +1415,39 @@ class Reader:
     def fuzzy_terms_batch(self, terms, max_edits=2, prefix_len=0, max_out=10):
         """ShardIndex.fuzzy_terms_batch on this reader's snapshot."""
         return _fuzzy_lists(self.fuzzy_terms_batch_arrays(terms, max_edits, prefix_len, max_out))
+
+    def fuzzy_expand(self, term: bytes, max_edits=2, prefix_len=0, max_expansions=50):
+        """ShardIndex.fuzzy_expand on this reader's snapshot."""
+        return _fuzzy_expand_single(L.load().tfidf_reader_fuzzy_expand, self._h, term, max_edits, prefix_len,
+                                    max_expansions)
+
+    def fuzzy_expand_batch_arrays(self, terms, max_edits=2, prefix_len=0, max_expansions=50):
+        """ShardIndex.fuzzy_expand_batch_arrays on this reader's snapshot."""
+        return _fuzzy_expand_arrays(L.load().tfidf_reader_fuzzy_expand_batch, self._h, terms, max_edits, prefix_len,
+                                    max_expansions)
+
+    def fuzzy_expand_batch(self, terms, max_edits=2, prefix_len=0, max_expansions=50):
+        """ShardIndex.fuzzy_expand_batch on this reader's snapshot."""
+        return _fuzzy_expand_lists(self.fuzzy_expand_batch_arrays(terms, max_edits, prefix_len, max_expansions))
+
+    def search_fuzzy_arrays(self, term: bytes, max_edits=2, prefix_len=0, max_expansions=50):
+        """ShardIndex.search_fuzzy_arrays on this reader's snapshot."""
+        return _fuzzy_search_single(L.load().tfidf_reader_search_fuzzy, self._h, term, max_edits, prefix_len,
+                                    max_expansions)
+
+    def search_fuzzy(self, term: bytes, max_edits=2, prefix_len=0, max_expansions=50):
+        """ShardIndex.search_fuzzy on this reader's snapshot."""
+        d, s, _ = self.search_fuzzy_arrays(term, max_edits, prefix_len, max_expansions)
+        return list(zip(d.tolist(), s.tolist()))
+
+    def search_fuzzy_batch_arrays(self, terms, max_edits=2, prefix_len=0, max_expansions=50, cap=None):
+        """ShardIndex.search_fuzzy_batch_arrays on this reader's snapshot."""
+        return _fuzzy_search_arrays(L.load().tfidf_reader_search_fuzzy_batch, self._h, terms, max_edits, prefix_len,
+                                    max_expansions, cap)
+
+    def search_fuzzy_batch(self, terms, max_edits=2, prefix_len=0, max_expansions=50):
+        """ShardIndex.search_fuzzy_batch on this reader's snapshot."""
+        return _fuzzy_search_lists(self.search_fuzzy_batch_arrays(terms, max_edits, prefix_len, max_expansions))
 
     def search_phrase(self, phrase: bytes):
         """ShardIndex.search_phrase on this reader's snapshot."""

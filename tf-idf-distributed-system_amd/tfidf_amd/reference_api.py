@@ -15,7 +15,7 @@ import os
 import re
 
 from . import _lib as L
-from .engine import ShardIndex, leader_merge, query_positive_terms
+from .engine import ShardIndex, analyze, leader_merge, query_positive_terms
 
 
 def extract_text(data: bytes) -> bytes:
@@ -261,6 +261,20 @@ class Worker:
             hits = rd.search(corrected.encode() if changed else q, 0)
             out = [document_score_info(rd.doc_key(d).decode(), s) for d, s in hits]
         return (corrected if changed else None), out
+
+    # No reference counterpart (QueryParser.escape neutralises '~'): Lucene's
+    # FuzzyQuery on the one word ``word`` analyses to: the documents holding
+    # any of the max_expansions closest spellings within max_edits, a closer
+    # spelling weighing more and all weighted with the most frequent one's idf;
+    # every hit in the order and shape of search_index.  Text that analyses to
+    # no word or to several is a ValueError.
+    def search_fuzzy(self, word: str, max_edits=2, prefix_len=0, max_expansions=50):
+        tokens = analyze(word.encode())
+        if len(tokens) != 1:
+            raise ValueError("fuzzy search takes exactly one word, got %d" % len(tokens))
+        with self.index.reader() as rd:
+            hits = rd.search_fuzzy(tokens[0], max_edits, prefix_len, max_expansions)
+            return [document_score_info(rd.doc_key(d).decode(), s) for d, s in hits]
 
     # No reference counterpart (QueryParser.escape neutralises '*' and '?'):
     # the documents holding a term that starts with ``text`` (lower-cased, not
