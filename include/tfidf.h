@@ -249,6 +249,13 @@ int tfidf_add_docs_device(tfidf_index *ix, const void *d_utf8, const void *d_off
  *   term-major and full builds), *remapped = 1 when the kept count rows moved
  *   to a wider column layout because the vocabulary grew.  Each pointer may be
  *   NULL.  TFIDF_DEBUG=1 TFIDF_FULL_INVERSION=1 inverts every block (A/B runs).
+ * tfidf_commit_inversion_shape: the launch shape of the last tfidf_commit's
+ *   block-major inversion: *slices = document slices per (block, range) tile,
+ *   *scan_parts = workgroups per block row in the row scan (1 / 1: one
+ *   workgroup each, as for every grid that fills the device; also for
+ *   term-major).  Few inverted blocks (an incremental commit's tail) are cut
+ *   up so that they use the whole device; the published index is the same
+ *   under every shape.  Each pointer may be NULL.
  * Host mirrors: df lookups, the vocabulary export, query analysis and the
  *   GLOBAL setters read pinned host copies of a snapshot's dictionary keys,
  *   per-slot df and slot -> column words.  An incremental block-major commit
@@ -267,6 +274,7 @@ int tfidf_commit(tfidf_index *ix);
 int tfidf_commit_tokenized_docs(const tfidf_index *ix, uint64_t *docs, uint32_t *was_full);
 int tfidf_commit_inverted_blocks(const tfidf_index *ix, uint32_t *first_block, uint32_t *n_blocks,
                                  uint32_t *remapped);
+int tfidf_commit_inversion_shape(const tfidf_index *ix, uint32_t *slices, uint32_t *scan_parts);
 int tfidf_commit_host_profile(const tfidf_index *ix, tfidf_host_profile *out);
 
 /* ---- document lifecycle: delete, reclaim, read back ----

@@ -1,12 +1,14 @@
 // commit_plan.h — the host side of an incremental tfidf_commit: whether the
 // build target's rows and dictionary can be kept (and from which document the
 // tokenizers then start), how the kept host lists take the new entries, and
-// how the host mirrors of the dictionary and df follow.  Plain C++ (no HIP),
-// so the decisions are tested on their own (tests/commit_plan_check.cpp,
-// tests/mirror_plan_check.cpp).
+// how the host mirrors of the dictionary and df follow, and the launch shape
+// of a few-block inversion.  Plain C++ (no HIP), so the decisions are tested
+// on their own (tests/commit_plan_check.cpp, tests/mirror_plan_check.cpp,
+// tests/slice_plan_check.cpp).
 #pragma once
 
 #include <stdint.h>
+#include <stdlib.h>
 
 #include <algorithm>
 #include <vector>
@@ -162,6 +164,94 @@ TFIDF_PLAN_HD uint32_t remap_row_value(const uint32_t *old_row, uint32_t NC_inv,
 // kept blocks are those with a posting index below post_base = bbase[first_block].
 inline uint64_t post_esc_keep(const std::vector<uint64_t> &sorted, uint64_t post_base) {
   return (uint64_t)(std::lower_bound(sorted.begin(), sorted.end(), post_base << 24) - sorted.begin());
+}
+
+// ---------------------------------------------------------------------------
+// The inversion's launch shape when few blocks are inverted (an incremental
+// commit's tail block, a small shard).  One workgroup per (block, range) tile
+// and one per block row leave a 256-CU device idle, so a tile's documents are
+// cut into slices (one workgroup each: k_df_partial<true>, k_scatter_part<true>)
+// and a row's columns into parts (k_row_scan_parts).  Nothing that is kept
+// depends on the shape: the published index is the same under every one.
+
+constexpr uint32_t kSliceGroupDocs = 48;      // a slice is a multiple of every loader's document group (4 Q, Q = 1 .. 4)
+// Documents per slice, at least (DESIGN.md §6 "Sliced tiles" has the sweep):
+// one round of k_scatter_part's sixteen waves (16 x 12 documents).  Below it a
+// slice's fixed cost (LDS clear, stream bases, the walk over the range's crank
+// words) is no longer paid for by the shorter document loop.
+constexpr uint32_t kSliceMinDocs = 192;
+constexpr uint32_t kSliceWgsPerCu = 2;        // k_scatter_part (60 KiB of LDS); k_df_partial at 128 KiB runs one
+constexpr uint32_t kScanPartCols = 16384;     // columns of one k_row_scan round: a part is never narrower (unless forced)
+constexpr uint32_t kScanPartAlign = 256;      // a part starts on a k_df_sum workgroup's first column
+constexpr uint32_t kSliceKnobMax = 256, kScanKnobMax = 64;
+// k_scatter_sort takes kSortSpw of a range's 64 streams per workgroup in turn (its regions stay L2-resident in
+// a full build); with few blocks that leaves 16 workgroups per (block, range), so it takes fewer, down to one,
+// until the grid holds two workgroups per CU (1 / 2 / 4 measured on a lone tail block)
+constexpr uint32_t kSortSpw = 4, kSortStreams = 64, kSortWgsPerCu = 2;
+
+struct SlicePlan {
+  uint32_t slices = 1;                        // document slices per (block, range) tile
+  uint32_t slice_docs = (uint32_t)kPlanBlockDocs;   // slice i of block b: documents [b 8192 + i slice_docs, + slice_docs) of the block
+  uint32_t scan_parts = 1;                    // workgroups per block row in the row scan
+  uint32_t scan_width = 0;                    // part j: columns [j scan_width, + scan_width) below NC (scan_parts > 1)
+  uint32_t sort_spw = 4;                      // k_scatter_sort: sub-range streams per workgroup (TFIDF_SORT_SPW overrides)
+};
+
+// blocks: the blocks to invert (n_blocks - first_block); max_docs: the
+// documents of the largest of them; cus: the device's compute units.
+// slices_knob / parts_knob: TFIDF_TEST_INV_SLICES / TFIDF_TEST_SCAN_PARTS
+// (nullptr = unset), which force either number (a forced slice count may
+// leave slices without documents, a forced part count parts without columns).
+inline SlicePlan slice_plan(uint32_t blocks, uint32_t R, uint64_t max_docs, uint32_t NC, uint32_t cus,
+                            const char *slices_knob, const char *parts_knob) {
+  SlicePlan p;
+  if (blocks == 0 || R == 0) return p;        // nothing is inverted: no tile kernel, no row scan
+  while (p.sort_spw > 1 && (uint64_t)blocks * R * (kSortStreams / p.sort_spw) < (uint64_t)cus * kSortWgsPerCu)
+    p.sort_spw /= 2;
+  max_docs = std::min<uint64_t>(std::max<uint64_t>(max_docs, 1), kPlanBlockDocs);
+  auto docs_for = [&](uint32_t s) {
+    const uint64_t per = (max_docs + s - 1) / s;
+    return (uint32_t)((per + kSliceGroupDocs - 1) / kSliceGroupDocs * kSliceGroupDocs);
+  };
+  if (slices_knob && *slices_knob) {
+    p.slices = (uint32_t)std::max(1, std::min(atoi(slices_knob), (int)kSliceKnobMax));
+    p.slice_docs = p.slices > 1 ? docs_for(p.slices) : (uint32_t)kPlanBlockDocs;
+  } else {
+    // a grid that fills the device stays as it is; else slices until it does, each of kSliceMinDocs or more
+    const uint64_t tiles = (uint64_t)blocks * R;
+    const uint64_t by_grid = tiles >= cus ? 1 : (uint64_t)cus * kSliceWgsPerCu / tiles;
+    const uint64_t by_docs = std::max<uint64_t>(1, max_docs / kSliceMinDocs);
+    const uint32_t s = (uint32_t)std::min(by_grid, by_docs);
+    if (s > 1) {
+      p.slice_docs = docs_for(s);
+      p.slices = (uint32_t)((max_docs + p.slice_docs - 1) / p.slice_docs);   // (rounding up to groups may have emptied the last ones)
+      if (p.slices == 1) p.slice_docs = (uint32_t)kPlanBlockDocs;
+    }
+  }
+  const uint32_t max_parts = std::max(1u, (uint32_t)(((uint64_t)NC + kScanPartCols - 1) / kScanPartCols));
+  if (parts_knob && *parts_knob)
+    p.scan_parts = (uint32_t)std::max(1, std::min(atoi(parts_knob), (int)kScanKnobMax));
+  else
+    p.scan_parts = std::min(max_parts, std::max(1u, cus / (2 * blocks)));     // many rows: one workgroup each, as ever
+  if (p.scan_parts > 1) {
+    const uint64_t per = std::max<uint64_t>(1, ((uint64_t)NC + p.scan_parts - 1) / p.scan_parts);
+    p.scan_width = (uint32_t)((per + kScanPartAlign - 1) / kScanPartAlign * kScanPartAlign);
+  }
+  return p;
+}
+
+// documents [*lo, *hi) of slice i of a block that holds documents [d0, d1) (empty: *lo == *hi)
+inline void slice_range(const SlicePlan &p, uint32_t i, uint64_t d0, uint64_t d1, uint64_t *lo, uint64_t *hi) {
+  const uint64_t a = d0 + (uint64_t)i * p.slice_docs;
+  *lo = std::min(a, d1);
+  *hi = std::min(a + p.slice_docs, d1);
+}
+// columns [*lo, *hi) of part j of a row of NC columns
+inline void scan_part_range(const SlicePlan &p, uint32_t j, uint32_t NC, uint64_t *lo, uint64_t *hi) {
+  if (p.scan_parts <= 1) { *lo = 0; *hi = NC; return; }
+  const uint64_t a = (uint64_t)j * p.scan_width;
+  *lo = std::min<uint64_t>(a, NC);
+  *hi = std::min<uint64_t>(a + p.scan_width, NC);
 }
 
 // ---------------------------------------------------------------------------

@@ -2618,16 +2618,33 @@ static uint32_t tiles_grid(uint32_t n_blocks, uint32_t R) { return (n_blocks + 7
 // in its group i (inv_load).  The counts
 // of the range's occupied slots are written at their columns (col_rank), so
 // the count table follows the vocabulary, not the dictionary's probe table.
+//
+// SLICED (few blocks: commit_plan.h slice_plan): a tile's documents are cut
+// into p.slices slices of p.slice_docs, one workgroup each; the grid's "blocks"
+// are the (block, slice) pairs, so the R tiles of a pair still share an XCD.
+// Each workgroup adds its non-zero counts to the row with global atomics; the
+// row was zeroed on the stream before (k_inv_zero).  A slice holds at most
+// kBlockDocs documents, so the 16-bit counters hold as before.
+template <bool SLICED>
 __global__ void __launch_bounds__(1024) k_df_partial(PostingParams p) {
   extern __shared__ uint32_t hist[];
-  uint32_t b, r;
-  if (!tile_of(blockIdx.x, p.n_blocks - p.first_block, p.n_ranges, &b, &r)) return;
+  uint32_t b, r, slice = 0;
+  if (!tile_of(blockIdx.x, (p.n_blocks - p.first_block) * (SLICED ? p.slices : 1u), p.n_ranges, &b, &r)) return;
+  if (SLICED) {
+    slice = b % p.slices;
+    b /= p.slices;
+  }
   b += p.first_block;                                             // (incremental: the blocks before are kept)
   const uint32_t RS = 1u << p.range_shift;
+  uint64_t d0 = (uint64_t)b * kBlockDocs;
+  uint64_t d1 = d0 + kBlockDocs < p.n_docs ? d0 + kBlockDocs : p.n_docs;
+  if (SLICED) {
+    d0 += (uint64_t)slice * p.slice_docs;
+    if (d0 >= d1) return;                                         // workgroup-uniform: a slice past the block's documents
+    d1 = d0 + p.slice_docs < d1 ? d0 + p.slice_docs : d1;
+  }
   for (uint32_t i = threadIdx.x; i < RS / 2; i += blockDim.x) hist[i] = 0;
   __syncthreads();
-  const uint64_t d0 = (uint64_t)b * kBlockDocs;
-  const uint64_t d1 = d0 + kBlockDocs < p.n_docs ? d0 + kBlockDocs : p.n_docs;
   const uint32_t nw = blockDim.x >> 6;
   const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const uint32_t rmask = RS - 1;
@@ -2672,7 +2689,10 @@ __global__ void __launch_bounds__(1024) k_df_partial(PostingParams p) {
     while (bits) {
       const uint32_t sl = 32 * w + (uint32_t)__builtin_ctz(bits);
       bits &= bits - 1;
-      out[col++] = (hist[sl >> 1] >> ((sl & 1u) << 4)) & 0xFFFFu;
+      const uint32_t n = (hist[sl >> 1] >> ((sl & 1u) << 4)) & 0xFFFFu;
+      if (!SLICED) out[col] = n;
+      else if (n) atomicAdd(&out[col], n);
+      col++;
     }
   }
 }
@@ -2680,9 +2700,32 @@ __global__ void __launch_bounds__(1024) k_df_partial(PostingParams p) {
 // per column: df = sum of the per-block counts (row n_blocks).  The rows of
 // kept blocks (b < first_block) are in offset form: a column's count is the
 // distance to the next column's offset, the last column's to the block total.
+//
+// PARTS (the row scan over several workgroups, k_row_scan_parts): the counts
+// of the inverted rows pass through here anyway, so each workgroup also adds
+// the sum of its 256 columns of a row to the total of the part they belong to
+// (p.scan_width is a multiple of 256; part_tot was zeroed by k_inv_zero).
+template <bool PARTS>
 __global__ void __launch_bounds__(256) k_df_sum(PostingParams p) {
+  __shared__ uint32_t psum[4];
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= p.NC) return;
+  if (!PARTS && t >= p.NC) return;
+  if (PARTS) {                                        // (no early exit: the reductions take whole waves)
+    const bool in = t < p.NC;
+    const uint32_t part = (uint32_t)(((uint64_t)blockIdx.x * blockDim.x) / p.scan_width);
+    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    for (uint32_t b = p.first_block; b < p.n_blocks; b++) {
+      const uint32_t w = wave_sum(in ? p.blk[(size_t)b * p.NC + t] : 0u);
+      if (lane == 0) psum[wid] = w;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        const uint32_t tot = psum[0] + psum[1] + psum[2] + psum[3];
+        if (tot) atomicAdd(&p.part_tot[(size_t)(b - p.first_block) * p.scan_parts + part], tot);
+      }
+      __syncthreads();
+    }
+    if (!in) return;
+  }
   uint32_t run = 0;
   if (p.first_block) {
     // sum of (next - own) over the kept rows = (sum of next) - (sum of own);
@@ -2736,18 +2779,15 @@ __global__ void __launch_bounds__(256) k_blk_remap(PostingParams p, const uint32
 // Tiles of 16384 columns: each thread loads 16 consecutive counts with four
 // 16 B loads (coalesced across the workgroup), scans them in registers, and a
 // workgroup scan of the 1024 thread totals gives the offsets.
-__global__ void __launch_bounds__(1024) k_row_scan(PostingParams p) {
-  __shared__ uint32_t wsum[16];
-  __shared__ uint32_t carry_sh;
-  const uint32_t b = blockIdx.x + p.first_block;
-  uint32_t *row = p.blk + (size_t)b * p.NC;
+// Columns [c0, c1) of one row, carry_sh = the offset of column c0 on entry and
+// of column c1 on return.
+__device__ __forceinline__ void row_scan_span(uint32_t *row, uint32_t c0, uint32_t c1, uint32_t *wsum,
+                                              uint32_t *carry_sh) {
   const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  if (tid == 0) carry_sh = 0;
-  __syncthreads();
-  for (uint32_t t0 = 0; t0 < p.NC; t0 += 16384) {
+  for (uint32_t t0 = c0; t0 < c1; t0 += 16384) {
     const uint32_t i0 = t0 + tid * 16;
     uint32_t v[16];
-    if (i0 + 16 <= p.NC) {
+    if (i0 + 16 <= c1) {
       const uint4 *src = reinterpret_cast<const uint4 *>(row + i0);
 #pragma unroll
       for (int q = 0; q < 4; q++) {
@@ -2756,7 +2796,7 @@ __global__ void __launch_bounds__(1024) k_row_scan(PostingParams p) {
       }
     } else {
 #pragma unroll
-      for (int q = 0; q < 16; q++) v[q] = (i0 + q < p.NC) ? row[i0 + q] : 0u;
+      for (int q = 0; q < 16; q++) v[q] = (i0 + q < c1) ? row[i0 + q] : 0u;
     }
     uint32_t tot = 0;
 #pragma unroll
@@ -2769,7 +2809,7 @@ __global__ void __launch_bounds__(1024) k_row_scan(PostingParams p) {
     }
     if (lane == 63) wsum[wid] = x;
     __syncthreads();
-    uint32_t base = carry_sh, all = 0;
+    uint32_t base = *carry_sh, all = 0;
     for (uint32_t w = 0; w < 16; w++) {
       const uint32_t sw = wsum[w];
       if (w < wid) base += sw;
@@ -2777,23 +2817,58 @@ __global__ void __launch_bounds__(1024) k_row_scan(PostingParams p) {
     }
     base += x - tot;
     __syncthreads();
-    if (tid == 0) carry_sh += all;
+    if (tid == 0) *carry_sh += all;
     uint32_t run = base;
     uint32_t o[16];
 #pragma unroll
     for (int q = 0; q < 16; q++) { o[q] = run; run += v[q]; }
-    if (i0 + 16 <= p.NC) {
+    if (i0 + 16 <= c1) {
       uint4 *dst = reinterpret_cast<uint4 *>(row + i0);
 #pragma unroll
       for (int q = 0; q < 4; q++) dst[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
     } else {
 #pragma unroll
       for (int q = 0; q < 16; q++)
-        if (i0 + q < p.NC) row[i0 + q] = o[q];
+        if (i0 + q < c1) row[i0 + q] = o[q];
     }
     __syncthreads();
   }
-  if (tid == 0) p.bbase[b + 1] = carry_sh;
+}
+
+__global__ void __launch_bounds__(1024) k_row_scan(PostingParams p) {
+  __shared__ uint32_t wsum[16];
+  __shared__ uint32_t carry_sh;
+  const uint32_t b = blockIdx.x + p.first_block;
+  uint32_t *row = p.blk + (size_t)b * p.NC;
+  if (threadIdx.x == 0) carry_sh = 0;
+  __syncthreads();
+  row_scan_span(row, 0, p.NC, wsum, &carry_sh);
+  if (threadIdx.x == 0) p.bbase[b + 1] = carry_sh;
+}
+
+// Few rows (commit_plan.h slice_plan): a row's columns in p.scan_parts parts
+// of p.scan_width, one workgroup each (grid = rows x parts).  The scan is in
+// place, so a part never reads another part's columns: its first offset is
+// the sum of the totals of the parts before it, which k_df_sum<true> left in
+// part_tot before any part writes.  The last part leaves the row total in
+// bbase[b + 1]; a forced part count may leave parts without columns.
+__global__ void __launch_bounds__(1024) k_row_scan_parts(PostingParams p) {
+  __shared__ uint32_t wsum[16];
+  __shared__ uint32_t carry_sh;
+  const uint32_t rb = blockIdx.x / p.scan_parts, part = blockIdx.x - rb * p.scan_parts;
+  const uint32_t b = rb + p.first_block;
+  uint32_t *row = p.blk + (size_t)b * p.NC;
+  const uint64_t a = (uint64_t)part * p.scan_width;
+  const uint32_t c0 = (uint32_t)(a < p.NC ? a : p.NC), c1 = (uint32_t)(a + p.scan_width < p.NC ? a + p.scan_width : p.NC);
+  if (threadIdx.x == 0) {
+    const uint32_t *tot = p.part_tot + (size_t)rb * p.scan_parts;
+    uint32_t start = 0;
+    for (uint32_t j = 0; j < part; j++) start += tot[j];
+    carry_sh = start;
+  }
+  __syncthreads();
+  row_scan_span(row, c0, c1, wsum, &carry_sh);
+  if (threadIdx.x == 0 && part + 1 == p.scan_parts) p.bbase[b + 1] = carry_sh;
 }
 
 // Inversion in two passes so that every store stream stays L2-resident.
@@ -2826,10 +2901,12 @@ __device__ __forceinline__ uint32_t part_word(const PostingParams &p, uint32_t e
 
 // entries past a segment's first 64 (c from inv_load; dl0 = the block-local
 // document of the lane in quad 0): appended to their streams straight from
-// the wave
-template <int Q>
-__device__ __forceinline__ void part_entries(const PostingParams &p, uint32_t *bcur, uint32_t rmask, uint64_t bb,
-                                             uint32_t dl0, const uint32_t *c) {
+// the wave.  SLICED: bcur holds the streams' bases and stays as it is; the
+// place in a stream comes from the tile's cursors in global memory (gcur), one
+// atomic per distinct stream of the wave's 64 entries.
+template <int Q, bool SLICED>
+__device__ __forceinline__ void part_entries(const PostingParams &p, uint32_t *bcur, uint32_t *gcur, uint32_t rmask,
+                                             uint64_t bb, uint32_t dl0, const uint32_t *c) {
   const uint32_t lane = threadIdx.x & 63;
   constexpr uint32_t kNoop = kPartStreams;                    // idle lanes bump a spare cursor
 #pragma unroll
@@ -2838,7 +2915,13 @@ __device__ __forceinline__ void part_entries(const PostingParams &p, uint32_t *b
     if (!__any(in)) continue;                                 // wave-uniform
     const uint32_t sl = c[j] & rmask;
     const uint32_t val = part_word(p, c[j], rmask, dl0 + (uint32_t)(j & ~3));
-    const uint32_t pos = cursor_bump<kRangeBits - kSubBits + 1>(bcur, in ? sl >> kSubBits : kNoop, lane);
+    uint32_t pos;
+    if (SLICED) {
+      const uint32_t k = in ? sl >> kSubBits : 0u;
+      pos = bcur[k] + cursor_bump_if<kRangeBits - kSubBits>(gcur, k, in, lane);
+    } else {
+      pos = cursor_bump<kRangeBits - kSubBits + 1>(bcur, in ? sl >> kSubBits : kNoop, lane);
+    }
     if (in) p.post_tmp[bb + pos] = val;
   }
 }
@@ -2849,6 +2932,15 @@ __device__ __forceinline__ void part_entries(const PostingParams &p, uint32_t *b
 // stream in LDS and stored stream run by stream run, ~16x longer runs than
 // wave-local staging (one to two lines per store instruction instead of ~13).
 constexpr uint32_t kPartStage = 16 * 4 * kPartQuads * 64;   // 12 288 entries at 3 quads: 60 KiB, two workgroups per CU
+
+// SLICED (few blocks: commit_plan.h slice_plan; the grid as k_df_partial<true>'s):
+// the workgroups of a tile's slices append to the same 64 streams, so the
+// streams' cursors are a tile's 64 words of p.slice_cur in global memory
+// (zeroed by k_inv_zero) and count from the stream's base, which stays in
+// bcur.  A round's run of a stream is reserved with one global atomic.  Which
+// slice comes first in a stream is free: k_scatter_sort orders by slot, and the
+// order inside a (block, slot) segment is free there as well.
+template <bool SLICED>
 __global__ void __launch_bounds__(1024) k_scatter_part(PostingParams p) {
   __shared__ uint32_t bcur[kPartStreams + 1];
   __shared__ uint32_t cnt[kPartStreams], soff[kPartStreams], gb[kPartStreams], tot_sh;
@@ -2856,9 +2948,21 @@ __global__ void __launch_bounds__(1024) k_scatter_part(PostingParams p) {
   __shared__ uint8_t sid[kPartStage];
   const uint32_t lane = threadIdx.x & 63, nw = blockDim.x >> 6;
   const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  uint32_t b, r;
-  if (!tile_of(blockIdx.x, p.n_blocks - p.first_block, p.n_ranges, &b, &r)) return;
+  uint32_t b, r, slice = 0;
+  if (!tile_of(blockIdx.x, (p.n_blocks - p.first_block) * (SLICED ? p.slices : 1u), p.n_ranges, &b, &r)) return;
+  if (SLICED) {
+    slice = b % p.slices;
+    b /= p.slices;
+  }
+  uint32_t *gcur = SLICED ? p.slice_cur + ((size_t)b * p.n_ranges + r) * kPartStreams : nullptr;
   b += p.first_block;
+  const uint64_t d0 = (uint64_t)b * kBlockDocs;
+  uint64_t d1 = d0 + kBlockDocs < p.n_docs ? d0 + kBlockDocs : p.n_docs;
+  const uint64_t s0 = SLICED ? d0 + (uint64_t)slice * p.slice_docs : d0;   // the workgroup's documents: [s0, d1)
+  if (SLICED) {
+    if (s0 >= d1) return;                                           // workgroup-uniform: a slice past the block's documents
+    d1 = s0 + p.slice_docs < d1 ? s0 + p.slice_docs : d1;
+  }
   const uint32_t RS = 1u << p.range_shift, rmask = RS - 1;
   const uint32_t nsub = RS > kSubSlots ? RS / kSubSlots : 1u;
   const uint32_t *row = p.blk + (size_t)b * p.NC;
@@ -2871,12 +2975,10 @@ __global__ void __launch_bounds__(1024) k_scatter_part(PostingParams p) {
   if (threadIdx.x < kPartStreams) cnt[threadIdx.x] = 0;
   __syncthreads();
   const uint64_t bb = p.bbase[b];
-  const uint64_t d0 = (uint64_t)b * kBlockDocs;
-  const uint64_t d1 = d0 + kBlockDocs < p.n_docs ? d0 + kBlockDocs : p.n_docs;
   constexpr int Q = kPartQuads, E = 4 * Q;
   const uint64_t step = (uint64_t)nw * E;
-  const uint32_t rounds = (uint32_t)((d1 - d0 + step - 1) / step);   // workgroup-uniform
-  uint64_t dd = d0 + (uint64_t)wid * E;                              // the wave's 4 Q consecutive documents
+  const uint32_t rounds = (uint32_t)((d1 - s0 + step - 1) / step);   // workgroup-uniform
+  uint64_t dd = s0 + (uint64_t)wid * E;                              // the wave's 4 Q consecutive documents
   InvQuads<Q> g = inv_quads<Q>(p, dd, d1, r);
   uint32_t c[E];
   inv_load<Q>(p, g, 0, c);
@@ -2895,7 +2997,8 @@ __global__ void __launch_bounds__(1024) k_scatter_part(PostingParams p) {
       const uint32_t n = cnt[lane];
       const uint32_t incl = wave_incl_add(n);
       soff[lane] = incl - n;
-      gb[lane] = n ? atomicAdd(&bcur[lane], n) : 0u;
+      if (SLICED) gb[lane] = n ? bcur[lane] + atomicAdd(&gcur[lane], n) : 0u;
+      else gb[lane] = n ? atomicAdd(&bcur[lane], n) : 0u;
       cnt[lane] = 0;
       if (lane == 63) tot_sh = incl;
     }
@@ -2917,7 +3020,7 @@ __global__ void __launch_bounds__(1024) k_scatter_part(PostingParams p) {
     const uint32_t maxn = inv_maxn<Q>(g);
     for (uint32_t off = 64; __any(off < maxn); off += 64) {      // segments longer than 64
       inv_load<Q>(p, g, off, c);
-      part_entries<Q>(p, bcur, rmask, bb, dl0, c);
+      part_entries<Q, SLICED>(p, bcur, gcur, rmask, bb, dl0, c);
     }
     g = gn;
 #pragma unroll
@@ -3167,25 +3270,64 @@ hipError_t launch_tokenize_long(const BuildParams &p, int grid, hipStream_t s) {
   return hipGetLastError();
 }
 static void allow_big_lds() {
-  static std::atomic<uint64_t> done{0};
-  allow_dyn_lds((const void *)k_df_partial, 2 << kRangeBits, done);
+  static std::atomic<uint64_t> done{0}, done_sliced{0};
+  allow_dyn_lds((const void *)k_df_partial<false>, 2 << kRangeBits, done);
+  allow_dyn_lds((const void *)k_df_partial<true>, 2 << kRangeBits, done_sliced);
+}
+
+static_assert(kSliceGroupDocs % (4 * kDfQuads) == 0 && kSliceGroupDocs % (4 * kPartQuads) == 0,
+              "a slice is a whole number of the loaders' document groups");
+static_assert(kScanPartAlign == 256 && kScanPartCols == 16384, "k_df_sum's workgroup, k_row_scan's round");
+
+// What a sliced / split inversion adds into, in one launch: the count rows of
+// the inverted blocks and the tiles' stream cursors (slices > 1), the rows'
+// part totals (scan_parts > 1).  slice_cur and part_tot are one array.
+__global__ void __launch_bounds__(256) k_inv_zero(uint32_t *rows, uint64_t n_rows, uint32_t *aux, uint64_t n_aux) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_rows + n_aux; i += stride) {
+    if (i < n_rows) rows[i] = 0;
+    else aux[i - n_rows] = 0;
+  }
+}
+hipError_t launch_inv_zero(const PostingParams &p, hipStream_t s) {
+  const uint64_t nb = p.n_blocks - p.first_block;
+  if (nb == 0 || (p.slices <= 1 && p.scan_parts <= 1)) return hipSuccess;
+  const uint64_t n_rows = p.slices > 1 ? nb * p.NC : 0;
+  const uint64_t n_cur = p.slices > 1 ? nb * p.n_ranges * kPartStreams : 0;
+  const uint64_t n_tot = p.scan_parts > 1 ? nb * p.scan_parts : 0;
+  if (p.slices > 1 && p.scan_parts > 1 && p.part_tot != p.slice_cur + n_cur) return hipErrorInvalidValue;
+  uint32_t *aux = p.slices > 1 ? p.slice_cur : p.part_tot;
+  const uint64_t n = n_rows + n_cur + n_tot;
+  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 1023) / 1024, 1024));
+  hipLaunchKernelGGL(k_inv_zero, dim3(grid), dim3(256), 0, s, p.blk + (size_t)p.first_block * p.NC, n_rows, aux,
+                     n_cur + n_tot);
+  return hipGetLastError();
 }
 
 hipError_t launch_df_partial(const PostingParams &p, hipStream_t s) {
   allow_big_lds();
   const size_t lds = (size_t)2 << p.range_shift;             // 16-bit counters
   if (p.n_blocks == p.first_block) return hipSuccess;       // every block kept
-  hipLaunchKernelGGL(k_df_partial, dim3(tiles_grid(p.n_blocks - p.first_block, p.n_ranges)), dim3(1024), lds, s, p);
+  const uint32_t nb = p.n_blocks - p.first_block;
+  if (p.slices > 1)
+    hipLaunchKernelGGL(k_df_partial<true>, dim3(tiles_grid(nb * p.slices, p.n_ranges)), dim3(1024), lds, s, p);
+  else
+    hipLaunchKernelGGL(k_df_partial<false>, dim3(tiles_grid(nb, p.n_ranges)), dim3(1024), lds, s, p);
   return hipGetLastError();
 }
 hipError_t launch_df_sum(const PostingParams &p, hipStream_t s) {
   if (p.NC == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_df_sum, dim3((p.NC + 255) / 256), dim3(256), 0, s, p);
+  if (p.scan_parts > 1 && p.n_blocks != p.first_block)
+    hipLaunchKernelGGL(k_df_sum<true>, dim3((p.NC + 255) / 256), dim3(256), 0, s, p);
+  else
+    hipLaunchKernelGGL(k_df_sum<false>, dim3((p.NC + 255) / 256), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_row_scan(const PostingParams &p, hipStream_t s) {
   if (p.n_blocks == p.first_block) return hipSuccess;
-  hipLaunchKernelGGL(k_row_scan, dim3(p.n_blocks - p.first_block), dim3(1024), 0, s, p);
+  const uint32_t nb = p.n_blocks - p.first_block;
+  if (p.scan_parts > 1) hipLaunchKernelGGL(k_row_scan_parts, dim3(nb * p.scan_parts), dim3(1024), 0, s, p);
+  else hipLaunchKernelGGL(k_row_scan, dim3(nb), dim3(1024), 0, s, p);
   return hipGetLastError();
 }
 hipError_t launch_blk_remap(const PostingParams &p, const uint32_t *blk_old, const uint2 *crank_inv, uint32_t NC_inv,
@@ -3330,7 +3472,12 @@ hipError_t launch_scatter(const PostingParams &p, hipStream_t s) {
     const int t = e ? atoi(e) : 1024;
     return (uint32_t)(t == 256 || t == 512 ? t : 1024);
   }();
-  hipLaunchKernelGGL(k_scatter_part, dim3(tiles_grid(p.n_blocks - p.first_block, p.n_ranges)), dim3(pthreads), 0, s, p);
+  if (p.slices > 1)
+    hipLaunchKernelGGL(k_scatter_part<true>, dim3(tiles_grid((p.n_blocks - p.first_block) * p.slices, p.n_ranges)),
+                       dim3(pthreads), 0, s, p);
+  else
+    hipLaunchKernelGGL(k_scatter_part<false>, dim3(tiles_grid(p.n_blocks - p.first_block, p.n_ranges)), dim3(pthreads), 0,
+                       s, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   const uint32_t RS = 1u << p.range_shift;

@@ -469,6 +469,8 @@ struct tfidf_index {
   // ... and the blocks its inversion kept / the published index holds, and whether the kept rows
   // were moved to another column layout (tfidf_commit_inverted_blocks)
   uint32_t last_inv_first = 0, last_inv_blocks = 0, last_inv_remap = 0;
+  // ... and the launch shape it ran in (commit_plan.h slice_plan; tfidf_commit_inversion_shape)
+  uint32_t last_inv_slices = 1, last_inv_scan_parts = 1;
   // host side of the last commit (tfidf_commit_host_profile): points since prof_t0
   tfidf_host_profile prof{};
   std::chrono::steady_clock::time_point prof_t0;
@@ -485,6 +487,7 @@ struct tfidf_index {
   // delta mirrors (commit_plan.h): the device lists of new dictionary slots and of slots whose df changed, and
   // their pinned host copies (sized once for the largest list, so no commit reallocates pinned memory)
   DevBuf mir_dict_list, mir_df_list;
+  DevBuf inv_aux;                      // sliced inversion (commit_plan.h slice_plan): the tiles' stream cursors, the rows' part totals
   PinnedVec<DictDelta> h_dict_delta;
   PinnedVec<DfDelta> h_df_delta;
   DevBuf bad_list;                     // documents that are not valid UTF-8 (indexed empty)
@@ -653,7 +656,7 @@ extern "C" int tfidf_destroy(tfidf_index *ix) {
   ix->text.reset();
   ix->offsets.reset();
   DevBuf *bufs[] = {&ix->d_live_map, &ix->long_list, &ix->uni_list, &ix->counters, &ix->retry_list, &ix->new_list, &ix->bad_list,
-                    &ix->mir_dict_list, &ix->mir_df_list,
+                    &ix->mir_dict_list, &ix->mir_df_list, &ix->inv_aux,
                     &ix->post_tmp, &ix->lt_keys, &ix->lt_cnt, &ix->lt_g, &ix->lt_pos, &ix->verify_defer, &ix->pairs,
                     &ix->pair_ub, &ix->chunk_list, &ix->chunk_docs, &ix->chunk_fail, &ix->uchunk, &ix->canon_of_slot,
                     &ix->tvals, &ix->term_tmp, &ix->term_esc, &ix->sent_slot, &ix->vcounts, &ix->vnu, &ix->vt_table,
@@ -1741,6 +1744,20 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   ix->last_inv_first = first_block;
   ix->last_inv_blocks = S.n_blocks;
   ix->last_inv_remap = inv.remap ? 1u : 0u;
+  // ... and the shape they are inverted in: few blocks leave most of the device idle with one workgroup
+  // per (block, range) tile and per row, so their documents are sliced and their rows split (slice_plan)
+  SlicePlan sp;
+  if (!S.term_major) {
+    const uint32_t inv_blocks = S.n_blocks - first_block;
+    const uint64_t max_docs = inv_blocks == 0 ? 0 : inv_blocks > 1 ? kBlockDocs : N - (uint64_t)first_block * kBlockDocs;
+    sp = slice_plan(inv_blocks, S.R, max_docs, S.NC, (uint32_t)ix->num_cus, knob("TFIDF_TEST_INV_SLICES"),
+                    knob("TFIDF_TEST_SCAN_PARTS"));
+    if (sp.slices > 1 || sp.scan_parts > 1)
+      HIP_TRY(ix->inv_aux.reserve_slack(((uint64_t)inv_blocks * S.R * 64 * (sp.slices > 1) +
+                                         (uint64_t)inv_blocks * sp.scan_parts * (sp.scan_parts > 1)) * 4));
+  }
+  ix->last_inv_slices = sp.slices;
+  ix->last_inv_scan_parts = sp.scan_parts;
   const uint32_t *blk_old = nullptr;
   if (!S.term_major) {
     const uint64_t blk_need = (uint64_t)(S.n_blocks + 1) * S.NC * 4 + 16;
@@ -1824,10 +1841,16 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   pp.post_esc = S.post_esc.as<uint64_t>();
   pp.post_esc_count = reinterpret_cast<uint32_t *>(ctr + 10);
   pp.post_esc_cap = post_esc_cap;
-  pp.sort_spw = 4;
+  pp.sort_spw = sp.sort_spw;                              // (4 unless few blocks are inverted)
   if (const char *e = knob("TFIDF_SORT_SPW")) pp.sort_spw = (uint32_t)std::max(1, std::min(8, atoi(e)));   // A/B only (<= kSortMaxSpw)
   pp.err = bp.err;
   pp.first_block = first_block;
+  pp.slices = sp.slices;
+  pp.slice_docs = sp.slice_docs;
+  pp.scan_parts = sp.scan_parts;
+  pp.scan_width = sp.scan_width;
+  pp.slice_cur = ix->inv_aux.as<uint32_t>();
+  pp.part_tot = pp.slice_cur + (sp.slices > 1 ? (size_t)(S.n_blocks - first_block) * S.R * 64 : 0);
   HIP_TRY(hipEventRecord(ix->ev[EV_D0], s));
   if (S.term_major) {
     TermParams tp{};
@@ -1889,6 +1912,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   } else {
     if (inv.remap) HIP_TRY(launch_blk_remap(pp, blk_old, S.crank_inv.as<uint2>(), S.NC_inv, s));
     if (S.n_blocks) {
+      HIP_TRY(launch_inv_zero(pp, s));                    // (sliced / split shapes only)
       HIP_TRY(launch_df_partial(pp, s));                  // blocks [first_block, n_blocks)
     } else {
       HIP_TRY(hipMemsetAsync(S.blk.p, 0, (size_t)S.NC * 4, s));
@@ -2179,6 +2203,14 @@ extern "C" int tfidf_commit_inverted_blocks(const tfidf_index *ix, uint32_t *fir
   if (first_block) *first_block = ix->last_inv_first;
   if (n_blocks) *n_blocks = ix->last_inv_blocks;
   if (remapped) *remapped = ix->last_inv_remap;
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_commit_inversion_shape(const tfidf_index *ix, uint32_t *slices, uint32_t *scan_parts) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->mu);
+  if (slices) *slices = ix->last_inv_slices;
+  if (scan_parts) *scan_parts = ix->last_inv_scan_parts;
   return TFIDF_OK;
 }
 

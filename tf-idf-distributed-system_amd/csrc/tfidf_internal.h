@@ -238,6 +238,11 @@ struct PostingParams {
   uint32_t sort_spw;          // scatter pass 2: sub-range streams per workgroup
   uint32_t first_block;       // incremental inversion (commit_plan.h): blocks [first_block, n_blocks) are built;
                               // the rows of blk (offset form), bbase and post of the blocks before are kept
+  // launch shape of a few-block inversion (commit_plan.h slice_plan); 1 / 1: the unsliced kernels, which read none of these
+  uint32_t slices, slice_docs;      // document slices per (block, range) tile, documents per slice
+  uint32_t scan_parts, scan_width;  // workgroups per block row in the row scan, columns per part
+  uint32_t *slice_cur;        // [(n_blocks - first_block) * n_ranges * 64] postings appended per (block, range, stream); zeroed per commit
+  uint32_t *part_tot;         // [(n_blocks - first_block) * scan_parts] row totals per part (k_df_sum); zeroed per commit
 };
 
 // Raise a kernel's dynamic-LDS limit on the current device, once per device:
@@ -292,6 +297,8 @@ hipError_t launch_tokenize_uchunk(const BuildParams &p, int grid, hipStream_t s)
 constexpr uint32_t kUwaveWGsPerCU = 7;    // 64-thread workgroups, ~22 KB LDS each (two waves per SIMD)
 constexpr uint32_t kUchunkWGsPerCU = 8;   // k_tokenize_uchunk: ~19 KB LDS each
 hipError_t launch_verify_deferred(const BuildParams &p, hipStream_t s);           // kernels_index.hip
+// sliced / split shape: zeroes the rows the slices add into, slice_cur and part_tot (one launch; before launch_df_partial)
+hipError_t launch_inv_zero(const PostingParams &p, hipStream_t s);
 hipError_t launch_df_partial(const PostingParams &p, hipStream_t s);
 hipError_t launch_df_sum(const PostingParams &p, hipStream_t s);
 hipError_t launch_row_scan(const PostingParams &p, hipStream_t s);

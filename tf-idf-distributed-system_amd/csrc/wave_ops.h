@@ -33,6 +33,20 @@ __device__ __forceinline__ uint32_t cursor_bump(uint32_t *cur, uint32_t key, uin
   return base + rank;
 }
 
+// cursor_bump for lanes with `in` only (the others touch no cursor and get 0):
+// for cursors in global memory, where an idle lane's bump of a spare cursor
+// would be one more device-wide atomic on a word every workgroup shares.
+template <int BITS>
+__device__ __forceinline__ uint32_t cursor_bump_if(uint32_t *cur, uint32_t key, bool in, uint32_t lane) {
+  const uint64_t peers = peer_mask<BITS>(key) & __ballot(in);
+  const uint32_t rank = (uint32_t)__popcll(peers & ((1ull << lane) - 1));
+  const uint32_t leader = in ? (uint32_t)__builtin_ctzll(peers) : lane;
+  uint32_t base = 0;
+  if (in && rank == 0) base = atomicAdd(cur + key, (uint32_t)__popcll(peers));
+  base = (uint32_t)__shfl((int)base, (int)leader, 64);
+  return in ? base + rank : 0u;
+}
+
 // Wave-aggregated append (the wildcard and regex scans): the lanes with `take` get consecutive positions from one atomicAdd
 __device__ __forceinline__ uint32_t wc_wave_pos(uint32_t *cursor, bool take, uint32_t lane) {
   const uint64_t m = __ballot(take);

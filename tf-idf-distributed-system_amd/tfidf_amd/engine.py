@@ -1008,6 +1008,13 @@ class ShardIndex:
         L.check(L.load().tfidf_commit_inverted_blocks(self._h, C.byref(f), C.byref(n), C.byref(r)))
         return {"first_block": f.value, "n_blocks": n.value, "remapped": r.value}
 
+    def commit_inversion_shape(self):
+        """The launch shape of the last commit's inversion: document slices per (block, range) tile and
+        workgroups per block row in the row scan (tfidf_commit_inversion_shape)."""
+        s, p = C.c_uint32(), C.c_uint32()
+        L.check(L.load().tfidf_commit_inversion_shape(self._h, C.byref(s), C.byref(p)))
+        return {"slices": s.value, "scan_parts": p.value}
+
     def commit_host_profile(self):
         """The host side of the last commit (tfidf_commit_host_profile): host times in ms since the call
         began, stream synchronisations, and per mirror (dict, df, crank) its form ("none" / "delta" /
