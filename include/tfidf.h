@@ -249,6 +249,8 @@ int tfidf_add_docs_device(tfidf_index *ix, const void *d_utf8, const void *d_off
  *   term-major and full builds), *remapped = 1 when the kept count rows moved
  *   to a wider column layout because the vocabulary grew.  Each pointer may be
  *   NULL.  TFIDF_DEBUG=1 TFIDF_FULL_INVERSION=1 inverts every block (A/B runs).
+ *   The df of the kept blocks comes from a per-column base the snapshot keeps;
+ *   TFIDF_DEBUG=1 TFIDF_DF_FROM_ROWS=1 sums their count rows instead (A/B runs).
  * tfidf_commit_inversion_shape: the launch shape of the last tfidf_commit's
  *   block-major inversion: *slices = document slices per (block, range) tile,
  *   *scan_parts = workgroups per block row in the row scan (1 / 1: one

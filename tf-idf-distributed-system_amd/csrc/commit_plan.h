@@ -1,10 +1,11 @@
 // commit_plan.h — the host side of an incremental tfidf_commit: whether the
 // build target's rows and dictionary can be kept (and from which document the
 // tokenizers then start), how the kept host lists take the new entries, and
-// how the host mirrors of the dictionary and df follow, and the launch shape
-// of a few-block inversion.  Plain C++ (no HIP), so the decisions are tested
-// on their own (tests/commit_plan_check.cpp, tests/mirror_plan_check.cpp,
-// tests/slice_plan_check.cpp).
+// how the host mirrors of the dictionary and df follow, the launch shape
+// of a few-block inversion, and the df base a snapshot keeps for its kept
+// blocks.  Plain C++ (no HIP), so the decisions are tested on their own
+// (tests/commit_plan_check.cpp, tests/mirror_plan_check.cpp,
+// tests/slice_plan_check.cpp, tests/df_base_plan_check.cpp).
 #pragma once
 
 #include <stdint.h>
@@ -158,6 +159,48 @@ TFIDF_PLAN_HD uint32_t remap_old_col(uint32_t old_bits, uint32_t old_base, uint3
 // empty segment at the offset of the next old column.
 TFIDF_PLAN_HD uint32_t remap_row_value(const uint32_t *old_row, uint32_t NC_inv, uint32_t block_total, uint32_t old) {
   return old < NC_inv ? old_row[old] : block_total;
+}
+
+// The kept df base (Snapshot::df_base): per column the sum of the counts of
+// the blocks that were full at the snapshot's last inversion, so that a
+// commit's df is the base plus the rows it inverts and no kept row is read.
+// The base is valid exactly when the kept rows are: it is trusted if and only
+// if inversion_plan keeps blocks (first_block > 0), and it then covers blocks
+// [0, first_block), because the last successful commit left it at
+// inv_docs / 8192 blocks and first_block is that number.  Every path that
+// inverts from block 0 (a failed build before, TFIDF_FULL_COMMIT,
+// TFIDF_FULL_INVERSION, dead documents, an epoch change, a seed retry, a new
+// snapshot) rebuilds it from nothing in the same pass.
+struct DfBasePlan {
+  bool trusted = false;       // df_base holds blocks [0, base_before) (after the remap, in this commit's columns)
+  uint32_t base_before = 0;   // blocks the base covers when the commit begins (0: untrusted, it starts from 0)
+  uint32_t base_after = 0;    // ... and when it ends: the blocks that are full now, N / 8192
+  uint32_t fold_first = 0, fold_end = 0;   // the inverted rows [fold_first, fold_end) are added to the base
+  bool remap = false;         // the base moves to the new column layout with the kept rows
+  bool from_rows = false;     // df of the kept blocks summed from their rows, as before the base (A/B); the base is kept up all the same
+};
+
+// inv: this commit's inversion plan; N: its documents; rows_knob: the value of
+// TFIDF_DF_FROM_ROWS (nullptr = unset; an A/B switch outside the CommitSig:
+// the base is maintained under either value, so nothing kept depends on it).
+inline DfBasePlan df_base_plan(const InversionPlan &inv, bool term_major, uint64_t N, const char *rows_knob) {
+  DfBasePlan p;
+  if (term_major) return p;
+  p.trusted = inv.first_block > 0;
+  p.base_before = inv.first_block;
+  p.base_after = (uint32_t)(N / kPlanBlockDocs);
+  p.fold_first = inv.first_block;
+  p.fold_end = std::max(p.base_after, inv.first_block);   // (first_block <= N / 8192: inversion_plan keeps nothing when inv_docs > N)
+  p.remap = inv.remap;
+  p.from_rows = p.trusted && rows_knob && *rows_knob && !(rows_knob[0] == '0' && !rows_knob[1]);
+  return p;
+}
+
+// The base in the new column layout (arguments as remap_old_col's).  It is in
+// count form: a column new to the layout has no posting in a kept block and
+// gets 0, where a kept row takes the offset of the next old column.
+TFIDF_PLAN_HD uint32_t remap_base_value(const uint32_t *old_base, uint32_t old_bits, uint32_t old_base_col, uint32_t bit) {
+  return (old_bits >> bit) & 1u ? old_base[remap_old_col(old_bits, old_base_col, bit)] : 0u;
 }
 
 // Posting escapes ((posting index << 24) | tf, sorted): the entries of the
@@ -326,6 +369,20 @@ inline MirrorPlan mirror_plan(bool full, bool term_major, uint64_t kept_inv, boo
   if (new_nnz == 0) p.df = kMirrorNone;                             // nothing tokenized: no df moved
   else if (new_nnz <= (uint64_t)df_cap * kDfDeltaTry) p.df = kMirrorDelta;
   return p;
+}
+
+// Per-slot df (k_df_slots) need not be rebuilt when the commit can prove it
+// equal to the target's last build: that build succeeded and covered every
+// document (kept_inv == N, so the rows inverted again hold the same counts),
+// the columns are the same (no remap, no new slot), and the mirrors were valid
+// and take nothing (mp.delta with df and dictionary kMirrorNone: nothing was
+// tokenized).  Helps the commit that adds nothing only.  always_knob:
+// TFIDF_DF_SLOTS_ALWAYS (A/B).
+inline bool df_slots_kept(const MirrorPlan &mp, uint64_t kept_inv, uint64_t N, bool remap, uint32_t NC, uint32_t NC_inv,
+                          const char *always_knob) {
+  const bool forced = always_knob && *always_knob && !(always_knob[0] == '0' && !always_knob[1]);
+  return !forced && mp.delta && mp.df == kMirrorNone && mp.dict == kMirrorNone && kept_inv != 0 && kept_inv == N &&
+         !remap && NC == NC_inv;
 }
 
 // The lists applied to the mirrors (after the commit's error checks).  false:

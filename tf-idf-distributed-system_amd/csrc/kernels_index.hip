@@ -2697,72 +2697,102 @@ __global__ void __launch_bounds__(1024) k_df_partial(PostingParams p) {
   }
 }
 
-// per column: df = sum of the per-block counts (row n_blocks).  The rows of
-// kept blocks (b < first_block) are in offset form: a column's count is the
-// distance to the next column's offset, the last column's to the block total.
+// Column t's count over the kept rows, read from the rows themselves (the
+// summation before the df base; TFIDF_DF_FROM_ROWS keeps it for A/B).  The
+// rows of kept blocks are in offset form: a column's count is the distance to
+// the next column's offset, the last column's to the block total.
+__device__ __forceinline__ uint32_t df_from_kept_rows(const PostingParams &p, uint64_t t) {
+  // sum of (next - own) over the kept rows = (sum of next) - (sum of own);
+  // the last column's "next" is the block total, and those sum to
+  // bbase[first_block] - bbase[0].  Nobody touched the kept rows in this
+  // commit, so they come from HBM: eight rows' loads are issued together.
+  const bool last = t + 1 == p.NC;
+  const uint32_t *own = p.blk + t, *nxt = own + (last ? 0 : 1);
+  uint32_t lo = 0, hi = 0, b = 0;
+  for (; b + 8 <= p.first_block; b += 8) {
+    uint32_t x[8], y[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      x[j] = own[(size_t)(b + j) * p.NC];
+      y[j] = nxt[(size_t)(b + j) * p.NC];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) { lo += x[j]; hi += y[j]; }
+  }
+  for (; b < p.first_block; b++) {
+    lo += own[(size_t)b * p.NC];
+    hi += nxt[(size_t)b * p.NC];
+  }
+  return (last ? (uint32_t)(p.bbase[p.first_block] - p.bbase[0]) : hi) - lo;
+}
+
+// per column: df = the kept df base (the counts of the kept blocks
+// [0, first_block), commit_plan.h df_base_plan; nothing when first_block is 0)
+// plus the counts of the inverted rows, to row n_blocks.  The inverted rows
+// whose block is full now (b < p.df_fold_end) join the base, so the next
+// commit of this snapshot reads no kept row either.  The base is updated in
+// place before the commit is known good; that is sound only because a failed
+// commit leaves the snapshot's inv_docs at 0, so the next one starts from
+// block 0 and rebuilds the base without reading it.
 //
 // PARTS (the row scan over several workgroups, k_row_scan_parts): the counts
-// of the inverted rows pass through here anyway, so each workgroup also adds
-// the sum of its 256 columns of a row to the total of the part they belong to
-// (p.scan_width is a multiple of 256; part_tot was zeroed by k_inv_zero).
+// of the inverted rows pass through here anyway, so each workgroup also
+// leaves the sum of its 256 columns of a row in part_tot[row][workgroup]
+// (a plain store of a word nobody else writes: nothing to zero, no atomic);
+// p.scan_width is a multiple of 256, so a part is a whole number of them.
 template <bool PARTS>
 __global__ void __launch_bounds__(256) k_df_sum(PostingParams p) {
-  __shared__ uint32_t psum[4];
+  __shared__ uint32_t psum[2][4];
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (!PARTS && t >= p.NC) return;
-  if (PARTS) {                                        // (no early exit: the reductions take whole waves)
-    const bool in = t < p.NC;
-    const uint32_t part = (uint32_t)(((uint64_t)blockIdx.x * blockDim.x) / p.scan_width);
-    const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const bool in = t < p.NC;
+  if (!PARTS && !in) return;                          // (PARTS: no early exit, the reductions take whole waves)
+  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const uint32_t base = in && p.first_block ? p.df_base[t] : 0u;
+  uint32_t run = base;
+  if (p.df_from_rows && in && p.first_block) run = df_from_kept_rows(p, t);
+  // the inverted rows in two runs, those that join the base and those behind them (the partial tail): two plain
+  // sums, so a full build's pass over all rows keeps its loads in flight as it always did
+  uint32_t full = 0, tail = 0;
+  if (!PARTS) {
+    for (uint32_t b = p.first_block; b < p.df_fold_end; b++) full += p.blk[(size_t)b * p.NC + t];
+    for (uint32_t b = p.df_fold_end; b < p.n_blocks; b++) tail += p.blk[(size_t)b * p.NC + t];
+  } else {
     for (uint32_t b = p.first_block; b < p.n_blocks; b++) {
-      const uint32_t w = wave_sum(in ? p.blk[(size_t)b * p.NC + t] : 0u);
-      if (lane == 0) psum[wid] = w;
+      const uint32_t v = in ? p.blk[(size_t)b * p.NC + t] : 0u;
+      if (b < p.df_fold_end) full += v;
+      else tail += v;
+      uint32_t *ps = psum[(b - p.first_block) & 1u];  // two buffers: one barrier per row
+      const uint32_t w = wave_sum(v);
+      if (lane == 0) ps[wid] = w;
       __syncthreads();
-      if (threadIdx.x == 0) {
-        const uint32_t tot = psum[0] + psum[1] + psum[2] + psum[3];
-        if (tot) atomicAdd(&p.part_tot[(size_t)(b - p.first_block) * p.scan_parts + part], tot);
-      }
-      __syncthreads();
+      if (threadIdx.x == 0)
+        p.part_tot[(size_t)(b - p.first_block) * gridDim.x + blockIdx.x] = ps[0] + ps[1] + ps[2] + ps[3];
     }
     if (!in) return;
   }
-  uint32_t run = 0;
-  if (p.first_block) {
-    // sum of (next - own) over the kept rows = (sum of next) - (sum of own);
-    // the last column's "next" is the block total, and those sum to
-    // bbase[first_block] - bbase[0].  Nobody touched the kept rows in this
-    // commit, so they come from HBM: eight rows' loads are issued together.
-    const bool last = t + 1 == p.NC;
-    const uint32_t *own = p.blk + t, *nxt = own + (last ? 0 : 1);
-    uint32_t lo = 0, hi = 0, b = 0;
-    for (; b + 8 <= p.first_block; b += 8) {
-      uint32_t x[8], y[8];
-#pragma unroll
-      for (int j = 0; j < 8; j++) {
-        x[j] = own[(size_t)(b + j) * p.NC];
-        y[j] = nxt[(size_t)(b + j) * p.NC];
-      }
-#pragma unroll
-      for (int j = 0; j < 8; j++) { lo += x[j]; hi += y[j]; }
-    }
-    for (; b < p.first_block; b++) {
-      lo += own[(size_t)b * p.NC];
-      hi += nxt[(size_t)b * p.NC];
-    }
-    run = (last ? (uint32_t)(p.bbase[p.first_block] - p.bbase[0]) : hi) - lo;
-  }
-  for (uint32_t b = p.first_block; b < p.n_blocks; b++) run += p.blk[(size_t)b * p.NC + t];
-  p.blk[(size_t)p.n_blocks * p.NC + t] = run;
+  p.blk[(size_t)p.n_blocks * p.NC + t] = run + full + tail;
+  if (!p.first_block || p.df_fold_end > p.first_block) p.df_base[t] = base + full;
 }
 
 // Kept rows into a wider column layout (the dictionary gained slots since
 // they were laid out): thread per crank word, as k_df_partial's tail walks
 // them; grid.y = kept block.  Never in place: blk_old has stride NC_inv.
-__global__ void __launch_bounds__(256) k_blk_remap(PostingParams p, const uint32_t *blk_old, const uint2 *crank_inv,
-                                                   uint32_t NC_inv) {
+// One more row, grid.y = first_block, moves the df base (df_old -> p.df_base):
+// it is in count form, so a column new to the layout gets 0 (remap_base_value).
+__global__ void __launch_bounds__(256) k_blk_remap(PostingParams p, const uint32_t *blk_old, const uint32_t *df_old,
+                                                   const uint2 *crank_inv, uint32_t NC_inv) {
   const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
   if (w >= (p.C >> 5)) return;
   const uint2 e = p.crank[w], o = crank_inv[w];
+  if (b == p.first_block) {                             // (workgroup-uniform)
+    uint32_t bits = e.x, col = e.y;
+    while (bits) {
+      const uint32_t bit = (uint32_t)__builtin_ctz(bits);
+      bits &= bits - 1;
+      p.df_base[col++] = remap_base_value(df_old, o.x, o.y, bit);
+    }
+    return;
+  }
   const uint32_t *old_row = blk_old + (size_t)b * NC_inv;
   uint32_t *row = p.blk + (size_t)b * p.NC;
   const uint32_t total = (uint32_t)(p.bbase[b + 1] - p.bbase[b]);
@@ -2849,9 +2879,11 @@ __global__ void __launch_bounds__(1024) k_row_scan(PostingParams p) {
 // Few rows (commit_plan.h slice_plan): a row's columns in p.scan_parts parts
 // of p.scan_width, one workgroup each (grid = rows x parts).  The scan is in
 // place, so a part never reads another part's columns: its first offset is
-// the sum of the totals of the parts before it, which k_df_sum<true> left in
-// part_tot before any part writes.  The last part leaves the row total in
-// bbase[b + 1]; a forced part count may leave parts without columns.
+// the sum of the counts of the columns before it, which k_df_sum<true> left
+// in part_tot per 256 columns (one word per workgroup of its grid) before any
+// part writes: the part sums the words of the workgroups before its first
+// column.  The last part leaves the row total in bbase[b + 1]; a forced part
+// count may leave parts without columns.
 __global__ void __launch_bounds__(1024) k_row_scan_parts(PostingParams p) {
   __shared__ uint32_t wsum[16];
   __shared__ uint32_t carry_sh;
@@ -2860,11 +2892,20 @@ __global__ void __launch_bounds__(1024) k_row_scan_parts(PostingParams p) {
   uint32_t *row = p.blk + (size_t)b * p.NC;
   const uint64_t a = (uint64_t)part * p.scan_width;
   const uint32_t c0 = (uint32_t)(a < p.NC ? a : p.NC), c1 = (uint32_t)(a + p.scan_width < p.NC ? a + p.scan_width : p.NC);
-  if (threadIdx.x == 0) {
-    const uint32_t *tot = p.part_tot + (size_t)rb * p.scan_parts;
+  {
+    const uint32_t n_wg = (p.NC + kScanPartAlign - 1) / kScanPartAlign;          // k_df_sum's grid
+    const uint32_t before = (uint32_t)(a / kScanPartAlign < n_wg ? a / kScanPartAlign : n_wg);
+    const uint32_t *tot = p.part_tot + (size_t)rb * n_wg;
     uint32_t start = 0;
-    for (uint32_t j = 0; j < part; j++) start += tot[j];
-    carry_sh = start;
+    for (uint32_t j = threadIdx.x; j < before; j += blockDim.x) start += tot[j];
+    start = wave_sum(start);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = start;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t all = 0;
+      for (uint32_t w = 0; w < 16; w++) all += wsum[w];
+      carry_sh = all;
+    }
   }
   __syncthreads();
   row_scan_span(row, c0, c1, wsum, &carry_sh);
@@ -3279,9 +3320,10 @@ static_assert(kSliceGroupDocs % (4 * kDfQuads) == 0 && kSliceGroupDocs % (4 * kP
               "a slice is a whole number of the loaders' document groups");
 static_assert(kScanPartAlign == 256 && kScanPartCols == 16384, "k_df_sum's workgroup, k_row_scan's round");
 
-// What a sliced / split inversion adds into, in one launch: the count rows of
-// the inverted blocks and the tiles' stream cursors (slices > 1), the rows'
-// part totals (scan_parts > 1).  slice_cur and part_tot are one array.
+// What a sliced inversion adds into, in one launch: the count rows of the
+// inverted blocks and the tiles' stream cursors (slices > 1).  The rows' part
+// totals behind them (part_tot, the same array) are stored, never added to,
+// and need no zeroing.
 __global__ void __launch_bounds__(256) k_inv_zero(uint32_t *rows, uint64_t n_rows, uint32_t *aux, uint64_t n_aux) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_rows + n_aux; i += stride) {
@@ -3291,16 +3333,14 @@ __global__ void __launch_bounds__(256) k_inv_zero(uint32_t *rows, uint64_t n_row
 }
 hipError_t launch_inv_zero(const PostingParams &p, hipStream_t s) {
   const uint64_t nb = p.n_blocks - p.first_block;
-  if (nb == 0 || (p.slices <= 1 && p.scan_parts <= 1)) return hipSuccess;
-  const uint64_t n_rows = p.slices > 1 ? nb * p.NC : 0;
-  const uint64_t n_cur = p.slices > 1 ? nb * p.n_ranges * kPartStreams : 0;
-  const uint64_t n_tot = p.scan_parts > 1 ? nb * p.scan_parts : 0;
-  if (p.slices > 1 && p.scan_parts > 1 && p.part_tot != p.slice_cur + n_cur) return hipErrorInvalidValue;
-  uint32_t *aux = p.slices > 1 ? p.slice_cur : p.part_tot;
-  const uint64_t n = n_rows + n_cur + n_tot;
+  if (nb == 0 || p.slices <= 1) return hipSuccess;
+  const uint64_t n_rows = nb * p.NC;
+  const uint64_t n_cur = nb * p.n_ranges * kPartStreams;
+  if (p.scan_parts > 1 && p.part_tot != p.slice_cur + n_cur) return hipErrorInvalidValue;
+  const uint64_t n = n_rows + n_cur;
   const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 1023) / 1024, 1024));
-  hipLaunchKernelGGL(k_inv_zero, dim3(grid), dim3(256), 0, s, p.blk + (size_t)p.first_block * p.NC, n_rows, aux,
-                     n_cur + n_tot);
+  hipLaunchKernelGGL(k_inv_zero, dim3(grid), dim3(256), 0, s, p.blk + (size_t)p.first_block * p.NC, n_rows, p.slice_cur,
+                     n_cur);
   return hipGetLastError();
 }
 
@@ -3317,6 +3357,7 @@ hipError_t launch_df_partial(const PostingParams &p, hipStream_t s) {
 }
 hipError_t launch_df_sum(const PostingParams &p, hipStream_t s) {
   if (p.NC == 0) return hipSuccess;
+  if (!p.df_base || p.df_fold_end < p.first_block || p.df_fold_end > p.n_blocks) return hipErrorInvalidValue;
   if (p.scan_parts > 1 && p.n_blocks != p.first_block)
     hipLaunchKernelGGL(k_df_sum<true>, dim3((p.NC + 255) / 256), dim3(256), 0, s, p);
   else
@@ -3330,11 +3371,12 @@ hipError_t launch_row_scan(const PostingParams &p, hipStream_t s) {
   else hipLaunchKernelGGL(k_row_scan, dim3(nb), dim3(1024), 0, s, p);
   return hipGetLastError();
 }
-hipError_t launch_blk_remap(const PostingParams &p, const uint32_t *blk_old, const uint2 *crank_inv, uint32_t NC_inv,
-                            hipStream_t s) {
+hipError_t launch_blk_remap(const PostingParams &p, const uint32_t *blk_old, const uint32_t *df_old,
+                            const uint2 *crank_inv, uint32_t NC_inv, hipStream_t s) {
   if (!p.first_block || !(p.C >> 5)) return hipSuccess;
-  hipLaunchKernelGGL(k_blk_remap, dim3(((p.C >> 5) + 255) / 256, p.first_block), dim3(256), 0, s, p, blk_old, crank_inv,
-                     NC_inv);
+  if (!df_old || !p.df_base || df_old == p.df_base) return hipErrorInvalidValue;   // (never in place)
+  hipLaunchKernelGGL(k_blk_remap, dim3(((p.C >> 5) + 255) / 256, p.first_block + 1), dim3(256), 0, s, p, blk_old, df_old,
+                     crank_inv, NC_inv);
   return hipGetLastError();
 }
 // number of nonzero entries of a[0, n) (occupied dictionary slots): one

@@ -333,6 +333,13 @@ struct Snapshot {
   uint64_t inv_docs = 0;
   uint32_t NC_inv = 0;
   DevMem crank_inv, blk_alt;
+  // ... and the df base (commit_plan.h df_base_plan): per column of blk's
+  // layout, the counts of blocks [0, inv_docs / 8192), the blocks that were
+  // full at the last inversion.  Valid exactly when the kept blk rows are
+  // (inv_docs != 0 under the same signature); k_df_sum updates it in place,
+  // which a failed commit's inv_docs = 0 makes harmless.  df_base_alt: the
+  // target a remap writes it to (then swapped, as blk_alt).
+  DevMem df_base, df_base_alt;
   PinnedVec<uint64_t> h_bbase;
   PinnedVec<uint64_t> h_dict;          // host mirrors for query analysis (pinned)
   PinnedVec<uint32_t> h_df;
@@ -353,7 +360,8 @@ struct Snapshot {
   std::mutex mlt_mu;
   explicit Snapshot(int d)
       : dev(d), dict(d), csr(d), csr_esc(d), post_esc(d), doc_len(d), doc_nuniq(d), doc_norm(d), rsplit(d), blk(d),
-        bbase(d), post(d), row_off(d), toff(d), tdf(d), crank(d), sdf(d), crank_inv(d), blk_alt(d), mlt_idf(d) {}
+        bbase(d), post(d), row_off(d), toff(d), tdf(d), crank(d), sdf(d), crank_inv(d), blk_alt(d), df_base(d),
+        df_base_alt(d), mlt_idf(d) {}
   const uint32_t *df_dev() const { return term_major ? tdf.as<uint32_t>() : sdf.as<uint32_t>(); }   // per slot
   // what the scorers index a term's postings by: its column (block-major) or
   // its dictionary slot (term-major); the scorers' C is the matching count
@@ -1723,11 +1731,16 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   const InversionPlan inv = inversion_plan(plan.full, S.term_major, kept_inv, N, S.NC, S.NC_inv,
                                            knob("TFIDF_FULL_INVERSION"));
   const uint32_t first_block = inv.first_block;
+  // ... their df comes from the snapshot's df base, which takes the rows that are full now (df_base_plan)
+  const DfBasePlan dbp = df_base_plan(inv, S.term_major, N, knob("TFIDF_DF_FROM_ROWS"));
   // ... and how the host mirrors follow (commit_plan.h): whole, or the new slots and changed df alone
   uint32_t df_cap = kDfDeltaCap;
   if (const char *e = knob("TFIDF_TEST_DF_DELTA_CAP")) df_cap = (uint32_t)std::max(1, std::min(atoi(e), (int)kDfDeltaCap));
   const MirrorPlan mp = mirror_plan(plan.full, S.term_major, kept_inv, mir_was_ok, C, S.NC, S.NC_inv, hctr[2], df_cap,
                                     knob("TFIDF_FULL_MIRROR"));
+  // sdf stands when nothing it is made from changed (the commit that adds nothing)
+  const bool keep_sdf = !plan.full && !S.term_major &&
+                        df_slots_kept(mp, kept_inv, N, inv.remap, S.NC, S.NC_inv, knob("TFIDF_DF_SLOTS_ALWAYS"));
   // the fused delta kernel builds either list; it replaces k_df_slots only when one is wanted
   const bool dict_delta = mp.dict == kMirrorDelta, df_delta = mp.df == kMirrorDelta;
   const bool dict_whole = mp.dict == kMirrorWhole, df_whole = mp.df == kMirrorWhole, crank_whole = mp.crank == kMirrorWhole;
@@ -1754,19 +1767,29 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
                     knob("TFIDF_TEST_SCAN_PARTS"));
     if (sp.slices > 1 || sp.scan_parts > 1)
       HIP_TRY(ix->inv_aux.reserve_slack(((uint64_t)inv_blocks * S.R * 64 * (sp.slices > 1) +
-                                         (uint64_t)inv_blocks * sp.scan_parts * (sp.scan_parts > 1)) * 4));
+                                         (uint64_t)inv_blocks * ((S.NC + kScanPartAlign - 1) / kScanPartAlign) *
+                                             (sp.scan_parts > 1)) * 4));   // (part_tot: a word per k_df_sum workgroup and row)
   }
   ix->last_inv_slices = sp.slices;
   ix->last_inv_scan_parts = sp.scan_parts;
-  const uint32_t *blk_old = nullptr;
+  const uint32_t *blk_old = nullptr, *df_old = nullptr;
   if (!S.term_major) {
     const uint64_t blk_need = (uint64_t)(S.n_blocks + 1) * S.NC * 4 + 16;
+    const uint64_t base_need = (uint64_t)S.NC * 4 + 16;
     if (inv.remap) {
       HIP_TRY(S.blk_alt.reserve(blk_need + blk_need / 8));   // (slack: a shard that keeps gaining terms remaps every commit)
       std::swap(S.blk.p, S.blk_alt.p);
       std::swap(S.blk.bytes, S.blk_alt.bytes);
       blk_old = S.blk_alt.as<uint32_t>();
-    } else if (int rc = grow_keep(ix, &S.blk, blk_need, (uint64_t)first_block * S.NC * 4)) return rc;
+      HIP_TRY(S.df_base_alt.reserve(base_need + base_need / 8));
+      std::swap(S.df_base.p, S.df_base_alt.p);
+      std::swap(S.df_base.bytes, S.df_base_alt.bytes);
+      df_old = S.df_base_alt.as<uint32_t>();
+    } else {
+      if (int rc = grow_keep(ix, &S.blk, blk_need, (uint64_t)first_block * S.NC * 4)) return rc;
+      // (a trusted base has this commit's NC columns already: without a remap NC is NC_inv)
+      if (int rc = grow_keep(ix, &S.df_base, base_need + base_need / 8, dbp.trusted ? (uint64_t)S.NC * 4 : 0)) return rc;
+    }
     if (int rc = grow_keep(ix, &S.bbase, (uint64_t)(S.n_blocks + 2) * 8, first_block ? (uint64_t)(first_block + 1) * 8 : 0))
       return rc;
   }
@@ -1851,6 +1874,9 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   pp.scan_width = sp.scan_width;
   pp.slice_cur = ix->inv_aux.as<uint32_t>();
   pp.part_tot = pp.slice_cur + (sp.slices > 1 ? (size_t)(S.n_blocks - first_block) * S.R * 64 : 0);
+  pp.df_base = S.df_base.as<uint32_t>();
+  pp.df_fold_end = dbp.fold_end;
+  pp.df_from_rows = dbp.from_rows ? 1u : 0u;
   HIP_TRY(hipEventRecord(ix->ev[EV_D0], s));
   if (S.term_major) {
     TermParams tp{};
@@ -1910,7 +1936,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     HIP_TRY(launch_term_sort(tp, s));
     HIP_TRY(hipEventRecord(ix->ev[EV_SCAT], s));
   } else {
-    if (inv.remap) HIP_TRY(launch_blk_remap(pp, blk_old, S.crank_inv.as<uint2>(), S.NC_inv, s));
+    if (inv.remap) HIP_TRY(launch_blk_remap(pp, blk_old, df_old, S.crank_inv.as<uint2>(), S.NC_inv, s));
     if (S.n_blocks) {
       HIP_TRY(launch_inv_zero(pp, s));                    // (sliced / split shapes only)
       HIP_TRY(launch_df_partial(pp, s));                  // blocks [first_block, n_blocks)
@@ -1936,7 +1962,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
       dp.df_cap = df_cap;
       dp.df_count = reinterpret_cast<uint32_t *>(ctr + 14);
       HIP_TRY(launch_df_slots_delta(dp, s));
-    } else {
+    } else if (!keep_sdf) {
       HIP_TRY(launch_df_slots(S.crank.as<uint2>(), S.blk.as<uint32_t>() + (size_t)S.n_blocks * S.NC, C,
                               S.sdf.as<uint32_t>(), s));
     }
@@ -2265,7 +2291,7 @@ extern "C" int tfidf_stats(const tfidf_index *ix, tfidf_index_stats *out) {
   if (S) {
     const DevBuf *bufs[] = {&S->dict, &S->csr, &S->csr_esc, &S->doc_len, &S->doc_nuniq, &S->doc_norm,
                             &S->rsplit, &S->blk, &S->bbase, &S->post, &S->toff, &S->tdf, &S->crank, &S->sdf,
-                            &S->crank_inv, &S->blk_alt};
+                            &S->crank_inv, &S->blk_alt, &S->df_base, &S->df_base_alt};
     for (const DevBuf *b : bufs) tot += b->bytes;
   }
   out->device_bytes = tot;

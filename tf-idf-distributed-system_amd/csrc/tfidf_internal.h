@@ -242,7 +242,11 @@ struct PostingParams {
   uint32_t slices, slice_docs;      // document slices per (block, range) tile, documents per slice
   uint32_t scan_parts, scan_width;  // workgroups per block row in the row scan, columns per part
   uint32_t *slice_cur;        // [(n_blocks - first_block) * n_ranges * 64] postings appended per (block, range, stream); zeroed per commit
-  uint32_t *part_tot;         // [(n_blocks - first_block) * scan_parts] row totals per part (k_df_sum); zeroed per commit
+  uint32_t *part_tot;         // [(n_blocks - first_block) * ceil(NC / 256)] row totals per k_df_sum workgroup (scan_parts > 1)
+  // the kept df base (commit_plan.h df_base_plan)
+  uint32_t *df_base;          // [NC] counts of blocks [0, first_block) per column; k_df_sum adds rows [first_block, df_fold_end)
+  uint32_t df_fold_end;       // the blocks that are full now (n_docs / kBlockDocs), >= first_block
+  uint32_t df_from_rows;      // A/B: df of the kept blocks from their rows (the base is kept up all the same)
 };
 
 // Raise a kernel's dynamic-LDS limit on the current device, once per device:
@@ -297,7 +301,7 @@ hipError_t launch_tokenize_uchunk(const BuildParams &p, int grid, hipStream_t s)
 constexpr uint32_t kUwaveWGsPerCU = 7;    // 64-thread workgroups, ~22 KB LDS each (two waves per SIMD)
 constexpr uint32_t kUchunkWGsPerCU = 8;   // k_tokenize_uchunk: ~19 KB LDS each
 hipError_t launch_verify_deferred(const BuildParams &p, hipStream_t s);           // kernels_index.hip
-// sliced / split shape: zeroes the rows the slices add into, slice_cur and part_tot (one launch; before launch_df_partial)
+// sliced shape: zeroes the rows the slices add into and slice_cur (one launch; before launch_df_partial)
 hipError_t launch_inv_zero(const PostingParams &p, hipStream_t s);
 hipError_t launch_df_partial(const PostingParams &p, hipStream_t s);
 hipError_t launch_df_sum(const PostingParams &p, hipStream_t s);
@@ -325,9 +329,10 @@ struct MirrorDeltaParams {
 };
 hipError_t launch_df_slots_delta(const MirrorDeltaParams &p, hipStream_t s);
 hipError_t launch_scatter(const PostingParams &p, hipStream_t s);
-// kept blk rows [0, rows) from the column layout of crank_inv (stride NC_inv) to that of p.crank (p.blk, stride p.NC)
-hipError_t launch_blk_remap(const PostingParams &p, const uint32_t *blk_old, const uint2 *crank_inv, uint32_t NC_inv,
-                            hipStream_t s);
+// kept blk rows [0, rows) from the column layout of crank_inv (stride NC_inv) to that of p.crank (p.blk, stride p.NC),
+// and the df base with them (df_old -> p.df_base, count form)
+hipError_t launch_blk_remap(const PostingParams &p, const uint32_t *blk_old, const uint32_t *df_old,
+                            const uint2 *crank_inv, uint32_t NC_inv, hipStream_t s);
 
 // --- term-major inversion for large vocabularies (kernels_term.hip) ---
 // (hand-written LSD radix sort of packed words slot | doc | tf | norm)
