@@ -149,6 +149,8 @@ typedef struct tfidf_commit_timing {
   float ms_total;
   float ms_tokenize;   /* tfidf_tokenize_count: text -> per-doc TF rows (CSR) */
   float ms_long;       /* long-document path */
+  /* (a lone inverted block taken in one launch, tfidf_commit_inversion_fused: ms_df also carries the DF
+   * sum, the offset scan and the block base; ms_blockscan is the per-slot df kernel alone, ms_colscan ~0) */
   float ms_df;         /* per (doc block, term range) DF histograms */
   float ms_blockscan;  /* DF = sum over doc blocks + per-block posting offsets (scan over slots) */
   float ms_colscan;    /* exclusive scan of block totals -> block bases */
@@ -258,6 +260,13 @@ int tfidf_add_docs_device(tfidf_index *ix, const void *d_utf8, const void *d_off
  *   term-major).  Few inverted blocks (an incremental commit's tail) are cut
  *   up so that they use the whole device; the published index is the same
  *   under every shape.  Each pointer may be NULL.
+ * tfidf_commit_inversion_fused: *fused = 1 when the last tfidf_commit inverted
+ *   exactly one block in two or more slices and took its counts, df, column
+ *   offsets and block base in one launch (the usual case of an incremental
+ *   commit's tail block), 0 when it ran the separate kernels.  The published
+ *   index is the same either way.  TFIDF_DEBUG=1 TFIDF_INV_UNFUSED=1 keeps the
+ *   separate kernels (A/B runs); a forced TFIDF_TEST_SCAN_PARTS and
+ *   TFIDF_DF_FROM_ROWS do as well.
  * Host mirrors: df lookups, the vocabulary export, query analysis and the
  *   GLOBAL setters read pinned host copies of a snapshot's dictionary keys,
  *   per-slot df and slot -> column words.  An incremental block-major commit
@@ -277,6 +286,7 @@ int tfidf_commit_tokenized_docs(const tfidf_index *ix, uint64_t *docs, uint32_t 
 int tfidf_commit_inverted_blocks(const tfidf_index *ix, uint32_t *first_block, uint32_t *n_blocks,
                                  uint32_t *remapped);
 int tfidf_commit_inversion_shape(const tfidf_index *ix, uint32_t *slices, uint32_t *scan_parts);
+int tfidf_commit_inversion_fused(const tfidf_index *ix, uint32_t *fused);
 int tfidf_commit_host_profile(const tfidf_index *ix, tfidf_host_profile *out);
 
 /* ---- document lifecycle: delete, reclaim, read back ----

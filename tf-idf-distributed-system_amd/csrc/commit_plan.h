@@ -2,10 +2,12 @@
 // build target's rows and dictionary can be kept (and from which document the
 // tokenizers then start), how the kept host lists take the new entries, and
 // how the host mirrors of the dictionary and df follow, the launch shape
-// of a few-block inversion, and the df base a snapshot keeps for its kept
-// blocks.  Plain C++ (no HIP), so the decisions are tested on their own
+// of a few-block inversion, when a lone block is inverted in one launch, and
+// the df base a snapshot keeps for its kept blocks.  Plain C++ (no HIP), so the
+// decisions are tested on their own
 // (tests/commit_plan_check.cpp, tests/mirror_plan_check.cpp,
-// tests/slice_plan_check.cpp, tests/df_base_plan_check.cpp).
+// tests/slice_plan_check.cpp, tests/df_base_plan_check.cpp,
+// tests/fuse_plan_check.cpp).
 #pragma once
 
 #include <stdint.h>
@@ -295,6 +297,80 @@ inline void scan_part_range(const SlicePlan &p, uint32_t j, uint32_t NC, uint64_
   const uint64_t a = (uint64_t)j * p.scan_width;
   *lo = std::min<uint64_t>(a, NC);
   *hi = std::min<uint64_t>(a + p.scan_width, NC);
+}
+
+// ---------------------------------------------------------------------------
+// A lone inverted block (an incremental commit's tail): count, df, row scan
+// and block base in one launch (k_df_fused) instead of k_inv_zero, k_df_partial<true>,
+// k_df_sum<true>, k_row_scan_parts and k_block_scan.  The slices of a range add
+// their counts into a scratch row; the last of them to finish (a ticket per
+// range) turns the range's columns into df and offsets.  Nothing a range needs
+// comes from another range's counts: its first offset is the sum over the
+// block's documents of the entries their rows hold before the range (rsplit).
+
+// inv_blocks: n_blocks - first_block; sp: the commit's slice plan.  rows_knob /
+// parts_knob / unfused_knob: TFIDF_DF_FROM_ROWS, TFIDF_TEST_SCAN_PARTS (a forced
+// part count names k_row_scan_parts) and TFIDF_INV_UNFUSED (nullptr = unset; an
+// A/B switch outside the CommitSig: the published index is the same either way).
+inline bool fuse_plan(bool term_major, uint32_t inv_blocks, const SlicePlan &sp, const char *rows_knob,
+                      const char *parts_knob, const char *unfused_knob) {
+  auto on = [](const char *v) { return v && *v && !(v[0] == '0' && !v[1]); };
+  if (term_major || inv_blocks != 1 || sp.slices < 2) return false;
+  if (on(rows_knob) || on(unfused_knob)) return false;
+  if (parts_knob && *parts_knob) return false;            // (as slice_plan reads it: any value forces)
+  return true;
+}
+
+// The slices of the lone block that hold a document (docs >= 1 of them): each
+// draws one ticket per range, so the one that draws this number - 1 is last.
+inline uint32_t fuse_tickets(const SlicePlan &sp, uint64_t docs) {
+  if (docs == 0 || sp.slice_docs == 0) return 0;
+  return (uint32_t)std::min<uint64_t>(sp.slices, (docs + sp.slice_docs - 1) / sp.slice_docs);
+}
+
+// The scratch: [0, fuse_ctl_words(R)) control words (tickets [R], first offsets
+// [R], the block total), then one count word per column.  The kernel finds it
+// zero and leaves it zero, so it is zeroed only when it was just allocated or
+// when the last fused commit is not known to have run to its end.
+TFIDF_PLAN_HD uint32_t fuse_ctl_words(uint32_t R) { return (2 * R + 1 + 63) / 64 * 64; }
+inline uint64_t fuse_scratch_words(uint32_t R, uint32_t NC) { return (uint64_t)fuse_ctl_words(R) + NC; }
+
+struct FuseScratch {
+  uint64_t words = 0;       // allocated (0: none yet)
+  bool clean = false;       // every word is zero: set after a fused commit's last successful synchronisation
+};
+// need: this commit's fuse_scratch_words.  *grow: the buffer must be allocated
+// anew (for at least `need` words).  Returns whether it must be zeroed before
+// the launch.  The caller then marks the scratch dirty (fuse_scratch_launch)
+// until the commit has synchronised without an error (fuse_scratch_done).
+inline bool fuse_scratch_must_zero(const FuseScratch &s, uint64_t need, bool *grow) {
+  *grow = need > s.words;
+  return *grow || !s.clean;
+}
+inline void fuse_scratch_launch(FuseScratch *s, uint64_t words) { s->words = words; s->clean = false; }
+inline void fuse_scratch_done(FuseScratch *s) { s->clean = true; }
+
+// Host model of what a range's last slice computes (k_df_fused's finisher;
+// tests/fuse_plan_check.cpp holds it against a scan of the whole row).
+// rsplit[d R + r]: the entries of document d's row in ranges 0 .. r.
+inline uint64_t fuse_range_start(const uint32_t *rsplit, uint64_t n_docs, uint32_t R, uint32_t r) {
+  uint64_t s = 0;
+  if (r)
+    for (uint64_t d = 0; d < n_docs; d++) s += rsplit[d * R + r - 1];
+  return s;
+}
+inline uint64_t fuse_block_total(const uint32_t *rsplit, uint64_t n_docs, uint32_t R) {
+  uint64_t s = 0;
+  for (uint64_t d = 0; d < n_docs; d++) s += rsplit[d * R + R - 1];
+  return s;
+}
+// offsets[c0 .. c1) = start + the exclusive scan of counts[c0 .. c1); returns the offset behind the span
+inline uint64_t fuse_range_offsets(const uint32_t *counts, uint32_t c0, uint32_t c1, uint64_t start, uint32_t *offsets) {
+  for (uint32_t c = c0; c < c1; c++) {
+    offsets[c] = (uint32_t)start;
+    start += counts[c];
+  }
+  return start;
 }
 
 // ---------------------------------------------------------------------------

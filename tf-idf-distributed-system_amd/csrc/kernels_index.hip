@@ -2545,17 +2545,25 @@ struct InvQuads {               // per lane: its document of each quad
 // that lane by a wave shuffle.  (Each lane loading its own document's words,
 // sixteen lanes the same ones, costs four times the address arithmetic:
 // k_df_partial 0.36 -> 0.49 ms at cfg 2; both kernels are issue-bound.)
+// (*lo_out / *hi_out: the fetching lane's own document's row entries before
+// the range and up to its end, 0 in a lane without a document: k_df_fused sums
+// them; every other caller drops them)
 template <int Q>
-__device__ __forceinline__ InvQuads<Q> inv_quads(const PostingParams &p, uint64_t dd, uint64_t d1, uint32_t r) {
+__device__ __forceinline__ InvQuads<Q> inv_quads_lohi(const PostingParams &p, uint64_t dd, uint64_t d1, uint32_t r,
+                                                      uint32_t *lo_out, uint32_t *hi_out) {
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t d = dd + lane;
   uint64_t at = 0;
   uint32_t n = 0;
+  *lo_out = *hi_out = 0;
   if (lane < (uint32_t)(4 * Q) && d < d1) {
     const uint64_t src = p.live_map ? p.live_map[d] : d;
     const uint32_t lo = r ? p.rsplit[d * p.n_ranges + r - 1] : 0;
+    const uint32_t hi = p.rsplit[d * p.n_ranges + r];
     at = csr_row_base(p.offsets, src) + lo;
-    n = p.rsplit[d * p.n_ranges + r] - lo;
+    n = hi - lo;
+    *lo_out = lo;
+    *hi_out = hi;
   }
   InvQuads<Q> g;
 #pragma unroll
@@ -2566,6 +2574,11 @@ __device__ __forceinline__ InvQuads<Q> inv_quads(const PostingParams &p, uint64_
     g.n[q] = (uint32_t)__shfl((int)n, from, 64);
   }
   return g;
+}
+template <int Q>
+__device__ __forceinline__ InvQuads<Q> inv_quads(const PostingParams &p, uint64_t dd, uint64_t d1, uint32_t r) {
+  uint32_t lo, hi;
+  return inv_quads_lohi<Q>(p, dd, d1, r, &lo, &hi);
 }
 
 // the longest segment among the lane's documents (the follow-up loops run
@@ -2625,6 +2638,51 @@ static uint32_t tiles_grid(uint32_t n_blocks, uint32_t R) { return (n_blocks + 7
 // Each workgroup adds its non-zero counts to the row with global atomics; the
 // row was zeroed on the stream before (k_inv_zero).  A slice holds at most
 // kBlockDocs documents, so the 16-bit counters hold as before.
+//
+// The document loop (df_count_docs) is shared with k_df_fused.  SUMS: each
+// lane also returns the sums of inv_quads_lohi's two values over the documents
+// it fetched (every document of [d0, d1) is fetched by exactly one lane).
+template <bool SUMS>
+__device__ __forceinline__ void df_count_docs(const PostingParams &p, uint32_t *hist, uint64_t d0, uint64_t d1, uint32_t r,
+                                              uint32_t *lo_sum, uint32_t *hi_sum) {
+  const uint32_t nw = blockDim.x >> 6;
+  const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t rmask = (1u << p.range_shift) - 1;
+  constexpr int Q = kDfQuads, E = 4 * Q;
+  const uint64_t step = (uint64_t)nw * E;
+  uint64_t dd = d0 + (uint64_t)wid * E;
+  uint32_t lo, hi, los, his;
+  InvQuads<Q> cur = inv_quads_lohi<Q>(p, dd, d1, r, &los, &his);
+  uint32_t c[E];
+  inv_load<Q>(p, cur, 0, c);
+  auto count = [&](uint32_t e) __attribute__((always_inline)) {
+    const uint32_t sl = e & rmask;
+    atomicAdd(&hist[sl >> 1], 1u << ((sl & 1u) << 4));
+  };
+  while (dd < d1) {
+    const uint64_t dn = dd + step;
+    const InvQuads<Q> nxt = inv_quads_lohi<Q>(p, dn, d1, r, &lo, &hi);
+    if (SUMS) { los += lo; his += hi; }
+    uint32_t cn[E];
+    inv_load<Q>(p, nxt, 0, cn);                                    // next group in flight
+#pragma unroll
+    for (int j = 0; j < E; j++)
+      if (c[j]) count(c[j]);
+    const uint32_t maxn = inv_maxn<Q>(cur);
+    for (uint32_t off = 64; __any(off < maxn); off += 64) {        // segments longer than 64
+      inv_load<Q>(p, cur, off, c);
+#pragma unroll
+      for (int j = 0; j < E; j++)
+        if (c[j]) count(c[j]);
+    }
+    cur = nxt;
+#pragma unroll
+    for (int j = 0; j < E; j++) c[j] = cn[j];
+    dd = dn;
+  }
+  if (SUMS) { *lo_sum = los; *hi_sum = his; }
+}
+
 template <bool SLICED>
 __global__ void __launch_bounds__(1024) k_df_partial(PostingParams p) {
   extern __shared__ uint32_t hist[];
@@ -2645,39 +2703,7 @@ __global__ void __launch_bounds__(1024) k_df_partial(PostingParams p) {
   }
   for (uint32_t i = threadIdx.x; i < RS / 2; i += blockDim.x) hist[i] = 0;
   __syncthreads();
-  const uint32_t nw = blockDim.x >> 6;
-  const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint32_t rmask = RS - 1;
-  constexpr int Q = kDfQuads, E = 4 * Q;
-  const uint64_t step = (uint64_t)nw * E;
-  uint64_t dd = d0 + (uint64_t)wid * E;
-  InvQuads<Q> cur = inv_quads<Q>(p, dd, d1, r);
-  uint32_t c[E];
-  inv_load<Q>(p, cur, 0, c);
-  auto count = [&](uint32_t e) __attribute__((always_inline)) {
-    const uint32_t sl = e & rmask;
-    atomicAdd(&hist[sl >> 1], 1u << ((sl & 1u) << 4));
-  };
-  while (dd < d1) {
-    const uint64_t dn = dd + step;
-    const InvQuads<Q> nxt = inv_quads<Q>(p, dn, d1, r);
-    uint32_t cn[E];
-    inv_load<Q>(p, nxt, 0, cn);                                    // next group in flight
-#pragma unroll
-    for (int j = 0; j < E; j++)
-      if (c[j]) count(c[j]);
-    const uint32_t maxn = inv_maxn<Q>(cur);
-    for (uint32_t off = 64; __any(off < maxn); off += 64) {        // segments longer than 64
-      inv_load<Q>(p, cur, off, c);
-#pragma unroll
-      for (int j = 0; j < E; j++)
-        if (c[j]) count(c[j]);
-    }
-    cur = nxt;
-#pragma unroll
-    for (int j = 0; j < E; j++) c[j] = cn[j];
-    dd = dn;
-  }
+  df_count_docs<false>(p, hist, d0, d1, r, nullptr, nullptr);
   __syncthreads();
   // occupied slots of the range -> their columns (a word's slots hold
   // consecutive columns from its prefix count)
@@ -3222,6 +3248,177 @@ __global__ void __launch_bounds__(1024) k_block_scan(PostingParams p) {
   if (tid == 0 && p.first_block == 0) p.bbase[0] = 0;
 }
 
+// A lone inverted block under a sliced shape (commit_plan.h fuse_plan): count,
+// df, row scan and block base in one launch; the grid is k_df_partial<true>'s.
+// p.fuse = [tickets R | first offsets R | block total | pad] [counts NC], all
+// zero on entry and on exit (fuse_scratch_must_zero), so no launch zeroes
+// anything per commit.
+//   every slice : histogram as k_df_partial; the non-zero counts are added to
+//       the count scratch; the slice's sums of rsplit's `lo` (the entries its
+//       documents' rows hold before the range) and, in the last range, `hi`
+//       are added to the range's first-offset word and the block-total word:
+//       every CSR entry is one posting, so over the block's documents they are
+//       the offset of the range's first column and the block's postings.  Then
+//       the slice draws the range's ticket: every wave drains its atomics, a
+//       barrier, lane 0's agent-scope release, a drain, a relaxed agent-scope
+//       fetch_add.  No workgroup waits for another.
+//   the last slice of a range (ticket p.fuse_tickets - 1; the slices without
+//       documents draw none): one agent-scope acquire, a drain and a barrier,
+//       then the range's columns [c0, c1) in tiles of 16384 as row_scan_span:
+//       df = base + count (k_df_sum's rule for the base, too), the row's
+//       exclusive offsets from the first-offset word, the count scratch back to
+//       0.  It clears its ticket and words, the tile's stream cursors
+//       (slice_cur, for k_scatter_part<true>), and in the last range writes the
+//       block's base as k_block_scan would.
+__global__ void __launch_bounds__(1024) k_df_fused(PostingParams p) {
+  extern __shared__ uint32_t hist[];
+  __shared__ uint32_t wsum[16];
+  __shared__ uint32_t carry_sh, sums_sh[2], last_sh;
+  uint32_t slice, r;
+  if (!tile_of(blockIdx.x, p.slices, p.n_ranges, &slice, &r)) return;
+  const uint32_t b = p.first_block;                               // the lone block (n_blocks == first_block + 1)
+  const uint32_t R = p.n_ranges, RS = 1u << p.range_shift;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  uint64_t d0 = (uint64_t)b * kBlockDocs;
+  uint64_t d1 = d0 + kBlockDocs < p.n_docs ? d0 + kBlockDocs : p.n_docs;
+  d0 += (uint64_t)slice * p.slice_docs;
+  if (d0 >= d1) return;                                           // workgroup-uniform: no documents, no ticket
+  d1 = d0 + p.slice_docs < d1 ? d0 + p.slice_docs : d1;
+  // the range's columns [c0, c1), for the finisher: read here, so that nothing waits for them behind the ticket
+  const uint32_t w0 = (r << p.range_shift) >> 5;
+  const uint32_t c0 = min(p.crank[w0].y, p.NC);
+  const uint32_t c1 = r + 1 < R ? min(p.crank[((r + 1) << p.range_shift) >> 5].y, p.NC) : p.NC;
+  for (uint32_t i = tid; i < RS / 2; i += blockDim.x) hist[i] = 0;
+  if (tid < 2) sums_sh[tid] = 0;
+  __syncthreads();
+  uint32_t lo_sum, hi_sum;
+  df_count_docs<true>(p, hist, d0, d1, r, &lo_sum, &hi_sum);
+  lo_sum = wave_sum(lo_sum);
+  hi_sum = wave_sum(hi_sum);
+  if (lane == 0) {
+    if (lo_sum) atomicAdd(&sums_sh[0], lo_sum);
+    if (hi_sum) atomicAdd(&sums_sh[1], hi_sum);
+  }
+  __syncthreads();
+  uint32_t *ctl = p.fuse, *cnt = p.fuse + fuse_ctl_words(R);
+  for (uint32_t w = tid; w < (RS >> 5); w += blockDim.x) {
+    const uint2 e = p.crank[w0 + w];
+    uint32_t bits = e.x, col = e.y;
+    while (bits) {
+      const uint32_t sl = 32 * w + (uint32_t)__builtin_ctz(bits);
+      bits &= bits - 1;
+      const uint32_t n = (hist[sl >> 1] >> ((sl & 1u) << 4)) & 0xFFFFu;
+      if (n) atomicAdd(&cnt[col], n);
+      col++;
+    }
+  }
+  if (tid == 0) {
+    if (sums_sh[0]) atomicAdd(&ctl[R + r], sums_sh[0]);
+    if (r + 1 == R && sums_sh[1]) atomicAdd(&ctl[2 * R], sums_sh[1]);
+  }
+  // the range's ticket (one release per slice, one acquire per range)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const uint32_t t = __hip_atomic_fetch_add(&ctl[r], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    last_sh = t + 1 == p.fuse_tickets ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!last_sh) return;                                           // workgroup-uniform
+  if (tid == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __syncthreads();
+  // (the first offset is in flight beside the first tile's loads: carry_sh is read behind that tile's first barrier)
+  uint32_t start = 0;
+  if (tid == 0) start = __hip_atomic_load(&ctl[R + r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const bool trusted = p.first_block != 0;
+  const bool fold = !p.first_block || p.df_fold_end > p.first_block;       // k_df_sum's rule: the base is rewritten
+  const bool full_now = p.first_block < p.df_fold_end;                      // ... and takes this block's counts
+  uint32_t *row = p.blk + (size_t)b * p.NC, *dfc = p.blk + (size_t)p.n_blocks * p.NC;
+  for (uint32_t t0 = c0; t0 < c1; t0 += 16384) {
+    const uint32_t i0 = t0 + tid * 16;
+    const bool whole = i0 + 16 <= c1;
+    uint32_t v[16], bs[16];
+    if (whole) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const csr_quad_t x = *reinterpret_cast<const csr_quad_t *>(cnt + i0 + 4 * q);
+        v[4 * q] = x.x; v[4 * q + 1] = x.y; v[4 * q + 2] = x.z; v[4 * q + 3] = x.w;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        csr_quad_t x = {0u, 0u, 0u, 0u};
+        if (trusted) x = *reinterpret_cast<const csr_quad_t *>(p.df_base + i0 + 4 * q);
+        bs[4 * q] = x.x; bs[4 * q + 1] = x.y; bs[4 * q + 2] = x.z; bs[4 * q + 3] = x.w;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 16; q++) {
+        v[q] = i0 + q < c1 ? cnt[i0 + q] : 0u;
+        bs[q] = trusted && i0 + q < c1 ? p.df_base[i0 + q] : 0u;
+      }
+    }
+    uint32_t tot = 0;
+#pragma unroll
+    for (int q = 0; q < 16; q++) tot += v[q];
+    const uint32_t x = wave_incl_add(tot);
+    if (lane == 63) wsum[wid] = x;
+    if (tid == 0 && t0 == c0) carry_sh = start;
+    __syncthreads();
+    uint32_t base = carry_sh, all = 0;
+    for (uint32_t w = 0; w < 16; w++) {
+      const uint32_t sw = wsum[w];
+      if (w < wid) base += sw;
+      all += sw;
+    }
+    base += x - tot;
+    __syncthreads();
+    if (tid == 0) carry_sh += all;
+    uint32_t o[16];
+#pragma unroll
+    for (int q = 0; q < 16; q++) { o[q] = base; base += v[q]; }
+    if (whole) {
+      const csr_quad_t zero = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const csr_quad_t vv = {v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
+        const csr_quad_t bb = {bs[4 * q], bs[4 * q + 1], bs[4 * q + 2], bs[4 * q + 3]};
+        const csr_quad_t oo = {o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]};
+        *reinterpret_cast<csr_quad_t *>(cnt + i0 + 4 * q) = zero;
+        *reinterpret_cast<csr_quad_t *>(dfc + i0 + 4 * q) = bb + vv;
+        if (fold) *reinterpret_cast<csr_quad_t *>(p.df_base + i0 + 4 * q) = full_now ? bb + vv : bb;
+        *reinterpret_cast<csr_quad_t *>(row + i0 + 4 * q) = oo;
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 16; q++)
+        if (i0 + q < c1) {
+          cnt[i0 + q] = 0;
+          dfc[i0 + q] = bs[q] + v[q];
+          if (fold) p.df_base[i0 + q] = full_now ? bs[q] + v[q] : bs[q];
+          row[i0 + q] = o[q];
+        }
+    }
+    __syncthreads();
+  }
+  if (tid < kPartStreams) p.slice_cur[(size_t)r * kPartStreams + tid] = 0;
+  if (tid == 0) {
+    __hip_atomic_store(&ctl[r], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&ctl[R + r], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (r + 1 == R) {
+      const uint32_t total = __hip_atomic_load(&ctl[2 * R], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&ctl[2 * R], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint64_t bb = p.first_block ? p.bbase[b] : 0ull;       // (k_block_scan: bbase[0] = 0 when nothing is kept)
+      if (!p.first_block) p.bbase[0] = 0;
+      p.bbase[b + 1] = bb + total;
+    }
+  }
+}
+
 // Hashed-key checks deferred by dict_verify (the slot's reference occurrence
 // was not visible yet): every reference is final after the tokenizers.
 __global__ void __launch_bounds__(256) k_verify_deferred(BuildParams p) {
@@ -3353,6 +3550,17 @@ hipError_t launch_df_partial(const PostingParams &p, hipStream_t s) {
     hipLaunchKernelGGL(k_df_partial<true>, dim3(tiles_grid(nb * p.slices, p.n_ranges)), dim3(1024), lds, s, p);
   else
     hipLaunchKernelGGL(k_df_partial<false>, dim3(tiles_grid(nb, p.n_ranges)), dim3(1024), lds, s, p);
+  return hipGetLastError();
+}
+// k_df_fused in place of launch_inv_zero, launch_df_partial, launch_df_sum, launch_row_scan and launch_block_base
+hipError_t launch_df_fused(const PostingParams &p, hipStream_t s) {
+  static std::atomic<uint64_t> done{0};
+  allow_dyn_lds((const void *)k_df_fused, 2 << kRangeBits, done);
+  if (p.n_blocks != p.first_block + 1 || p.slices < 2 || !p.fuse || !p.slice_cur || !p.df_base || p.df_from_rows ||
+      p.fuse_tickets == 0 || p.fuse_tickets > p.slices || p.df_fold_end < p.first_block || p.df_fold_end > p.n_blocks)
+    return hipErrorInvalidValue;
+  const size_t lds = (size_t)2 << p.range_shift;             // 16-bit counters
+  hipLaunchKernelGGL(k_df_fused, dim3(tiles_grid(p.slices, p.n_ranges)), dim3(1024), lds, s, p);
   return hipGetLastError();
 }
 hipError_t launch_df_sum(const PostingParams &p, hipStream_t s) {

@@ -479,6 +479,7 @@ struct tfidf_index {
   uint32_t last_inv_first = 0, last_inv_blocks = 0, last_inv_remap = 0;
   // ... and the launch shape it ran in (commit_plan.h slice_plan; tfidf_commit_inversion_shape)
   uint32_t last_inv_slices = 1, last_inv_scan_parts = 1;
+  uint32_t last_inv_fused = 0;         // ... and whether a lone block took k_df_fused (fuse_plan; tfidf_commit_inversion_fused)
   // host side of the last commit (tfidf_commit_host_profile): points since prof_t0
   tfidf_host_profile prof{};
   std::chrono::steady_clock::time_point prof_t0;
@@ -496,6 +497,8 @@ struct tfidf_index {
   // their pinned host copies (sized once for the largest list, so no commit reallocates pinned memory)
   DevBuf mir_dict_list, mir_df_list;
   DevBuf inv_aux;                      // sliced inversion (commit_plan.h slice_plan): the tiles' stream cursors, the rows' part totals
+  DevBuf inv_fuse;                     // k_df_fused's tickets, first offsets and count row: zero between commits ...
+  FuseScratch fuse_state;              // ... as far as the host knows (fuse_scratch_must_zero)
   PinnedVec<DictDelta> h_dict_delta;
   PinnedVec<DfDelta> h_df_delta;
   DevBuf bad_list;                     // documents that are not valid UTF-8 (indexed empty)
@@ -664,7 +667,7 @@ extern "C" int tfidf_destroy(tfidf_index *ix) {
   ix->text.reset();
   ix->offsets.reset();
   DevBuf *bufs[] = {&ix->d_live_map, &ix->long_list, &ix->uni_list, &ix->counters, &ix->retry_list, &ix->new_list, &ix->bad_list,
-                    &ix->mir_dict_list, &ix->mir_df_list, &ix->inv_aux,
+                    &ix->mir_dict_list, &ix->mir_df_list, &ix->inv_aux, &ix->inv_fuse,
                     &ix->post_tmp, &ix->lt_keys, &ix->lt_cnt, &ix->lt_g, &ix->lt_pos, &ix->verify_defer, &ix->pairs,
                     &ix->pair_ub, &ix->chunk_list, &ix->chunk_docs, &ix->chunk_fail, &ix->uchunk, &ix->canon_of_slot,
                     &ix->tvals, &ix->term_tmp, &ix->term_esc, &ix->sent_slot, &ix->vcounts, &ix->vnu, &ix->vt_table,
@@ -1572,7 +1575,9 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   // one read of the counters: stats (0-2), error flags (3), long (4) and
   // non-ASCII (6) document counts, columns (7), CSR escapes (9) (32-bit
   // counters in the low halves); read again only when the long path ran
-  HIP_TRY(ix->hctr_h.resize(14));                      // pinned: a pageable read is staged by the runtime
+  // pinned: a pageable read is staged by the runtime (and makes the copy call wait for the stream).
+  // [0, 14): the counters after the tokenizers; [14, 27): the commit's last read (tail)
+  HIP_TRY(ix->hctr_h.resize(14 + 13));
   uint64_t *hctr = ix->hctr_h.data();
   HIP_TRY(hipMemcpyAsync(hctr, ctr, 14 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(commit_sync(ix, s));
@@ -1772,6 +1777,25 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   }
   ix->last_inv_slices = sp.slices;
   ix->last_inv_scan_parts = sp.scan_parts;
+  // a lone sliced block: count, df, row scan and block base in one launch (fuse_plan).  Its scratch is
+  // left zero by the kernel; it is zeroed here when new, or when the last fused commit did not reach
+  // its synchronisation (the flag stays down from here until then)
+  const bool fused = fuse_plan(S.term_major, S.term_major ? 0u : S.n_blocks - first_block, sp, knob("TFIDF_DF_FROM_ROWS"),
+                               knob("TFIDF_TEST_SCAN_PARTS"), knob("TFIDF_INV_UNFUSED"));
+  ix->last_inv_fused = fused ? 1u : 0u;
+  if (fused) {
+    const uint64_t need = fuse_scratch_words(S.R, S.NC);
+    bool grow = false;
+    const bool zero = fuse_scratch_must_zero(ix->fuse_state, need, &grow);
+    uint64_t words = ix->fuse_state.words;
+    if (grow) {
+      ix->fuse_state = FuseScratch{};
+      HIP_TRY(ix->inv_fuse.reserve((size_t)((need + need / 8 + 4096 + 15) / 16 * 16) * 4));   // (NC grows with the vocabulary)
+      words = ix->inv_fuse.bytes / 4;
+    }
+    if (zero) HIP_TRY(hipMemsetAsync(ix->inv_fuse.p, 0, (size_t)words * 4, s));
+    fuse_scratch_launch(&ix->fuse_state, words);
+  }
   const uint32_t *blk_old = nullptr, *df_old = nullptr;
   if (!S.term_major) {
     const uint64_t blk_need = (uint64_t)(S.n_blocks + 1) * S.NC * 4 + 16;
@@ -1877,6 +1901,8 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   pp.df_base = S.df_base.as<uint32_t>();
   pp.df_fold_end = dbp.fold_end;
   pp.df_from_rows = dbp.from_rows ? 1u : 0u;
+  pp.fuse = fused ? ix->inv_fuse.as<uint32_t>() : nullptr;
+  pp.fuse_tickets = fused ? fuse_tickets(sp, N - (uint64_t)first_block * kBlockDocs) : 0u;
   HIP_TRY(hipEventRecord(ix->ev[EV_D0], s));
   if (S.term_major) {
     TermParams tp{};
@@ -1937,14 +1963,16 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
     HIP_TRY(hipEventRecord(ix->ev[EV_SCAT], s));
   } else {
     if (inv.remap) HIP_TRY(launch_blk_remap(pp, blk_old, df_old, S.crank_inv.as<uint2>(), S.NC_inv, s));
-    if (S.n_blocks) {
+    if (fused) {
+      HIP_TRY(launch_df_fused(pp, s));                    // the lone block: counts, df, offsets and its base
+    } else if (S.n_blocks) {
       HIP_TRY(launch_inv_zero(pp, s));                    // (sliced / split shapes only)
       HIP_TRY(launch_df_partial(pp, s));                  // blocks [first_block, n_blocks)
     } else {
       HIP_TRY(hipMemsetAsync(S.blk.p, 0, (size_t)S.NC * 4, s));
     }
     HIP_TRY(hipEventRecord(ix->ev[EV_DF], s));
-    HIP_TRY(launch_df_sum(pp, s));
+    if (!fused) HIP_TRY(launch_df_sum(pp, s));
     if (dict_delta || df_delta) {
       // sdf still holds the df of this snapshot's last build, crank_inv its occupancy: the slots that
       // differ are listed while sdf is rewritten (counts: ctr[14] df, ctr[15] dictionary)
@@ -1967,9 +1995,9 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
                               S.sdf.as<uint32_t>(), s));
     }
     if (side_work) HIP_TRY(hipEventRecord(ix->mir_ev[2], s));   // df final: its host mirror copies beside the scatter
-    if (S.n_blocks) HIP_TRY(launch_row_scan(pp, s));
+    if (S.n_blocks && !fused) HIP_TRY(launch_row_scan(pp, s));
     HIP_TRY(hipEventRecord(ix->ev[EV_BSCAN], s));
-    HIP_TRY(launch_block_base(pp, s));
+    if (!fused) HIP_TRY(launch_block_base(pp, s));
     HIP_TRY(hipEventRecord(ix->ev[EV_CSCAN], s));
     if (S.n_blocks) HIP_TRY(launch_scatter(pp, s));
     HIP_TRY(hipEventRecord(ix->ev[EV_SCAT], s));
@@ -2036,8 +2064,9 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
       HIP_TRY(launch_count_nonzero(S.dict.as<uint64_t>(), C, reinterpret_cast<unsigned long long *>(ctr + 7), s));
   }
   // ctr[3] error flags .. ctr[7] occupied slots, [8] malformed, [10] posting escapes, [14] / [15] delta list counts
-  uint64_t tail[13];
-  HIP_TRY(hipMemcpyAsync(tail, ctr + 3, sizeof tail, hipMemcpyDeviceToHost, s));
+  // (into pinned memory: a pageable destination makes the copy call itself wait for the stream)
+  uint64_t *tail = hctr + 14;
+  HIP_TRY(hipMemcpyAsync(tail, ctr + 3, 13 * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   if (!S.term_major) {           // the block bases: the next commit's kept postings and escapes are found by them
     HIP_TRY(S.h_bbase.resize((size_t)S.n_blocks + 2));
     HIP_TRY(hipMemcpyAsync(S.h_bbase.data(), S.bbase.p, ((size_t)S.n_blocks + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -2045,6 +2074,7 @@ static int commit_once(tfidf_index *ix, Snapshot &S, bool may_keep) {
   ix->prof.ms_enqueued = prof_ms(ix);
   HIP_TRY(commit_sync(ix, s));
   ix->prof.ms_synced = prof_ms(ix);
+  if (fused) fuse_scratch_done(&ix->fuse_state);      // k_df_fused ran to its end: its finishers left the scratch zero
   {
     // rare (tf >= 2047): sorted for the scorer's binary search.  The kept
     // blocks' entries stand; the new ones were appended behind them.
@@ -2237,6 +2267,13 @@ extern "C" int tfidf_commit_inversion_shape(const tfidf_index *ix, uint32_t *sli
   std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->mu);
   if (slices) *slices = ix->last_inv_slices;
   if (scan_parts) *scan_parts = ix->last_inv_scan_parts;
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_commit_inversion_fused(const tfidf_index *ix, uint32_t *fused) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->mu);
+  if (fused) *fused = ix->last_inv_fused;
   return TFIDF_OK;
 }
 

@@ -247,6 +247,9 @@ struct PostingParams {
   uint32_t *df_base;          // [NC] counts of blocks [0, first_block) per column; k_df_sum adds rows [first_block, df_fold_end)
   uint32_t df_fold_end;       // the blocks that are full now (n_docs / kBlockDocs), >= first_block
   uint32_t df_from_rows;      // A/B: df of the kept blocks from their rows (the base is kept up all the same)
+  // a lone inverted block in one launch (commit_plan.h fuse_plan; k_df_fused alone reads these)
+  uint32_t *fuse;             // [fuse_scratch_words(n_ranges, NC)] tickets, first offsets, block total; counts.  Zero between launches
+  uint32_t fuse_tickets;      // the block's slices that hold documents (fuse_tickets())
 };
 
 // Raise a kernel's dynamic-LDS limit on the current device, once per device:
@@ -305,6 +308,7 @@ hipError_t launch_verify_deferred(const BuildParams &p, hipStream_t s);         
 hipError_t launch_inv_zero(const PostingParams &p, hipStream_t s);
 hipError_t launch_df_partial(const PostingParams &p, hipStream_t s);
 hipError_t launch_df_sum(const PostingParams &p, hipStream_t s);
+hipError_t launch_df_fused(const PostingParams &p, hipStream_t s);   // a lone sliced block: count, df, row scan, block base
 hipError_t launch_row_scan(const PostingParams &p, hipStream_t s);
 hipError_t launch_block_base(const PostingParams &p, hipStream_t s);
 hipError_t launch_count_nonzero(const uint64_t *a, uint32_t n, unsigned long long *out, hipStream_t s);

@@ -249,6 +249,7 @@ SIGNATURES = {
     "tfidf_commit_tokenized_docs": (C.c_int, [VP, U64P, U32P]),
     "tfidf_commit_inverted_blocks": (C.c_int, [VP, U32P, U32P, U32P]),
     "tfidf_commit_inversion_shape": (C.c_int, [VP, U32P, U32P]),
+    "tfidf_commit_inversion_fused": (C.c_int, [VP, U32P]),
     "tfidf_commit_host_profile": (C.c_int, [VP, C.POINTER(HostProfile)]),
     "tfidf_stats": (C.c_int, [VP, C.POINTER(IndexStats)]),
     "tfidf_search": (C.c_int, [VP, C.c_char_p, C.c_uint64, C.c_uint32, U32P, F32P, C.c_uint64, U64P]),

@@ -1015,6 +1015,13 @@ class ShardIndex:
         L.check(L.load().tfidf_commit_inversion_shape(self._h, C.byref(s), C.byref(p)))
         return {"slices": s.value, "scan_parts": p.value}
 
+    def commit_inversion_fused(self):
+        """Whether the last commit took its lone inverted block's counts, df, offsets and base in one
+        launch (tfidf_commit_inversion_fused)."""
+        f = C.c_uint32()
+        L.check(L.load().tfidf_commit_inversion_fused(self._h, C.byref(f)))
+        return bool(f.value)
+
     def commit_host_profile(self):
         """The host side of the last commit (tfidf_commit_host_profile): host times in ms since the call
         began, stream synchronisations, and per mirror (dict, df, crank) its form ("none" / "delta" /
