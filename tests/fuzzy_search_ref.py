@@ -132,6 +132,18 @@ class Shard:
         self.norms = [ix.doc_norm(d) for d in range(self.n)]
         self.doc_count, self.sum_ttf = ix.doc_count, ix.sum_ttf
         ix.close()
+        self._post()
+
+    @classmethod
+    def from_rows(cls, rows, norms, vocab, doc_count, sum_ttf):
+        """The same view from what a caller already read from an oracle of its own."""
+        self = cls.__new__(cls)
+        self.n, self.vocab, self.rows, self.norms = len(rows), vocab, rows, norms
+        self.doc_count, self.sum_ttf = doc_count, sum_ttf
+        self._post()
+        return self
+
+    def _post(self):
         self.postings = {}
         for d, row in enumerate(self.rows):
             for t, tf in row.items():
