@@ -933,9 +933,12 @@ int tfidf_search_batch_keys_device(tfidf_index *ix, const uint8_t *q_utf8, const
 int tfidf_search_all_keys_device(tfidf_index *ix, const uint8_t *q, uint64_t q_len, uint64_t doc_base, void *d_keys,
                                  uint64_t cap, uint64_t *n_out);
 /* Issue the index's device work on the caller's stream (a hipStream_t, e.g.
- * torch.cuda.current_stream().cuda_stream; NULL = the legacy default stream),
- * or back on the index's own stream with TFIDF_OWN_STREAM.  Pending work on
- * the previous stream is finished first. */
+ * torch.cuda.current_stream().cuda_stream), or back on the index's own stream
+ * with TFIDF_OWN_STREAM.  With a caller's stream the writers (commit,
+ * compaction, the GLOBAL exchange) and every search and reader run on it.
+ * NULL is the legacy default stream for the writers only: searches and
+ * readers keep their contexts' own streams, as under TFIDF_OWN_STREAM.
+ * Pending work on the previous stream is finished first. */
 #define TFIDF_OWN_STREAM ((void *)-1)
 int tfidf_set_stream(tfidf_index *ix, void *stream);
 

@@ -95,6 +95,27 @@ def test_create_accepts_legal_edge_parameters(k1, b):
     assert rc in (L.OK, L.E_NO_DEVICE, L.E_HIP), msg
 
 
+def test_stream_and_device_key_entries_reject_a_null_index():
+    """The building blocks of INTEGRATION.md 3c say so before any device call: tfidf_set_stream (with a
+    stream, NULL and TFIDF_OWN_STREAM), the two *_keys_device searches and the query-timing pair."""
+    lib = L.load()
+    offs = np.zeros(2, np.uint64)
+    n = C.c_uint64(7)
+    a, b = C.c_float(), C.c_float()
+    for rc in (lib.tfidf_set_stream(None, None),
+               lib.tfidf_set_stream(None, L.OWN_STREAM),
+               lib.tfidf_set_stream(None, C.c_void_p(0x1000)),
+               lib.tfidf_search_batch_keys_device(None, b"", L.ptr(offs, C.c_uint64), 1, 10, 0, None),
+               lib.tfidf_search_batch_keys_device(None, b"", L.ptr(offs, C.c_uint64), 0, 0, 0, None),
+               lib.tfidf_search_all_keys_device(None, b"q", 1, 0, None, 0, C.byref(n)),
+               lib.tfidf_search_all_keys_device(None, b"q", 1, 0, None, 0, None),
+               lib.tfidf_set_query_timing(None, 0),
+               lib.tfidf_last_search_ms(None, C.byref(a), C.byref(b))):
+        assert rc == L.E_INVALID_ARG
+        assert b"NULL" in lib.tfidf_last_error()
+    assert n.value == 7                                 # a refused call leaves *n_out alone
+
+
 def _raw_key(term):
     """tfidf_common.h key format for terms of <= 16 bytes (exact)."""
     b = term.lower()

@@ -431,7 +431,7 @@ struct tfidf_index {
   std::mutex mu;                     // writers: add_docs, commit, clear, load, the GLOBAL exchange
   hipStream_t stream = nullptr;      // the writers' stream (own_stream unless tfidf_set_stream)
   hipStream_t own_stream = nullptr;
-  hipStream_t user_stream = nullptr; // tfidf_set_stream: searches run on it too
+  hipStream_t user_stream = nullptr; // tfidf_set_stream: searches run on it too (null also for the NULL stream)
   hipEvent_t ev[EV_N];
   // side stream for the dictionary's host mirror: its D2H copy overlaps the inversion
   hipStream_t copy_stream = nullptr;
@@ -1302,6 +1302,19 @@ static void set_last_ms(tfidf_index *ix, float scoring, float total) {
   std::lock_guard<std::mutex> lk(ix->ms_mu);
   ix->last_ms_scoring = scoring;
   ix->last_ms_total = total;
+}
+
+// The same for the routes that report a part they do not time, or a call without device work, as 0:
+// with query timing off both values are -1, as after every other search (tfidf_set_query_timing).
+static void set_route_ms_locked(tfidf_index *ix, float scoring, float total) {
+  const bool timed = ix->q_timing.load();
+  ix->last_ms_scoring = timed ? scoring : -1.0f;
+  ix->last_ms_total = timed ? total : -1.0f;
+}
+
+static void set_route_ms(tfidf_index *ix, float scoring, float total) {
+  std::lock_guard<std::mutex> lk(ix->ms_mu);
+  set_route_ms_locked(ix, scoring, total);
 }
 
 // host time since tfidf_commit began (tfidf_commit_host_profile)
@@ -2782,7 +2795,7 @@ static int search_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *
   PreparedQuery pq;
   int rc = prepare_query(S, V, q, q_len, &pq);
   if (rc) return rc;
-  if (pq.slot.empty() || S.n_docs == 0) { set_last_ms(ix, 0, 0); return TFIDF_OK; }
+  if (pq.slot.empty() || S.n_docs == 0) { set_route_ms(ix, 0, 0); return TFIDF_OK; }
   // fused path for k <= kFusedMaxK: each block workgroup writes its k
   // candidates to pinned host memory over PCIe and the host merges n_blocks x k
   // keys, a cost that grows with k (larger k: run_scoring + the device merge)
@@ -3907,8 +3920,7 @@ static int multiterm_on(tfidf_index *ix, Snapshot &S, const std::vector<std::vec
   auto publish = [&](float ms) {
     std::lock_guard<std::mutex> lk(ix->ms_mu);
     R.publish(ix, n_scan, n_match, n_union, n_tab_bytes);
-    ix->last_ms_scoring = 0.0f;
-    ix->last_ms_total = ms;
+    set_route_ms_locked(ix, 0.0f, ms);
   };
   if (!any || S.n_docs == 0 || S.C == 0) { publish(0.0f); return TFIDF_OK; }
   std::vector<uint64_t> cuts;
@@ -4605,7 +4617,7 @@ extern "C" int tfidf_search_batch(tfidf_index *ix, const uint8_t *q_utf8, const 
     c0 += nc;
   }
   const float ms_total = any ? qev_ms(X, QEV_0, QEV_2) : 0.0f;
-  set_last_ms(ix, any ? qev_ms(X, QEV_0, QEV_1) : 0.0f, ms_total);
+  set_route_ms(ix, any ? qev_ms(X, QEV_0, QEV_1) : 0.0f, ms_total);
   if (knob("TFIDF_HOST_TIMING")) {          // profiling only
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     fprintf(stderr, "batch %u (%u chunks): prepare %.3f  submit %.3f  wait %.3f  copy-out %.3f  total %.3f ms (device %.3f)\n",
@@ -4741,7 +4753,7 @@ static int batch_all_prepared(tfidf_index *ix, Snapshot &S, StatsView &V, Search
   }
   *n_out = total;
   const float ms_all = ms_before + (any ? qev_ms(X, QEV_0, QEV_2) : 0.0f);
-  set_last_ms(ix, any ? qev_ms(X, QEV_0, QEV_1) : 0.0f, ms_all);
+  set_route_ms(ix, any ? qev_ms(X, QEV_0, QEV_1) : 0.0f, ms_all);
   if (ms_total) *ms_total = ms_all;
   if (!fits) return fail(TFIDF_E_BUFFER, "need %llu result slots", (unsigned long long)total);
   return TFIDF_OK;
@@ -4812,7 +4824,7 @@ static int fuzzy_expand_on(tfidf_index *ix, Snapshot &S, const uint8_t *t_utf8, 
   FuzzyExpansions ex;
   if (int rc = fuzzy_on(ix, S, t_utf8, t_offsets, n_terms, max_edits, prefix_len, max_exp, &fl, &ex)) return rc;
   if (ms_device) *ms_device = fl.ms_device;
-  set_last_ms(ix, 0.0f, fl.ms_device);
+  set_route_ms(ix, 0.0f, fl.ms_device);
   DeviceGuard g(ix->cfg.device);                       // slot_term may read a reference occurrence
   std::vector<std::string> strs;
   std::string ts;
@@ -4862,7 +4874,7 @@ static int fuzzy_search_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uin
   FuzzyExpansions ex;
   if (int rc = fuzzy_on(ix, S, t_utf8, t_offsets, n_terms, max_edits, prefix_len, max_exp, &fl, &ex)) return rc;
   if (ms_device) *ms_device = fl.ms_device;
-  set_last_ms(ix, 0.0f, fl.ms_device);
+  set_route_ms(ix, 0.0f, fl.ms_device);
   for (uint32_t i = 0; i < n_terms; i++) n_expanded[i] = (uint32_t)ex[i].size();
   if (n_terms == 0 || S.n_docs == 0) return TFIDF_OK;
   if (int e = V.wait_gdf()) return e;
@@ -5313,7 +5325,7 @@ static int phrase_batch_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uin
   if (X.q_timing) HIP_TRY(hipEventRecord(X.ev[QEV_P1], s));
   HIP_TRY(hipStreamSynchronize(s));
   // tfidf_last_search_ms: the conjunctions' scoring of the last chunk of phrases, the whole call on the device
-  set_last_ms(ix, any ? qev_ms(X, QEV_0, QEV_1) : 0.0f, qev_ms(X, QEV_P0, QEV_P1));
+  set_route_ms(ix, any ? qev_ms(X, QEV_0, QEV_1) : 0.0f, qev_ms(X, QEV_P0, QEV_P1));
   for (uint32_t i = 0; i < n_p; i++) hit_offsets[i + 1] = hit_offsets[i] + cnt[i];
   *n_out = run;
   report();
@@ -5700,7 +5712,7 @@ static int mlt_terms_call(tfidf_index *ix, Snapshot &S, const uint32_t *seeds, u
   if (int rc = mlt_terms_on(ix, S, X, s, seeds, n, R, out)) return rc;
   if (X.q_timing) HIP_TRY(hipEventRecord(X.ev[QEV_P1], s));
   HIP_TRY(hipStreamSynchronize(s));
-  set_last_ms(ix, 0.0f, qev_ms(X, QEV_P0, QEV_P1));
+  set_route_ms(ix, 0.0f, qev_ms(X, QEV_P0, QEV_P1));
   return TFIDF_OK;
 }
 
@@ -5733,7 +5745,7 @@ int tfidf::index_search_term_lists(tfidf_index *ix, const std::vector<std::vecto
       }
   bool any = false;
   if (int rc = score_prepared(ix, S, V, *lease.c, lease.stream(), pqs, k, doc_ids, scores, counts, &any)) return rc;
-  set_last_ms(ix, any ? qev_ms(*lease.c, QEV_0, QEV_1) : 0.0f, any ? qev_ms(*lease.c, QEV_0, QEV_2) : 0.0f);
+  set_route_ms(ix, any ? qev_ms(*lease.c, QEV_0, QEV_1) : 0.0f, any ? qev_ms(*lease.c, QEV_0, QEV_2) : 0.0f);
   return TFIDF_OK;
 }
 
@@ -5811,7 +5823,7 @@ static int mlt_search_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint3
   if (int rc = score_prepared(ix, S, V, X, s, pqs, kk, pd, ps, pc, &any)) return rc;
   if (X.q_timing) HIP_TRY(hipEventRecord(X.ev[QEV_P1], s));
   HIP_TRY(hipStreamSynchronize(s));
-  set_last_ms(ix, any ? qev_ms(X, QEV_0, QEV_2) : 0.0f, qev_ms(X, QEV_P0, QEV_P1));
+  set_route_ms(ix, any ? qev_ms(X, QEV_0, QEV_2) : 0.0f, qev_ms(X, QEV_P0, QEV_P1));
   if (excl)
     for (uint32_t i = 0; i < n; i++) {   // the top k of the others: the seed dropped from the top k + 1
       uint32_t m = 0;
@@ -6224,7 +6236,7 @@ int tfidf::reader_batch_all_keys_device(tfidf_reader *rd, const PreparedAllHits 
     la = lz;
   }
   *n_out = total;
-  set_last_ms(ix, any ? qev_ms(X, QEV_0, QEV_1) : 0.0f, any ? qev_ms(X, QEV_0, QEV_2) : 0.0f);
+  set_route_ms(ix, any ? qev_ms(X, QEV_0, QEV_1) : 0.0f, any ? qev_ms(X, QEV_0, QEV_2) : 0.0f);
   return TFIDF_OK;
 }
 
