@@ -10,8 +10,9 @@ candidate, code points of the term) -- the one rule this restatement chooses
 (Lucene would compute boost 0 or less there).  boost = 1 - ed / m in float32.
 Expansion: the first max_expansions by (boost descending, bytes ascending).
 Weights: boost * idf(largest df of the expansion, docCount) in float32.  Score:
-BM25 per clause in float32 (as test_query_operators.py::py_search), summed in
-double per document, (score descending, doc ascending).  Also the fixture."""
+BM25 per clause in float32 (as test_query_operators.py::py_search; k1 = 1.2 and
+b = 0.75 unless given), summed in double per document, (score descending, doc
+ascending).  Also the fixture."""
 import functools
 import math
 
@@ -150,20 +151,22 @@ class Shard:
                 self.postings.setdefault(t, []).append((d, tf))
 
 
-def norm_cache(doc_count, sum_ttf):
+def norm_cache(doc_count, sum_ttf, k1=1.2, b=0.75):
     avg = F32(sum_ttf / float(doc_count))
     lens = np.array([O.byte4_to_int(i) for i in range(256)], np.float32)
-    k1, b = F32(1.2), F32(0.75)
-    return F32(1) / (k1 * ((F32(1) - b) + b * lens / avg))
+    k1, b = F32(k1), F32(b)
+    with np.errstate(divide="ignore"):          # b = 1: length 0 gives inf, as the oracle's cache has it
+        return F32(1) / (k1 * ((F32(1) - b) + b * lens / avg))
 
 
-def clause_scores(shard, exp, df_of=None, doc_count=None, sum_ttf=None):
+def clause_scores(shard, exp, df_of=None, doc_count=None, sum_ttf=None, k1=1.2, b=0.75):
     """{doc: [float32 clause scores in selection order]} of an expansion on a
-    shard; df_of / doc_count / sum_ttf: the statistics in force (default: the shard's own)."""
+    shard; df_of / doc_count / sum_ttf: the statistics in force (default: the shard's own); k1 / b: the
+    index's BM25 parameters."""
     dc = shard.doc_count if doc_count is None else doc_count
     if dc == 0 or not exp:
         return {}
-    cache = norm_cache(dc, shard.sum_ttf if sum_ttf is None else sum_ttf)
+    cache = norm_cache(dc, shard.sum_ttf if sum_ttf is None else sum_ttf, k1, b)
     max_df = max((df_of[t] if df_of is not None else shard.vocab[t]) for t, _, _, _ in exp)
     idf = F32(np.log(1.0 + (dc - max_df + 0.5) / (max_df + 0.5)))
     per_doc = {}

@@ -1,5 +1,6 @@
 """Every query route on one corpus (helper of test_routes_fixture_cpu.py,
-test_gpu_routes_incremental.py and test_gpu_node_routes_incremental.py).
+test_gpu_routes_incremental.py, test_gpu_node_routes_incremental.py and
+test_gpu_routes_layouts.py).
 
 The corpus is the 25 200 documents of test_gpu_incremental_inversion (3-6 words
 over 400 words, 8 192 documents per block) with a few ROUTE DOCUMENTS put at
@@ -28,6 +29,10 @@ rest.  sweep(h, exp) asserts every route of a ShardIndex or a Reader equal to
 them (float32 scores by their bits) and the *_arrays forms equal, byte for byte,
 to those of a fresh one-commit index of the same documents.  Route documents
 are found by their text, so a list from which documents were deleted works too.
+expected(texts, k1, b, extra_route) takes the index's BM25 parameters and more
+documents to treat as route documents and more-like-this seeds (HEAVY_A and
+HEAVY_B of test_gpu_routes_layouts.py); the fresh index is a default-layout one
+with the same k1 and b.
 """
 import numpy as np
 
@@ -129,6 +134,17 @@ def new_batch():
     return out
 
 
+# Two heavy route documents (test_gpu_routes_layouts.py; test_routes_fixture_cpu.py holds them to these numbers).
+# HEAVY_A: over the tokenizer's 4096-byte window (the long-document path), tf 600: past the scatter temp's and a
+# 9-bit CSR field's escape value (511), below the block-major posting's (2047).  HEAVY_B: over two 16 384-byte
+# highlight items, tf 2100: past the posting's escape too; LONG_TERM's first bytes are written by the long path,
+# "mqalpha mqfill mqbeta" matches 2100 times, and the sloppy frequencies are float32 sums over 2099 and more matches.
+HEAVY_A = (M1 + b" " + M2 + b" ") * 600 + SEEDS[0]
+HEAVY_B = LONG_TERM + b" " + (M1 + b" " + MX + b" " + M2 + b" ") * 2100 + FUZ[0]
+HEAVY = BASE[:FIRST_A] + [HEAVY_A, HEAVY_B]
+BM25 = [(2.0, 1.0), (1.2, 0.0)]                          # (k1, b) beside the default; b = 0: scores without a length
+
+
 # ---------------------------------------------------------------------------
 # the probes
 
@@ -136,7 +152,8 @@ QUERIES = ([M1, M2, M3, MX, M1 + b" " + M2, LONG_TERM, N1, NEW_WORDS[0], NEW_WOR
             FUZ[0], FUZ[1], FUZ[4], CAFE_ACUTE, CAFE + b" " + W.HAN, PIV_A, PIV_B + b" " + c(10), b"seen here"] +
            MULTI + [c(i) for i in (1, 7, 55, 120, 200, 300, 399, 400)])
 PHRASES = [M1 + b" " + M2, M2 + b" " + M1, b" ".join([M1, M2, M3]), P_GAP, M1 + b" " + M3, LONG_TERM + b" first",
-           b"here " + LONG_TERM, CAFE_ACUTE + b" " + CAFE, M1]
+           b"here " + LONG_TERM, CAFE_ACUTE + b" " + CAFE, M1,
+           MX + b" " + M1]                               # slop 1 in HEAVY_B: 2099 matches of length 1, 1049.5
 SLOPS = (0, 1, 2)
 OLD_AND_NEW = b"a?m*"                                    # aama .. aamz of the 400 words, abml .. abmz of the new ones
 WILDCARDS = [b"*", b"zorbl*", OLD_AND_NEW, LONG_TERM[:12] + b"*", "caf?".encode(), b"mq*", b"z?rb*t", b"pivot*"]
@@ -165,17 +182,20 @@ def hit_bits(hits):
 # the references of one document list
 
 class Expected:
-    def __init__(self, texts):
+    def __init__(self, texts, k1=1.2, b=0.75, extra_route=()):
         self.texts = texts = list(texts)
+        self.k1, self.b = k1, b
         n = len(texts)
-        self.route_ids = [i for i, t in enumerate(texts) if t in ROUTE]
-        self.seeds = [i for i, t in enumerate(texts) if t in SEEDS] + [texts.index(TEXTS[PLAIN])]
-        self.mlt = M.MltRef(texts)
+        extra = [i for i, t in enumerate(texts) if t in extra_route]
+        assert len(extra) == len(set(extra_route))
+        self.route_ids = sorted([i for i, t in enumerate(texts) if t in ROUTE] + extra)
+        self.seeds = [i for i, t in enumerate(texts) if t in SEEDS] + [texts.index(TEXTS[PLAIN])] + extra
+        self.mlt = M.MltRef(texts, k1, b)
         self.o = self.mlt.o
         self.vocab = self.o.vocab()
         self.term_sets = [set(r) for r in self.mlt.rows]
         self.shard = R.Shard.from_rows(self.mlt.rows, self.mlt.norm, self.vocab, self.o.doc_count, self.o.sum_ttf)
-        self.phrase = P.PhraseRef(texts)
+        self.phrase = P.PhraseRef(texts, k1, b)
         assert self.o.num_docs == n and not self.phrase.bad
         w = self.want = {}
         for q in QUERIES:
@@ -199,7 +219,7 @@ class Expected:
                     w["fuzzy_terms", t, e, p, m] = F.expected(self.vocab, t, e, p, m)
                 exp, within = R.expansion(self.vocab, t, e, p, EXPANSIONS)
                 w["fuzzy_expand", t, e, p] = ([(a, b, d, float(x)) for a, b, d, x in exp], within)
-                per_doc = R.clause_scores(self.shard, exp)
+                per_doc = R.clause_scores(self.shard, exp, k1=k1, b=b)
                 assert R.sums_are_order_independent(per_doc)         # so the scorer's clause order cannot show
                 w["fuzzy_hits", t, e, p] = (R.bits(R.hits(per_doc)), len(exp))
         for i, params in enumerate(MLT_PARAMS):
@@ -218,7 +238,7 @@ class Expected:
     def fresh_arrays(self):
         """arrays() of a fresh index that took the documents in one commit (built once, closed again)."""
         if self._fresh is None:
-            f = ShardIndex()
+            f = ShardIndex(k1=self.k1, b=self.b)
             try:
                 f.add_documents(self.texts, [k for k, _ in keyed(self.texts)])
                 f.commit()
@@ -235,10 +255,10 @@ class Expected:
 _expected = {}
 
 
-def expected(texts):
-    key = (len(texts), hash(tuple(texts)))
+def expected(texts, k1=1.2, b=0.75, extra_route=()):
+    key = (len(texts), hash(tuple(texts)), k1, b, tuple(extra_route))
     if key not in _expected:
-        _expected[key] = Expected(texts)
+        _expected[key] = Expected(texts, k1, b, extra_route)
     return _expected[key]
 
 

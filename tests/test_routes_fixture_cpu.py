@@ -3,10 +3,20 @@ against the references alone: what keeps the sweeps of
 test_gpu_routes_incremental.py from passing vacuously.  The states are the
 document lists those tests commit: 8300 documents and 200 more (shape A: block
 0 is kept), the same with 50 new words in the 200, and 16 500 documents grown
-to 3 * 8192 + 1 (shape B: blocks 0 and 1 are kept)."""
+to 3 * 8192 + 1 (shape B: blocks 0 and 1 are kept).  For
+test_gpu_routes_layouts.py: the two heavy documents against the thresholds of
+the sources, and the references under the other BM25 parameters."""
 import functools
+import os
+import re
+
+import numpy as np
+import pytest
 
 import fuzzy_ref as F
+import fuzzy_search_ref as R
+import phrase_ref as P
+import phrase_slop_ref as S
 import routes_ref as RR
 from routes_ref import BASE, BLOCK, END_B, FIRST_A, FIRST_B, APPEND_A
 
@@ -127,3 +137,98 @@ def test_every_probes_answer_differs_between_two_states():
         del probes[probe]
     same = [p for p, differs in probes.items() if not any(differs)]
     assert not same, same
+
+
+# ---------------------------------------------------------------------------
+# the heavy documents and the BM25 parameters of test_gpu_routes_layouts.py
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tf-idf-distributed-system_amd", "csrc")
+
+
+@functools.lru_cache(maxsize=None)
+def _sources():
+    return "".join(open(os.path.join(CSRC, f)).read() for f in ("tfidf_internal.h", "snippet_plan.h", "kernels_index.hip"))
+
+
+def const(name):
+    """A constexpr integer of the sources: a literal, or + - << ( ) over literals and other such constants."""
+    m = re.search(r"constexpr\s+\w+\s+%s\s*=\s*([^;]+);" % name, _sources())
+    assert m, name
+    expr = re.sub(r"\b(\d+)u?(?:ll)?\b", r"\1", m.group(1))
+    expr = re.sub(r"\bk[A-Z]\w*", lambda k: str(const(k.group(0))), expr)
+    assert re.fullmatch(r"[\d\s()+\-<]+", expr), (name, expr)
+    return int(eval(expr))                                                     # digits, blanks and ( ) + - << only
+
+
+def f32(bits):
+    return float(np.uint32(bits).view(np.float32))
+
+
+def test_the_heavy_documents_cross_every_threshold():
+    tmp_esc, post_esc, chunk, window = const("kTmpTfEsc"), const("kPostTfEsc"), const("kHlChunkBytes"), const("kWaveWindow")
+    assert (tmp_esc, post_esc, chunk, window) == (511, 2047, 16384, 4096)      # what routes_ref.py's comment says
+    x = RR.expected(RR.HEAVY, extra_route=[RR.HEAVY_A, RR.HEAVY_B])            # builds: order-free fuzzy sums too
+    assert not x.phrase.bad
+    a, b = len(RR.HEAVY) - 2, len(RR.HEAVY) - 1
+    assert (x.texts[a], x.texts[b]) == (RR.HEAVY_A, RR.HEAVY_B) and RR.HEAVY[:FIRST_A] == BASE[:FIRST_A]
+    assert x.route_ids[-2:] == [a, b] and x.seeds[-2:] == [a, b]
+    # HEAVY_A: the long-document tokenizer path; a tf the scatter temp word and a 9-bit CSR field escape and a
+    # block-major posting holds
+    assert len(RR.HEAVY_A) > window and RR.HEAVY_A.endswith(RR.SEEDS[0])
+    assert tmp_esc <= x.mlt.rows[a][RR.M1] == x.mlt.rows[a][RR.M2] == 600 < post_esc
+    # HEAVY_B: three highlight items or more; a tf the posting escapes too; LONG_TERM in the first bytes
+    assert len(RR.HEAVY_B) > 2 * chunk and RR.HEAVY_B.startswith(RR.LONG_TERM + b" ") and RR.HEAVY_B.endswith(b" " + RR.FUZ[0])
+    for t in (RR.M1, RR.MX, RR.M2):
+        assert x.mlt.rows[b][t] == 2100 > post_esc
+    assert x.mlt.rows[b][RR.LONG_TERM] == x.mlt.rows[b][RR.FUZ[0]] == 1
+    w = x.want
+    m12 = RR.M1 + b" " + RR.M2
+    assert {d: f for d, _, f in w["phrase", m12]}[a] == 600 and f32({d: f for d, _, f in w["slop", m12, 0]}[a]) == 600.0
+    assert {d: f for d, _, f in w["phrase", RR.P_GAP]}[b] == 2100
+    assert [f32({d: f for d, _, f in w["slop", RR.P_GAP, s]}[b]) for s in RR.SLOPS] == [2100.0] * 3
+    # sloppy frequencies that no integer holds, summed over the matches of one heavy document
+    for s in (1, 2):
+        heavy = [(p, d, f32(f)) for p in RR.PHRASES for d, _, f in w["slop", p, s] if d in (a, b)]
+        assert any(v > 1000 and v != int(v) for _, _, v in heavy), (s, heavy)
+    for p in RR.PHRASES:                                                       # no repeated term, none over 64 terms
+        for s in RR.SLOPS:
+            assert S.supported(P.terms_of(p), s), (p, s)
+    # the text routes see both documents: each of the first four text queries matches in one of them, the first
+    # one 2100 times in HEAVY_B
+    for q in RR.TEXT_QUERIES[:4]:
+        ms = dict(zip(x.route_ids, w["matches", q]))
+        assert ms[a] or ms[b], q
+    assert len(dict(zip(x.route_ids, w["matches", RR.M1]))[b]) == 2100
+    # more like this from either selects mqalpha with its escaped tf; fuzzy search scores HEAVY_B's "zorblat"
+    # posting, the scorer both escaped ones
+    for d, tf in ((a, 600), (b, 2100)):
+        assert (RR.M1, tf) in [(t, n) for t, n, _, _ in w["mlt_terms", d, 0][0]] and w["mlt_hits", d, 0]
+    assert b in [d for d, _ in w["fuzzy_hits", RR.FUZ[0], 2, 0][0]]
+    assert {a, b} <= {d for d, _ in w["search", RR.M1, 0]}
+
+
+def test_the_weak_hash_collision():
+    assert len(RR.LONG_TERM) == len(RR.N1) > 16 and RR.LONG_TERM != RR.N1      # two hashed keys of one length
+    assert RR.LONG_TERM in state("c1").vocab and RR.N1 in state("c1").vocab and RR.N1 not in state("a0").vocab
+
+
+@pytest.mark.parametrize("k1,b", RR.BM25)
+def test_other_bm25_parameters(k1, b):
+    """The fuzzy search's clause sums are order-independent under these parameters (a condition on the inputs, which
+    expected() asserts as well); the scores differ from the default ones, and b = 0 makes them length-free."""
+    from test_gpu_bm25_params import SETS
+    assert (k1, b) in SETS.values()
+    x, dflt = RR.expected(BASE[:FIRST_A], k1, b), state("a0")
+    for t in RR.FUZZY:
+        for e, p in RR.FUZZY_PARAMS:
+            exp, _ = R.expansion(x.vocab, t, e, p, RR.EXPANSIONS)
+            assert R.sums_are_order_independent(R.clause_scores(x.shard, exp, k1=k1, b=b)), (t, e, p)
+    w, d = x.want, dflt.want
+    m12 = RR.M1 + b" " + RR.M2
+    for key in (("search", RR.M1, 0), ("phrase", m12), ("slop", m12, 1), ("fuzzy_hits", RR.FUZ[0], 2, 0)):
+        got, base = (w[key][0], d[key][0]) if key[0] == "fuzzy_hits" else (w[key], d[key])
+        assert got and got != base and sorted(h[0] for h in got) == sorted(h[0] for h in base), key
+    assert w["mlt_hits", x.seeds[0], 0] and w["mlt_hits", x.seeds[0], 0] != d["mlt_hits", x.seeds[0], 0]
+    if b == 0.0:                                                               # one term, one tf: one score
+        scores = [{s for _, s in v["search", RR.CAFE_ACUTE, 0]} for v in (w, d)]
+        assert len(scores[0]) == 1 < len(scores[1])
