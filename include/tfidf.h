@@ -846,6 +846,80 @@ int tfidf_reader_search_phrase_slop(tfidf_reader *rd, const uint8_t *p, uint64_t
  * document) rows that were scanned and the row chunks they ran in (test and
  * bench instruments). */
 int tfidf_last_phrase_stats(const tfidf_index *ix, uint64_t *candidates, uint64_t *row_chunks);
+/* ---- compound queries: MUST / SHOULD / MUST_NOT / FILTER over every query kind
+ * (Lucene 9.8 BooleanQuery, flat, restated; DESIGN.md section 2, "Compound
+ * queries") ----
+ * A compound query is an ordered list of 0..64 clauses.  A clause has an occur
+ * (TFIDF_OCCUR_*), a kind (TFIDF_CLAUSE_*), a payload byte string and the kind's
+ * parameters: slop for PHRASE; max_edits, prefix_len and max_expansions for
+ * FUZZY (the other fields are ignored).  A clause's row is exactly what its
+ * kind's all-hits batch call returns for the payload on the same snapshot and
+ * statistics: TEXT tfidf_search_batch_all (the whole grammar; a payload that does
+ * not parse has an empty row), PHRASE tfidf_search_phrase_slop_batch, WILDCARD
+ * and REGEX the document set with every score 1.0f, FUZZY
+ * tfidf_search_fuzzy_batch.  Whatever fails that route's whole call fails this
+ * one with the same code and nothing written (a regex syntax error, an
+ * unsupported automaton, a sloppy phrase that repeats a term, a phrase of more
+ * than 1024 terms, max_edits > 2, max_expansions outside 1..64);
+ * tfidf_last_error names the query and the clause.
+ * With R the MUST and FILTER clauses, N the MUST_NOT clauses and S the SHOULD
+ * clauses, a document matches when it is in every row of R, in no row of N and,
+ * when R is empty, in at least one row of S; a query with neither R nor S has no
+ * hits.  Equal clauses are not de-duplicated.  Score: must = (float) of the
+ * double sum of the MUST clauses' scores, should = (float) of the double sum of
+ * the scores of the SHOULD clauses that hold the document, both in clause order;
+ * must + should in one float addition when both exist, else the one that does,
+ * else 0.0f (FILTER only).  FILTER and MUST_NOT scores never count.  Hits are
+ * ordered by score bits descending, then doc ascending.
+ * Input: the payloads in c_utf8 by c_offsets[n_clauses + 1], clauses[n_clauses],
+ * and q_clause_offsets[n_q + 1] giving each query's clauses (n_clauses =
+ * q_clause_offsets[n_q]).  Output protocol of tfidf_search_batch_all:
+ * hit_offsets[n_q + 1] and *n_out always, the payload when *n_out <= cap, else
+ * TFIDF_E_BUFFER (cap 0 with NULL payload pointers asks for the sizes).
+ * ms_device (may be NULL): the call's device time, also tfidf_last_search_ms's
+ * total.  TFIDF_E_INVALID_ARG with nothing written: an unknown occur or kind,
+ * more than 64 clauses in a query, more than 65 536 queries or 2^20 clauses,
+ * offsets that do not start at 0 or decrease, NULL arguments.  TFIDF_E_STATE
+ * before the first commit.
+ * The clause rows are combined on the device in chunks of whole queries whose
+ * rows total at most 2^22 entries (one query at least); the result does not
+ * depend on the chunking.  Out of scope: nesting, boosts, minimumShouldMatch,
+ * top-k (the call returns all hits). */
+#define TFIDF_OCCUR_SHOULD 0
+#define TFIDF_OCCUR_MUST 1
+#define TFIDF_OCCUR_MUST_NOT 2
+#define TFIDF_OCCUR_FILTER 3
+#define TFIDF_CLAUSE_TEXT 0
+#define TFIDF_CLAUSE_PHRASE 1
+#define TFIDF_CLAUSE_WILDCARD 2
+#define TFIDF_CLAUSE_REGEX 3
+#define TFIDF_CLAUSE_FUZZY 4
+typedef struct tfidf_clause {
+  uint8_t occur, kind, max_edits, max_expansions;
+  uint32_t prefix_len, slop;
+} tfidf_clause;
+int tfidf_search_compound_batch(tfidf_index *ix, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                const tfidf_clause *clauses, const uint64_t *q_clause_offsets, uint32_t n_q,
+                                uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out,
+                                float *ms_device);
+int tfidf_reader_search_compound_batch(tfidf_reader *rd, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                       const tfidf_clause *clauses, const uint64_t *q_clause_offsets, uint32_t n_q,
+                                       uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                                       uint64_t *n_out, float *ms_device);
+/* The batch of one query of n_clauses clauses. */
+int tfidf_search_compound(tfidf_index *ix, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                          const tfidf_clause *clauses, uint32_t n_clauses, uint32_t *doc_ids, float *scores,
+                          uint64_t cap, uint64_t *n_out, float *ms_device);
+int tfidf_reader_search_compound(tfidf_reader *rd, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                 const tfidf_clause *clauses, uint32_t n_clauses, uint32_t *doc_ids, float *scores,
+                                 uint64_t cap, uint64_t *n_out, float *ms_device);
+/* Of the last compound call that ran on this index (any form): the clause-row
+ * entries it combined, the chunks it ran in and the (query, block) pairs of
+ * those chunks (test and bench instruments). */
+int tfidf_last_compound_stats(const tfidf_index *ix, uint64_t *row_entries, uint64_t *chunks, uint64_t *pairs);
+/* The combine pass's own device time within the last compound call, in ms (the
+ * rest of the call's device time is its clause routes'). */
+int tfidf_last_compound_ms(const tfidf_index *ix, float *ms_combine);
 /* ---- more-like-this: documents similar to a seed document (Lucene 9.8
  * MoreLikeThis restated on the index's own forward rows; the reference stores
  * no term vectors and cannot offer it; DESIGN.md section 2, "More like this") ----
@@ -1349,6 +1423,17 @@ int tfidf_node_search_phrase_slop_batch(tfidf_node *n, const uint8_t *p_utf8, co
 int tfidf_node_more_like_this_batch(tfidf_node *n, const uint64_t *seeds, uint32_t n_seeds,
                                     const tfidf_mlt_params *params, uint32_t k, uint32_t flags, uint64_t *doc_ids,
                                     float *scores, uint32_t *counts);
+/* tfidf_search_compound_batch over the node, after tfidf_node_commit, in both
+ * statistics modes: every shard with documents runs the batch at once on its own
+ * device (wildcard, regex and fuzzy clauses expand on the shard's own
+ * vocabulary, as their node routes do), doc_ids become global by the shard's
+ * doc_base, and the host merges each query's ordered lists by (score
+ * descending, global id ascending).  A shard's failure fails the call with that
+ * shard's code. */
+int tfidf_node_search_compound_batch(tfidf_node *n, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                     const tfidf_clause *clauses, const uint64_t *q_clause_offsets, uint32_t n_q,
+                                     uint64_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                                     uint64_t *n_out, float *ms_device);
 typedef struct tfidf_node_stats {
   uint64_t n_shards;
   uint64_t num_docs;      /* all shards */

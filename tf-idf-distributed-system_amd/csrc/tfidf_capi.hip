@@ -27,6 +27,7 @@
 #include "analysis.h"
 #include "commit_plan.h"
 #include "compact_plan.h"
+#include "compound_plan.h"
 #include "fuzzy_plan.h"
 #include "fuzzy_search_plan.h"
 #include "wildcard_plan.h"
@@ -394,6 +395,7 @@ struct SearchCtx {
   DevMem ml_in, ml_c, ml_tmp;               // more-like-this: staged seeds + row extents + counters, candidates, sort scratch
   DevMem wc_bits, wc_cnt, wc_out, wc_len;   // wildcard union: pattern bitmaps, (pattern, block) counts, doc ids, matched rows' lengths
   DevMem rx_tab;                            // regex scan: the staged DFA tables of a scan chunk
+  DevMem cq_in, cq_rows, cq_binned, cq_bins;   // compound queries: a chunk's offsets and occurs, its row entries, the binned entries, bin counts and cursors
   PinnedVec<uint32_t> q_host, q_res, q_cand_h;   // q_cand_h: fused single query's block candidates (host merge)
   std::vector<uint64_t> q_merge;
   std::vector<uint32_t> q_units;            // batch scoring units {q, b0, b1, 0} (run_scoring)
@@ -403,7 +405,7 @@ struct SearchCtx {
       : dev(d), q_in(d), q_out(d), cand(d), cand_n(d), out_doc(d), out_score(d), hits(d), hits_n(d), hits_c(d),
         hits_s(d), hits_P(d), ovf(d), hl_in(d), hl_cnt(d), hl_m(d), hl_s(d), hl_o(d), fz_in(d), fz_hs(d), fz_c(d),
         fz_tmp(d), fz_o(d), ph_in(d), ph_s(d), ph_o(d), ph_tmp(d), ml_in(d), ml_c(d), ml_tmp(d), wc_bits(d),
-        wc_cnt(d), wc_out(d), wc_len(d), rx_tab(d) {}
+        wc_cnt(d), wc_out(d), wc_len(d), rx_tab(d), cq_in(d), cq_rows(d), cq_binned(d), cq_bins(d) {}
   int init() {
     DeviceGuard g(dev);
     if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess ||
@@ -453,6 +455,8 @@ struct tfidf_index {
   uint64_t last_fz_scan_chunks = 0, last_fz_cand_chunks = 0;  // of the last fuzzy term lookup (ms_mu)
   uint64_t last_ph_candidates = 0, last_ph_row_chunks = 0;    // of the last phrase search (ms_mu)
   uint64_t last_mlt_entries = 0, last_mlt_chunks = 0;         // of the last more-like-this call (ms_mu)
+  uint64_t last_cq_entries = 0, last_cq_chunks = 0, last_cq_pairs = 0;   // of the last compound call (ms_mu)
+  float last_cq_ms = 0;                                       // ... and its combine pass's device time
   uint64_t last_wc_scan_chunks = 0, last_wc_matches = 0, last_wc_union_chunks = 0;   // of the last wildcard call (ms_mu)
   uint64_t last_rx_scan_chunks = 0, last_rx_matches = 0, last_rx_union_chunks = 0, last_rx_table_bytes = 0;   // of the last regex call (ms_mu)
 
@@ -5455,6 +5459,380 @@ extern "C" int tfidf_last_phrase_stats(const tfidf_index *ix, uint64_t *candidat
   std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->ms_mu);
   if (candidates) *candidates = ix->last_ph_candidates;
   if (row_chunks) *row_chunks = ix->last_ph_row_chunks;
+  return TFIDF_OK;
+}
+
+// ---------------------------------------------------------------------------
+// compound queries ("Compound queries"; rules in
+// compound_plan.h, device pass in kernels_compound.hip).  The call's clauses
+// are grouped by kind (fuzzy clauses also by their parameters) and each group
+// runs once as a batch through its route on the call's snapshot and view; the
+// rows come back as the routes' host arrays.  Chunks of whole queries are then
+// uploaded clause by clause, combined on the device and ordered by the batched
+// all-hits merge; each chunk's hits go to the caller at the running offset.
+
+namespace {
+struct CqGroup {
+  uint32_t kind = 0, max_edits = 0, prefix_len = 0, max_exp = 0;
+  std::vector<uint32_t> clause;            // the call's clauses of this group, ascending
+  std::vector<uint32_t> docs;              // their rows, one after the other
+  std::vector<float> scores;               // empty: a set row, every score 1.0f
+  std::vector<uint64_t> off{0};            // clause.size() + 1
+};
+struct CqRow {
+  const uint32_t *docs = nullptr;
+  const float *scores = nullptr;
+  uint64_t n = 0;
+};
+}  // namespace
+
+static float route_total_ms(tfidf_index *ix) {
+  std::lock_guard<std::mutex> lk(ix->ms_mu);
+  return ix->last_ms_total > 0.0f ? ix->last_ms_total : 0.0f;
+}
+
+// clauses [a, z) of a group through the group's route, appended to the group's rows; *ms: the route's device time
+static int cq_run_slice(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                        const tfidf_clause *clauses, CqGroup &g, size_t a, size_t z, float *ms) {
+  const uint32_t n = (uint32_t)(z - a);
+  std::string blob;
+  std::vector<uint64_t> off((size_t)n + 1, 0);
+  std::vector<uint32_t> slops(n ? n : 1, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t c = g.clause[a + i];
+    if (c_offsets[c + 1] > c_offsets[c])
+      blob.append(reinterpret_cast<const char *>(c_utf8 + c_offsets[c]), c_offsets[c + 1] - c_offsets[c]);
+    off[i + 1] = blob.size();
+    slops[i] = clauses[c].slop;
+  }
+  const uint8_t *text = reinterpret_cast<const uint8_t *>(blob.data());
+  const uint64_t base = g.docs.size();
+  if (g.kind == TFIDF_CLAUSE_WILDCARD || g.kind == TFIDF_CLAUSE_REGEX) {
+    std::vector<std::vector<uint32_t>> tabs;
+    if (g.kind == TFIDF_CLAUSE_REGEX)
+      if (int rc = regex_compile_all(text, off.data(), n, &tabs)) return rc;
+    WildcardLists wl;
+    if (int rc = g.kind == TFIDF_CLAUSE_REGEX ? multiterm_on(ix, S, tabs, n, kRegexRoute, true, 0, &wl)
+                                              : wildcard_on(ix, S, text, off.data(), n, true, 0, &wl))
+      return rc;
+    *ms += wl.ms_device > 0.0f ? wl.ms_device : 0.0f;
+    g.docs.insert(g.docs.end(), wl.docs.begin(), wl.docs.end());
+    for (uint32_t i = 0; i < n; i++) g.off.push_back(base + wl.hit_off[i + 1]);
+    return TFIDF_OK;
+  }
+  // the scored routes: once with a guessed payload size, once more with the size the route reports
+  std::vector<uint64_t> hoff((size_t)n + 1, 0);
+  std::vector<uint32_t> n_exp(n ? n : 1, 0), freqs;
+  uint64_t total = 0, guess = std::min<uint64_t>(256ull * n + 4096, 1ull << 24);
+  int rc = TFIDF_OK;
+  for (int attempt = 0; attempt < 2; attempt++) {
+    g.docs.resize(base + guess);
+    g.scores.resize(base + guess);
+    uint32_t *d = g.docs.data() + base;
+    float *sc = g.scores.data() + base;
+    if (g.kind == TFIDF_CLAUSE_TEXT) {
+      rc = batch_all_on(ix, S, V, text, off.data(), n, d, sc, guess, hoff.data(), &total);
+    } else if (g.kind == TFIDF_CLAUSE_PHRASE) {
+      freqs.resize(guess ? guess : 1);
+      rc = phrase_batch_on(ix, S, V, text, off.data(), slops.data(), n, d, sc, freqs.data(), guess, hoff.data(), &total);
+    } else {
+      rc = fuzzy_search_on(ix, S, V, text, off.data(), n, g.max_edits, g.prefix_len, g.max_exp, d, sc, guess,
+                           hoff.data(), n_exp.data(), &total, nullptr);
+    }
+    *ms += route_total_ms(ix);
+    if (rc != TFIDF_E_BUFFER) break;
+    guess = total;
+  }
+  if (rc) {
+    g.docs.resize(base);
+    g.scores.resize(base);
+    return rc;
+  }
+  g.docs.resize(base + total);
+  g.scores.resize(base + total);
+  for (uint32_t i = 0; i < n; i++) g.off.push_back(base + hoff[i + 1]);
+  return TFIDF_OK;
+}
+
+static int compound_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                       const tfidf_clause *clauses, const uint64_t *q_coff, uint32_t n_q, uint32_t *doc_ids,
+                       float *scores, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out, float *ms_device) {
+  const uint64_t n_c = n_q ? q_coff[n_q] : 0;
+  // the groups: one per kind, the fuzzy clauses one per (max_edits, prefix_len, max_expansions)
+  std::vector<std::unique_ptr<CqGroup>> groups;
+  for (uint64_t c = 0; c < n_c; c++) {
+    const tfidf_clause &cl = clauses[c];
+    const bool fz = cl.kind == TFIDF_CLAUSE_FUZZY;
+    CqGroup *g = nullptr;
+    for (auto &x : groups)
+      if (x->kind == cl.kind &&
+          (!fz || (x->max_edits == cl.max_edits && x->prefix_len == cl.prefix_len && x->max_exp == cl.max_expansions)))
+        g = x.get();
+    if (!g) {
+      groups.emplace_back(new CqGroup());
+      g = groups.back().get();
+      g->kind = cl.kind;
+      if (fz) { g->max_edits = cl.max_edits; g->prefix_len = cl.prefix_len; g->max_exp = cl.max_expansions; }
+    }
+    g->clause.push_back((uint32_t)c);
+  }
+  auto query_of = [&](uint32_t c) {
+    return (uint32_t)(std::upper_bound(q_coff, q_coff + n_q + 1, (uint64_t)c) - q_coff - 1);
+  };
+  float ms_routes = 0.0f;
+  const size_t kSlice = std::min<size_t>(kWcMaxPatterns, kFzMaxTerms);
+  for (auto &gp : groups) {
+    CqGroup &g = *gp;
+    for (size_t a = 0; a < g.clause.size(); a += kSlice) {
+      const size_t z = std::min(g.clause.size(), a + kSlice);
+      const int rc = cq_run_slice(ix, S, V, c_utf8, c_offsets, clauses, g, a, z, &ms_routes);
+      if (rc == TFIDF_OK) continue;
+      // the route failed the whole slice: find the first clause it fails alone, and name it
+      const std::string why = g_err;
+      for (size_t i = a; i < z; i++) {
+        CqGroup one;
+        one.kind = g.kind;
+        one.max_edits = g.max_edits;
+        one.prefix_len = g.prefix_len;
+        one.max_exp = g.max_exp;
+        one.clause.push_back(g.clause[i]);
+        float ms1 = 0.0f;
+        if (cq_run_slice(ix, S, V, c_utf8, c_offsets, clauses, one, 0, 1, &ms1) == rc) {
+          const uint32_t q = query_of(g.clause[i]);
+          const std::string w1 = g_err;
+          return fail(rc, "query %u clause %u: %s", q, (uint32_t)(g.clause[i] - q_coff[q]), w1.c_str());
+        }
+      }
+      return fail(rc, "a clause of kind %u: %s", g.kind, why.c_str());
+    }
+  }
+  std::vector<CqRow> rows(n_c);
+  for (auto &gp : groups)
+    for (size_t i = 0; i < gp->clause.size(); i++) {
+      CqRow &r = rows[gp->clause[i]];
+      r.n = gp->off[i + 1] - gp->off[i];
+      r.docs = gp->docs.data() + gp->off[i];
+      r.scores = gp->scores.empty() ? nullptr : gp->scores.data() + gp->off[i];
+    }
+
+  for (uint32_t i = 0; i <= n_q; i++) hit_offsets[i] = 0;
+  *n_out = 0;
+  if (ms_device) *ms_device = 0.0f;
+  uint64_t st_entries = 0, st_chunks = 0, st_pairs = 0;
+  float ms_combine = 0.0f;
+  auto report = [&]() {
+    std::lock_guard<std::mutex> lk(ix->ms_mu);
+    ix->last_cq_entries = st_entries;
+    ix->last_cq_chunks = st_chunks;
+    ix->last_cq_pairs = st_pairs;
+    ix->last_cq_ms = ms_combine;
+    set_route_ms_locked(ix, ms_combine, ms_routes + ms_combine);
+  };
+  if (n_q == 0 || S.n_docs == 0) {
+    report();
+    return TFIDF_OK;
+  }
+
+  const uint32_t R = S.n_blocks, R2 = hits_runs_per_query(R);
+  std::vector<uint64_t> q_entries(n_q, 0), row_n(n_c, 0);
+  for (uint64_t c = 0; c < n_c; c++) row_n[c] = rows[c].n;
+  for (uint32_t q = 0; q < n_q; q++)
+    for (uint64_t c = q_coff[q]; c < q_coff[q + 1]; c++) q_entries[q] += rows[c].n;
+  uint64_t budget = kCqEntryBudget;
+  if (const char *e = knob("TFIDF_COMPOUND_CHUNK")) budget = (uint64_t)std::max<long long>(1, atoll(e));
+  // the gapped runs of a chunk stay in the all-hits budget, its run and pair indices in 31 bits, its bins in 2^22
+  const uint64_t max_q = std::max<uint64_t>(
+      1, std::min<uint64_t>(kAllHitsBudget / ((uint64_t)R2 * kBlockDocs * 8), (1u << 30) / R2));
+  const uint64_t max_c = std::max<uint64_t>(kCqMaxClausesPerQuery, (1ull << 22) / R);
+  std::vector<uint64_t> cuts;
+  cq_plan_chunks(q_entries.data(), q_coff, n_q, budget, max_q, max_c, &cuts);
+
+  CtxLease lease(ix);
+  if (lease.rc) return lease.rc;
+  SearchCtx &X = *lease.c;
+  const hipStream_t s = lease.stream();
+  DeviceGuard dg(ix->cfg.device);
+  std::vector<uint2> h_rows;
+  std::vector<uint64_t> h_coff, qoff_h;
+  std::vector<uint32_t> h_occ, h_qc;
+  uint64_t total = 0;
+  bool fits = true;
+  for (size_t k = 0; k + 1 < cuts.size(); k++) {
+    const uint32_t a = (uint32_t)cuts[k], z = (uint32_t)cuts[k + 1], nq = z - a;
+    const uint64_t c_lo = q_coff[a], c_hi = q_coff[z];
+    const uint32_t nc = (uint32_t)(c_hi - c_lo);
+    uint64_t n_e = 0, bound = 0;
+    for (uint32_t q = a; q < z; q++) {
+      n_e += q_entries[q];
+      bound += cq_hit_bound(clauses + q_coff[q], row_n.data() + q_coff[q], q_coff[q + 1] - q_coff[q], S.n_docs);
+    }
+    st_chunks++;
+    st_entries += n_e;
+    st_pairs += (uint64_t)nq * R;
+    if (n_e == 0 || bound == 0) {                      // no hit in the chunk
+      for (uint32_t i = 1; i <= nq; i++) hit_offsets[a + i] = total;
+      continue;
+    }
+    h_rows.resize(n_e);
+    h_coff.assign((size_t)nc + 1, 0);
+    h_occ.resize(nc);
+    h_qc.resize((size_t)nq + 1);
+    uint64_t at = 0;
+    for (uint32_t c = 0; c < nc; c++) {
+      const CqRow &r = rows[c_lo + c];
+      for (uint64_t i = 0; i < r.n; i++)
+        h_rows[at++] = make_uint2(r.docs[i], r.scores ? cq_float_bits(r.scores[i]) : 0x3F800000u);
+      h_coff[c + 1] = at;
+      h_occ[c] = clauses[c_lo + c].occur;
+    }
+    for (uint32_t i = 0; i <= nq; i++) h_qc[i] = (uint32_t)(q_coff[a + i] - c_lo);
+    const uint64_t n_bins = (uint64_t)nc * R;
+    const size_t runs = (size_t)nq * R2;
+    const size_t in_coff = 0, in_occ = ((size_t)nc + 1) * 8, in_qc = in_occ + (((size_t)nc * 4 + 7) & ~(size_t)7),
+                 in_bytes = in_qc + ((size_t)nq + 1) * 4;
+    HIP_TRY(X.cq_in.reserve(in_bytes));
+    HIP_TRY(X.cq_rows.reserve(n_e * 8));
+    HIP_TRY(X.cq_binned.reserve(n_e * 8));
+    HIP_TRY(X.cq_bins.reserve(2 * (n_bins + 1) * 8));
+    HIP_TRY(X.hits.reserve(runs * kBlockDocs * 8));
+    HIP_TRY(X.hits_n.reserve(runs * 4));
+    HIP_TRY(X.hits_c.reserve(bound * 8 + 8));
+    HIP_TRY(X.hits_s.reserve(bound * 8 + 8));
+    HIP_TRY(X.hits_P.reserve((runs + 1 + nq + 1) * 8));
+    HIP_TRY(X.out_doc.reserve(bound * 4 + 4));
+    HIP_TRY(X.out_score.reserve(bound * 4 + 4));
+    uint8_t *d_in = X.cq_in.as<uint8_t>();
+    HIP_TRY(hipMemcpyAsync(d_in + in_coff, h_coff.data(), ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_in + in_occ, h_occ.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(d_in + in_qc, h_qc.data(), ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(X.cq_rows.p, h_rows.data(), n_e * 8, hipMemcpyHostToDevice, s));
+    CqPass p{};
+    p.rows = X.cq_rows.as<uint2>();
+    p.c_off = reinterpret_cast<const uint64_t *>(d_in + in_coff);
+    p.c_occur = reinterpret_cast<const uint32_t *>(d_in + in_occ);
+    p.q_coff = reinterpret_cast<const uint32_t *>(d_in + in_qc);
+    p.bin_cnt = X.cq_bins.as<uint64_t>();
+    p.bin_off = p.bin_cnt + n_bins + 1;
+    p.binned = X.cq_binned.as<uint2>();
+    p.hits = X.hits.as<uint64_t>();
+    p.hits_n = X.hits_n.as<uint32_t>();
+    p.n_e = n_e;
+    p.n_c = nc;
+    p.n_q = nq;
+    p.n_blocks = R;
+    p.R2 = R2;
+    p.n_docs = (uint32_t)S.n_docs;
+    HIP_TRY(hipEventRecord(X.ev[QEV_P0], s));
+    HIP_TRY(launch_compound_pass(p, ix->num_cus * 8, s));
+    uint64_t *d_qoff = X.hits_P.as<uint64_t>() + runs + 1;
+    HIP_TRY(launch_hits_order_batch(X.hits.as<uint64_t>(), X.hits_n.as<uint32_t>(), nq, R, X.hits_P.as<uint64_t>(),
+                                    X.hits_c.as<uint64_t>(), X.hits_s.as<uint64_t>(), X.out_doc.as<uint32_t>(),
+                                    X.out_score.as<float>(), d_qoff, nullptr, 0, bound, ix->num_cus * 4, s));
+    HIP_TRY(hipEventRecord(X.ev[QEV_P1], s));
+    qoff_h.resize((size_t)nq + 1);
+    HIP_TRY(hipMemcpyAsync(qoff_h.data(), d_qoff, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    float ms = 0.0f;
+    HIP_TRY(hipEventElapsedTime(&ms, X.ev[QEV_P0], X.ev[QEV_P1]));
+    ms_combine += ms;
+    const uint64_t H = qoff_h[nq];
+    for (uint32_t i = 1; i <= nq; i++) hit_offsets[a + i] = total + qoff_h[i];
+    fits = fits && total + H <= cap;
+    if (fits && H) {
+      HIP_TRY(hipMemcpyAsync(doc_ids + total, X.out_doc.p, H * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(scores + total, X.out_score.p, H * 4, hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipStreamSynchronize(s));
+    }
+    total += H;
+  }
+  *n_out = total;
+  if (ms_device) *ms_device = ms_routes + ms_combine;
+  report();
+  if (!fits) return fail(TFIDF_E_BUFFER, "need %llu result slots", (unsigned long long)total);
+  return TFIDF_OK;
+}
+
+static int compound_check(const void *h, const uint8_t *c_utf8, const uint64_t *c_offsets, const tfidf_clause *clauses,
+                          const uint64_t *q_coff, uint32_t n_q, const uint32_t *doc_ids, const float *scores,
+                          uint64_t cap, const uint64_t *hit_offsets, const uint64_t *n_out) {
+  if (!h || !hit_offsets || !n_out || (n_q && !q_coff) || (cap && (!doc_ids || !scores)))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (n_q && n_q <= kCqMaxQueries && q_coff[n_q] && (!clauses || !c_offsets))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  uint64_t at = 0;
+  switch (cq_check_args(c_offsets, clauses, q_coff, n_q, &at)) {
+    case kCqOk:
+      if (n_q && q_coff[n_q] && !c_utf8 && c_offsets[q_coff[n_q]]) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+      return TFIDF_OK;
+    case kCqTooManyQueries: return fail(TFIDF_E_INVALID_ARG, "more than %u queries in one call", kCqMaxQueries);
+    case kCqBadQueryOffsets: return fail(TFIDF_E_INVALID_ARG, "q_clause_offsets do not start at 0 or decrease at query %llu", (unsigned long long)at);
+    case kCqTooManyInQuery: return fail(TFIDF_E_INVALID_ARG, "query %llu has more than %u clauses", (unsigned long long)at, kCqMaxClausesPerQuery);
+    case kCqTooManyClauses: return fail(TFIDF_E_INVALID_ARG, "more than 2^20 clauses in one call");
+    case kCqBadPayloadOffsets: return fail(TFIDF_E_INVALID_ARG, "c_offsets do not start at 0 or decrease at clause %llu", (unsigned long long)at);
+    case kCqBadOccur: return fail(TFIDF_E_INVALID_ARG, "clause %llu: unknown occur", (unsigned long long)at);
+    default: return fail(TFIDF_E_INVALID_ARG, "clause %llu: unknown kind", (unsigned long long)at);
+  }
+}
+
+extern "C" int tfidf_search_compound_batch(tfidf_index *ix, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                           const tfidf_clause *clauses, const uint64_t *q_clause_offsets, uint32_t n_q,
+                                           uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                                           uint64_t *n_out, float *ms_device) {
+  if (int rc = compound_check(ix, c_utf8, c_offsets, clauses, q_clause_offsets, n_q, doc_ids, scores, cap, hit_offsets,
+                              n_out))
+    return rc;
+  std::shared_ptr<StatsView> view;
+  const std::shared_ptr<Snapshot> snap = current(ix, &view);
+  if (!snap) return fail(TFIDF_E_STATE, "compound search before commit");
+  return compound_on(ix, *snap, *view, c_utf8, c_offsets, clauses, q_clause_offsets, n_q, doc_ids, scores, cap,
+                     hit_offsets, n_out, ms_device);
+}
+
+extern "C" int tfidf_reader_search_compound_batch(tfidf_reader *rd, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                                  const tfidf_clause *clauses, const uint64_t *q_clause_offsets,
+                                                  uint32_t n_q, uint32_t *doc_ids, float *scores, uint64_t cap,
+                                                  uint64_t *hit_offsets, uint64_t *n_out, float *ms_device) {
+  if (int rc = compound_check(rd, c_utf8, c_offsets, clauses, q_clause_offsets, n_q, doc_ids, scores, cap, hit_offsets,
+                              n_out))
+    return rc;
+  return compound_on(rd->ix, *rd->S, *rd->V, c_utf8, c_offsets, clauses, q_clause_offsets, n_q, doc_ids, scores, cap,
+                     hit_offsets, n_out, ms_device);
+}
+
+// the single forms: the batch of one query
+extern "C" int tfidf_search_compound(tfidf_index *ix, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                     const tfidf_clause *clauses, uint32_t n_clauses, uint32_t *doc_ids, float *scores,
+                                     uint64_t cap, uint64_t *n_out, float *ms_device) {
+  if (!n_out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t qo[2] = {0, n_clauses};
+  uint64_t ho[2];
+  return tfidf_search_compound_batch(ix, c_utf8, c_offsets, clauses, qo, 1, doc_ids, scores, cap, ho, n_out, ms_device);
+}
+
+extern "C" int tfidf_reader_search_compound(tfidf_reader *rd, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                            const tfidf_clause *clauses, uint32_t n_clauses, uint32_t *doc_ids,
+                                            float *scores, uint64_t cap, uint64_t *n_out, float *ms_device) {
+  if (!n_out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t qo[2] = {0, n_clauses};
+  uint64_t ho[2];
+  return tfidf_reader_search_compound_batch(rd, c_utf8, c_offsets, clauses, qo, 1, doc_ids, scores, cap, ho, n_out,
+                                            ms_device);
+}
+
+extern "C" int tfidf_last_compound_stats(const tfidf_index *ix, uint64_t *row_entries, uint64_t *chunks,
+                                         uint64_t *pairs) {
+  if (!ix) return fail(TFIDF_E_INVALID_ARG, "NULL index");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->ms_mu);
+  if (row_entries) *row_entries = ix->last_cq_entries;
+  if (chunks) *chunks = ix->last_cq_chunks;
+  if (pairs) *pairs = ix->last_cq_pairs;
+  return TFIDF_OK;
+}
+
+extern "C" int tfidf_last_compound_ms(const tfidf_index *ix, float *ms_combine) {
+  if (!ix || !ms_combine) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  std::lock_guard<std::mutex> lk(const_cast<tfidf_index *>(ix)->ms_mu);
+  *ms_combine = ix->last_cq_ms;
   return TFIDF_OK;
 }
 

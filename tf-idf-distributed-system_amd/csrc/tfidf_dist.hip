@@ -38,6 +38,7 @@
 
 #include "../../include/tfidf.h"
 #include "analysis.h"
+#include "compound_plan.h"
 #include "mlt_plan.h"
 #include "tfidf_common.h"
 #include "tfidf_internal.h"
@@ -2540,6 +2541,92 @@ extern "C" int tfidf_node_search_phrase_slop_batch(tfidf_node *n, const uint8_t 
                                                    uint64_t *n_out) {
   return node_phrase_batch(n, p_utf8, p_offsets, slops, true, n_p, doc_ids, scores,
                            reinterpret_cast<uint32_t *>(freqs), cap, hit_offsets, n_out);
+}
+
+// ---------------------------------------------------------------------------
+// compound queries over the node: every shard with documents runs the whole
+// batch (tfidf_search_compound_batch: its clause routes on the shard's own
+// vocabulary and the statistics in force); the host merges each query's ordered
+// lists by (score bits descending, global id ascending).
+
+extern "C" int tfidf_node_search_compound_batch(tfidf_node *n, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                                const tfidf_clause *clauses, const uint64_t *q_clause_offsets,
+                                                uint32_t n_q, uint64_t *doc_ids, float *scores, uint64_t cap,
+                                                uint64_t *hit_offsets, uint64_t *n_out, float *ms_device) {
+  if (!n || !hit_offsets || !n_out || (n_q && !q_clause_offsets) || (cap && (!doc_ids || !scores)))
+    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (n_q && n_q <= kCqMaxQueries && q_clause_offsets[n_q] && (!clauses || !c_offsets))
+    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  uint64_t bad = 0;
+  if (const int why = cq_check_args(c_offsets, clauses, q_clause_offsets, n_q, &bad))
+    return errf(TFIDF_E_INVALID_ARG, "compound arguments: rule %d broken at %llu (compound_plan.h)", why,
+                (unsigned long long)bad);
+  std::lock_guard<std::mutex> lk(n->mu);
+  if (!n->committed) return errf(TFIDF_E_STATE, "compound search before tfidf_node_commit");
+  struct ShardHits {
+    std::vector<uint32_t> docs;
+    std::vector<float> scores;
+    std::vector<uint64_t> off;
+    float ms = 0.0f;
+    bool ran = false;
+  };
+  const size_t G = n->shards.size();
+  std::vector<ShardHits> sh(G);
+  // one shard's batch: once with a guessed payload size, once more with the size it reports
+  if (int rc = n->pool->run([&](uint32_t g) {
+        tfidf_index *ix = n->shards[g];
+        ShardHits &b = sh[g];
+        if (!index_committed(ix) || index_num_docs(ix) == 0) return (int)TFIDF_OK;
+        b.off.assign((size_t)n_q + 1, 0);
+        uint64_t total = 0, guess = std::min<uint64_t>(64ull * n_q + 4096, 1ull << 24);
+        int rc = TFIDF_OK;
+        for (int attempt = 0; attempt < 2; attempt++) {
+          b.docs.resize(guess);
+          b.scores.resize(guess);
+          rc = tfidf_search_compound_batch(ix, c_utf8, c_offsets, clauses, q_clause_offsets, n_q, b.docs.data(),
+                                           b.scores.data(), guess, b.off.data(), &total, &b.ms);
+          if (rc != TFIDF_E_BUFFER) break;
+          guess = total;
+        }
+        b.ran = rc == TFIDF_OK;
+        return rc;
+      }))
+    return rc;
+  if (ms_device) {
+    *ms_device = 0.0f;
+    for (size_t g = 0; g < G; g++)
+      if (sh[g].ran) *ms_device = std::max(*ms_device, sh[g].ms);   // the shards run at once: the slowest one's time
+  }
+  uint64_t total = 0;
+  hit_offsets[0] = 0;
+  for (uint32_t i = 0; i < n_q; i++) {
+    for (size_t g = 0; g < G; g++)
+      if (sh[g].ran) total += sh[g].off[i + 1] - sh[g].off[i];
+    hit_offsets[i + 1] = total;
+  }
+  *n_out = total;
+  if (total > cap) return errf(TFIDF_E_BUFFER, "need %llu result slots", (unsigned long long)total);
+  // the shards' lists of a query are ordered, and ascending shard = ascending global id among equal scores
+  auto bits = [](float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    return u;
+  };
+  std::vector<uint64_t> at(G);
+  for (uint32_t i = 0; i < n_q; i++) {
+    for (size_t g = 0; g < G; g++) at[g] = sh[g].ran ? sh[g].off[i] : 0;
+    for (uint64_t o = hit_offsets[i]; o < hit_offsets[i + 1]; o++) {
+      size_t best = G;
+      for (size_t g = 0; g < G; g++) {
+        if (!sh[g].ran || at[g] >= sh[g].off[i + 1]) continue;
+        if (best == G || bits(sh[g].scores[at[g]]) > bits(sh[best].scores[at[best]])) best = g;
+      }
+      const uint64_t j = at[best]++;
+      doc_ids[o] = n->doc_base[best] + sh[best].docs[j];
+      scores[o] = sh[best].scores[j];
+    }
+  }
+  return TFIDF_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -462,6 +462,26 @@ hipError_t launch_hits_order_batch(uint64_t *hits, const uint32_t *hits_n, uint3
                                    uint64_t *q_off, uint64_t *keys_out, uint64_t doc_base, uint64_t hits_bound,
                                    int grid, hipStream_t s);
 
+// --- compound queries (kernels_compound.hip; rules in compound_plan.h) ---
+// One chunk of queries: their clauses' rows flattened clause after clause (rows:
+// (doc, score bits); c_off: n_c + 1), binned by (clause, doc block) and combined
+// per (query, block) into sorted runs in the batched all-hits layout (run
+// q * R2 + b of hits / hits_n; n_q * n_blocks < 2^31).  bin_cnt / bin_off:
+// n_c * n_blocks + 1 u64 each; binned: n_e entries.
+struct CqPass {
+  const uint2 *rows;
+  const uint64_t *c_off;
+  const uint32_t *c_occur;    // per clause of the chunk: TFIDF_OCCUR_*
+  const uint32_t *q_coff;     // [n_q + 1] first clause of each query
+  uint64_t *bin_cnt, *bin_off;
+  uint2 *binned;
+  uint64_t *hits;
+  uint32_t *hits_n;
+  uint64_t n_e;
+  uint32_t n_c, n_q, n_blocks, R2, n_docs;
+};
+hipError_t launch_compound_pass(const CqPass &p, int grid, hipStream_t s);
+
 // --- GLOBAL statistics by term ownership (kernels_vocab.hip) ---
 hipError_t vocab_count(const uint64_t *dict, uint32_t C, uint32_t G, uint32_t *counts, hipStream_t s);
 hipError_t vocab_starts(const uint32_t *counts, uint32_t G, uint32_t *cursor, uint64_t *counts_out, hipStream_t s);

@@ -145,6 +145,26 @@ _MLT_TERMS_SIG = (C.c_int, [VP, U32P, C.c_uint32, MLTP, U64P, U64P, U64P, VP, C.
 _MLT_BATCH_SIG = (C.c_int, [VP, U32P, C.c_uint32, MLTP, C.c_uint32, C.c_uint32, U32P, F32P, U32P])
 _MLT_SINGLE_SIG = (C.c_int, [VP, C.c_uint32, MLTP, C.c_uint32, C.c_uint32, U32P, F32P, U32P])
 
+OCCUR_SHOULD, OCCUR_MUST, OCCUR_MUST_NOT, OCCUR_FILTER = 0, 1, 2, 3                       # TFIDF_OCCUR_*
+CLAUSE_TEXT, CLAUSE_PHRASE, CLAUSE_WILDCARD, CLAUSE_REGEX, CLAUSE_FUZZY = 0, 1, 2, 3, 4   # TFIDF_CLAUSE_*
+
+
+class Clause(C.Structure):
+    """tfidf_clause (12 bytes)."""
+    _fields_ = [("occur", C.c_uint8), ("kind", C.c_uint8), ("max_edits", C.c_uint8), ("max_expansions", C.c_uint8),
+                ("prefix_len", C.c_uint32), ("slop", C.c_uint32)]
+
+
+CLAUSEP = C.POINTER(Clause)
+
+
+def _compound_batch_sig(doc):
+    """tfidf_[reader_|node_]search_compound_batch; doc ids are u32 per shard, u64 over a node."""
+    return (C.c_int, [VP, C.c_char_p, U64P, CLAUSEP, U64P, C.c_uint32, doc, F32P, C.c_uint64, U64P, U64P, F32P])
+
+
+_COMPOUND_SINGLE_SIG = (C.c_int, [VP, C.c_char_p, U64P, CLAUSEP, C.c_uint32, U32P, F32P, C.c_uint64, U64P, F32P])
+
 SIGNATURES = {
     "tfidf_version": (C.c_char_p, []),
     "tfidf_last_error": (C.c_char_p, []),
@@ -235,6 +255,13 @@ SIGNATURES = {
                                                   U64P]),
     "tfidf_node_search_phrase_slop_batch": (C.c_int, [VP, C.c_char_p, U64P, U32P, C.c_uint32, U64P, F32P, F32P,
                                                       C.c_uint64, U64P, U64P]),
+    "tfidf_search_compound_batch": _compound_batch_sig(U32P),
+    "tfidf_reader_search_compound_batch": _compound_batch_sig(U32P),
+    "tfidf_node_search_compound_batch": _compound_batch_sig(U64P),
+    "tfidf_search_compound": _COMPOUND_SINGLE_SIG,
+    "tfidf_reader_search_compound": _COMPOUND_SINGLE_SIG,
+    "tfidf_last_compound_stats": (C.c_int, [VP, U64P, U64P, U64P]),
+    "tfidf_last_compound_ms": (C.c_int, [VP, F32P]),
     "tfidf_mlt_params_init": (C.c_int, [MLTP]),
     "tfidf_mlt_terms_batch": _MLT_TERMS_SIG,
     "tfidf_reader_mlt_terms_batch": _MLT_TERMS_SIG,

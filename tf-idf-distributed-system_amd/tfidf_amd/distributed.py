@@ -545,6 +545,21 @@ class Node:
         return E._phrase_lists(*E._phrase_batch_arrays(L.load().tfidf_node_search_phrase_slop_batch, self._h, phrases,
                                                        dtype=np.uint64, slops=slops))
 
+    def search_compound_batch_arrays(self, queries, cap=None):
+        """(global docs uint64[], scores float32[], hit offsets uint64[n + 1],
+        ms_device) of tfidf_node_search_compound_batch."""
+        from . import engine as E
+        return E._compound_arrays(L.load().tfidf_node_search_compound_batch, self._h, queries, cap, dtype=np.uint64)
+
+    def search_compound_batch(self, queries):
+        """ShardIndex.search_compound_batch over the node: [[(global doc,
+        score)]]; every shard combines the clauses on its own documents
+        (wildcard, regex and fuzzy clauses expand on the shard's vocabulary), and
+        the lists are merged per query by (score desc, global id asc)
+        (tfidf_node_search_compound_batch)."""
+        from . import engine as E
+        return E._compound_lists(self.search_compound_batch_arrays(queries))
+
     def more_like_this_batch(self, docs, k=10, exclude_seed=True, **params):
         """ShardIndex.more_like_this_batch over the node: ``docs`` are global
         ids; the owning shard picks a seed's interesting terms, every shard

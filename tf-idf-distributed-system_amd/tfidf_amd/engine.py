@@ -388,6 +388,99 @@ def _fuzzy_search_single(fn, handle, term, max_edits, prefix_len, max_expansions
     return docs[:total.value], scores[:total.value], n_exp.value
 
 
+# Compound queries: a query is a list of clauses, a clause the tuple (occur, kind,
+# payload, params...) with params = (slop,) for a phrase and (max_edits,
+# prefix_len, max_expansions) for a fuzzy term.  The constructors below build the
+# (kind, payload, params...) part, the occur wrappers put the occur in front:
+# must(phrase(b"a b", slop=1)), should(text(b"gpu")), must_not(fuzzy(b"nvidia", 1)).
+def text(payload: bytes):
+    return (L.CLAUSE_TEXT, bytes(payload))
+
+
+def phrase(payload: bytes, slop=0):
+    return (L.CLAUSE_PHRASE, bytes(payload), int(slop))
+
+
+def wildcard(payload: bytes):
+    return (L.CLAUSE_WILDCARD, bytes(payload))
+
+
+def regex(payload: bytes):
+    return (L.CLAUSE_REGEX, bytes(payload))
+
+
+def fuzzy(payload: bytes, max_edits=2, prefix_len=0, max_expansions=50):
+    return (L.CLAUSE_FUZZY, bytes(payload), int(max_edits), int(prefix_len), int(max_expansions))
+
+
+def should(clause):
+    return (L.OCCUR_SHOULD,) + tuple(clause)
+
+
+def must(clause):
+    return (L.OCCUR_MUST,) + tuple(clause)
+
+
+def must_not(clause):
+    return (L.OCCUR_MUST_NOT,) + tuple(clause)
+
+
+def filter_(clause):
+    return (L.OCCUR_FILTER,) + tuple(clause)
+
+
+def _clause_arrays(queries):
+    """[[clause]] -> (payload blob, uint64 payload offsets, Clause array, uint64 clause offsets per query)."""
+    flat = [c for q in queries for c in q]
+    q_offs = np.zeros(len(queries) + 1, np.uint64)
+    if len(queries):
+        q_offs[1:] = np.cumsum([len(q) for q in queries], dtype=np.uint64)
+    blob, c_offs = _key_arrays([c[2] for c in flat])
+    arr = (L.Clause * max(len(flat), 1))()
+    for i, c in enumerate(flat):
+        occur, kind, params = int(c[0]), int(c[1]), c[3:]
+        if not (0 <= occur <= 255 and 0 <= kind <= 255):
+            raise ValueError("occur and kind are bytes")
+        arr[i].occur, arr[i].kind = occur, kind
+        if kind == L.CLAUSE_PHRASE:
+            arr[i].slop = params[0] if params else 0
+        elif kind == L.CLAUSE_FUZZY:
+            me, pl, mx = (tuple(params) + (2, 0, 50)[len(params):])[:3]
+            arr[i].max_edits, arr[i].prefix_len, arr[i].max_expansions = min(me, 255), pl, min(max(mx, 0), 255)
+    return blob, c_offs, arr, q_offs
+
+
+def _compound_arrays(fn, handle, queries, cap=None, dtype=np.uint32):
+    """tfidf_[reader_|node_]search_compound_batch: one call with ``cap`` hit
+    slots, once more with the size the library reports when that was too small.
+    -> (docs, scores float32[], hit offsets uint64[n_q + 1], ms_device)."""
+    queries = [list(q) for q in queries]
+    blob, c_offs, arr, q_offs = _clause_arrays(queries)
+    nq = len(queries)
+    offs = np.zeros(nq + 1, np.uint64)
+    total, ms = C.c_uint64(), C.c_float()
+    cap = min(4096 * max(nq, 1), 1 << 24) if cap is None else cap
+    for _ in range(2):
+        docs = np.empty(max(cap, 1), dtype)
+        scores = np.empty(max(cap, 1), np.float32)
+        rc = fn(handle, blob, L.ptr(c_offs, C.c_uint64), arr, L.ptr(q_offs, C.c_uint64), nq,
+                L.ptr(docs, np.ctypeslib.as_ctypes_type(dtype)), L.ptr(scores, C.c_float), cap,
+                L.ptr(offs, C.c_uint64), C.byref(total), C.byref(ms))
+        if rc != L.E_BUFFER:
+            break
+        cap = total.value
+    L.check(rc)
+    m = total.value
+    return docs[:m], scores[:m], offs, ms.value
+
+
+def _compound_lists(arrays):
+    """-> per query [(doc, score)]."""
+    docs, scores, offs, _ = arrays
+    d, s, o = docs.tolist(), scores.tolist(), offs.tolist()
+    return [list(zip(d[o[i]:o[i + 1]], s[o[i]:o[i + 1]])) for i in range(len(o) - 1)]
+
+
 def _wildcard_terms_arrays(fn, handle, patterns, max_out, df_dtype=np.uint32):
     """tfidf_[reader_|node_]wildcard_terms_batch, sized as _fuzzy_batch_arrays
     sizes the fuzzy batch.  -> (cand offsets uint64[n + 1], n_matched
@@ -942,6 +1035,31 @@ class ShardIndex:
         L.check(L.load().tfidf_last_phrase_stats(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def search_compound_batch_arrays(self, queries, cap=None):
+        """(docs uint32[], scores float32[], hit offsets uint64[n + 1], ms_device)
+        of tfidf_search_compound_batch.  A query is a list of clauses (occur,
+        kind, payload, params...): see must / should / must_not / filter_ and
+        text / phrase / wildcard / regex / fuzzy of this module."""
+        return _compound_arrays(L.load().tfidf_search_compound_batch, self._h, queries, cap)
+
+    def search_compound_batch(self, queries):
+        """Per query every hit [(doc, score)] of the Boolean combination of its
+        clauses (Lucene's flat BooleanQuery), score descending, doc ascending."""
+        return _compound_lists(self.search_compound_batch_arrays(queries))
+
+    def search_compound(self, clauses):
+        """search_compound_batch([clauses])[0]."""
+        return self.search_compound_batch([clauses])[0]
+
+    def last_compound_stats(self):
+        """(clause-row entries, chunks, (query, block) pairs, combine pass ms) of
+        the last compound call on this index or one of its readers
+        (tfidf_last_compound_stats, tfidf_last_compound_ms)."""
+        a, b, c, ms = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_float()
+        L.check(L.load().tfidf_last_compound_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        L.check(L.load().tfidf_last_compound_ms(self._h, C.byref(ms)))
+        return a.value, b.value, c.value, ms.value
+
     def more_like_this(self, doc, k=10, exclude_seed=True, **params):
         """[(doc, score)]: the top ``k`` of the disjunction of document
         ``doc``'s interesting terms (Lucene's MoreLikeThis on the index's own
@@ -1486,6 +1604,18 @@ class Reader:
     def search_phrase_slop_batch(self, phrases, slops):
         """ShardIndex.search_phrase_slop_batch on this reader's snapshot."""
         return _phrase_lists(*self.search_phrase_slop_batch_arrays(phrases, slops))
+
+    def search_compound_batch_arrays(self, queries, cap=None):
+        """ShardIndex.search_compound_batch_arrays on this reader's snapshot."""
+        return _compound_arrays(L.load().tfidf_reader_search_compound_batch, self._h, queries, cap)
+
+    def search_compound_batch(self, queries):
+        """ShardIndex.search_compound_batch on this reader's snapshot."""
+        return _compound_lists(self.search_compound_batch_arrays(queries))
+
+    def search_compound(self, clauses):
+        """ShardIndex.search_compound on this reader's snapshot."""
+        return self.search_compound_batch([clauses])[0]
 
     def more_like_this(self, doc, k=10, exclude_seed=True, **params):
         """ShardIndex.more_like_this on this reader's snapshot."""

@@ -39,6 +39,86 @@ def document_score_info(name: str, score: float):
     return {"document": {"name": name}, "score": float(score)}
 
 
+_OCCUR_PREFIX = {"+": L.OCCUR_MUST, "-": L.OCCUR_MUST_NOT, "#": L.OCCUR_FILTER}
+
+
+def _syntax(msg):
+    return L.QuerySyntaxError(L.E_QUERY_SYNTAX, msg)
+
+
+def parse_compound_query(text: str):
+    """Worker.search_query's grammar: one query string -> the clause list of
+    ShardIndex.search_compound, on the host.  Clauses are separated by
+    whitespace.  A prefix gives the occur: ``+`` MUST, ``-`` MUST_NOT, ``#``
+    FILTER, none SHOULD.  ``"..."`` with an optional ``~N`` is a phrase with slop
+    N; ``/.../`` is a regular expression (``\\/`` is a slash in it); ``word~`` or
+    ``word~N`` is a fuzzy term with N edits (0..2, default 2), lower-cased; a
+    token with an unescaped ``*`` or ``?`` is a wildcard pattern; anything else
+    is a one-token text clause, handed on as search_index hands its query.  An
+    unclosed quote or slash, a prefix without a clause, text glued to a closing
+    quote or slash, or an edit count above 2 raises QuerySyntaxError."""
+    from . import engine as E
+    out, i, n = [], 0, len(text)
+    while i < n:
+        if text[i].isspace():
+            i += 1
+            continue
+        occur = L.OCCUR_SHOULD
+        if text[i] in _OCCUR_PREFIX:
+            occur = _OCCUR_PREFIX[text[i]]
+            i += 1
+            if i >= n or text[i].isspace():
+                raise _syntax("a '%s' without a clause at %d" % (text[i - 1], i - 1))
+        if text[i] == '"':
+            j = text.find('"', i + 1)
+            if j < 0:
+                raise _syntax("unclosed quote at %d" % i)
+            body, i = text[i + 1:j], j + 1
+            m = re.match(r"~(\d+)", text[i:])
+            slop = 0
+            if m:
+                slop, i = int(m.group(1)), i + m.end()
+            if i < n and not text[i].isspace():
+                raise _syntax("text after the closing quote at %d" % i)
+            clause = E.phrase(body.encode(), min(slop, 0x7FFFFFFF))
+        elif text[i] == "/":
+            j, body = i + 1, []
+            while j < n and text[j] != "/":
+                if text[j] == "\\" and j + 1 < n and text[j + 1] == "/":
+                    body.append("/")
+                    j += 2
+                    continue
+                if text[j] == "\\" and j + 1 < n:          # any other escape stays the pattern's own
+                    body.append(text[j:j + 2])
+                    j += 2
+                    continue
+                body.append(text[j])
+                j += 1
+            if j >= n:
+                raise _syntax("unclosed slash at %d" % i)
+            i = j + 1
+            if i < n and not text[i].isspace():
+                raise _syntax("text after the closing slash at %d" % i)
+            clause = E.regex("".join(body).encode())
+        else:
+            j = i
+            while j < n and not text[j].isspace():
+                j += 1
+            tok, i = text[i:j], j
+            m = re.match(r"^(.+)~(\d*)$", tok, re.S)
+            if m:
+                edits = int(m.group(2)) if m.group(2) else 2
+                if edits > 2:
+                    raise _syntax("fuzzy edits %d above 2 in '%s'" % (edits, tok))
+                clause = E.fuzzy(m.group(1).lower().encode(), edits)
+            elif re.search(r"(?<!\\)(?:\\\\)*[*?]", tok):
+                clause = E.wildcard(tok.encode())
+            else:
+                clause = E.text(tok.encode())
+        out.append((occur,) + clause)
+    return out
+
+
 class Worker:
     """Worker.java:42-242 — one shard: builds its index at init, answers
     /worker/process with every hit of its shard-local BM25 ranking."""
@@ -180,6 +260,17 @@ class Worker:
                 info["freq"] = f
                 out.append(info)
             return out
+
+    # No reference counterpart (QueryParser.escape neutralises every operator):
+    # one query string of mixed clauses (parse_compound_query), combined by
+    # Lucene's flat BooleanQuery rule on the device; the first ``k`` hits (0 =
+    # all) in the order and shape of search_index.  A string that does not
+    # parse raises QuerySyntaxError, as search_index's query does.
+    def search_query(self, text: str, k=10):
+        clauses = parse_compound_query(text)
+        with self.index.reader() as rd:
+            hits = rd.search_compound(clauses)
+            return [document_score_info(rd.doc_key(d).decode(), s) for d, s in (hits[:k] if k else hits)]
 
     # No reference counterpart ("contents" has no term vectors, so Lucene's
     # MoreLikeThis.like(docNum) would find no terms there): the ``k``
