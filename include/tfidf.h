@@ -920,6 +920,68 @@ int tfidf_last_compound_stats(const tfidf_index *ix, uint64_t *row_entries, uint
 /* The combine pass's own device time within the last compound call, in ms (the
  * rest of the call's device time is its clause routes'). */
 int tfidf_last_compound_ms(const tfidf_index *ix, float *ms_combine);
+/* ---- nested compound queries: clause groups and minimumShouldMatch (Lucene 9.8
+ * BooleanQuery as a clause of a BooleanQuery, restated and evaluated as written;
+ * DESIGN.md section 2, "Nested compound queries") ----
+ * A query is a tree of at most 64 nodes given in pre-order.  A leaf is a clause
+ * of the flat call (kind TEXT .. FUZZY, its payload and parameters) and its row
+ * is that clause's row.  A group has kind TFIDF_CLAUSE_GROUP, an empty payload,
+ * the nodes that name it as their parent as its children, in order, and
+ * min_should_match m.  Node 0 is the root, a group whose parent is
+ * TFIDF_QNODE_ROOT; every other node's parent is an earlier group node of the
+ * query and its occur is the one towards that parent.  Groups sit at depths
+ * 0..3 (the root is depth 0), leaves at depths 1..4.  A query of 0 nodes has no
+ * hits.
+ * With R a group's MUST and FILTER children, N its MUST_NOT children and S its
+ * SHOULD children, a document matches the group when every R child holds it, no
+ * N child holds it and at least max(m, R empty ? 1 : 0) S children hold it, a
+ * leaf holding its row's documents and a group child the documents it matches;
+ * the comparison is made in 32 bits, so any m > |S| matches nothing.  A group
+ * without children, or with MUST_NOT children only, matches nothing.  The score
+ * is the flat rule per group, a group child scoring what the rule gave it: must
+ * = (float) of the double sum of the MUST children's scores, should = (float) of
+ * the double sum of the scores of the SHOULD children that hold the document,
+ * both in child order; must + should in one float addition, or the one that
+ * exists, or 0.0f.  No rewrite is applied (no inlining of nested disjunctions,
+ * no SHOULD -> MUST when m = |S|, no de-duplication).  Order: score bits
+ * descending, then doc ascending.  A root with m = 0 and leaf children only
+ * gives exactly the flat call's result for the same clause list.
+ * Input and output follow tfidf_search_compound_batch, with nodes[n_nodes] and
+ * q_node_offsets[n_q + 1] in place of the clauses (n_nodes =
+ * q_node_offsets[n_q]; c_offsets has n_nodes + 1 entries, a group's payload is
+ * empty).  A failing leaf route fails the call with the route's code and
+ * tfidf_last_error starts with "query Q node N:".  TFIDF_E_INVALID_ARG with
+ * nothing written, the error naming the query and the node: more than 65 536
+ * queries, 64 nodes in a query or 2^20 nodes in a call; offsets that do not
+ * start at 0 or decrease; an unknown occur or a kind above 5; a node 0 that is
+ * no group or has a parent; a later node whose parent is not an earlier group
+ * that is node i - 1 or one of its ancestors; a group with a payload; a group
+ * deeper than 3 or a leaf deeper than 4; NULL arguments.  TFIDF_E_STATE before
+ * the first commit.  tfidf_last_compound_stats and tfidf_last_compound_ms report
+ * these calls as they report the flat ones.  Out of scope: boosts, top-k. */
+#define TFIDF_CLAUSE_GROUP 5              /* nested calls only */
+#define TFIDF_QNODE_ROOT 0xFFFFFFFFu
+typedef struct tfidf_qnode {
+  uint8_t occur, kind, max_edits, max_expansions;
+  uint32_t prefix_len, slop;
+  uint32_t parent;             /* index within the query; TFIDF_QNODE_ROOT for node 0 */
+  uint32_t min_should_match;   /* groups only */
+} tfidf_qnode;                 /* 20 bytes */
+int tfidf_search_nested_batch(tfidf_index *ix, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                              const tfidf_qnode *nodes, const uint64_t *q_node_offsets, uint32_t n_q,
+                              uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out,
+                              float *ms_device);
+int tfidf_reader_search_nested_batch(tfidf_reader *rd, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                     const tfidf_qnode *nodes, const uint64_t *q_node_offsets, uint32_t n_q,
+                                     uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                                     uint64_t *n_out, float *ms_device);
+/* The batch of one query of n_nodes nodes. */
+int tfidf_search_nested(tfidf_index *ix, const uint8_t *c_utf8, const uint64_t *c_offsets, const tfidf_qnode *nodes,
+                        uint32_t n_nodes, uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *n_out,
+                        float *ms_device);
+int tfidf_reader_search_nested(tfidf_reader *rd, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                               const tfidf_qnode *nodes, uint32_t n_nodes, uint32_t *doc_ids, float *scores,
+                               uint64_t cap, uint64_t *n_out, float *ms_device);
 /* ---- more-like-this: documents similar to a seed document (Lucene 9.8
  * MoreLikeThis restated on the index's own forward rows; the reference stores
  * no term vectors and cannot offer it; DESIGN.md section 2, "More like this") ----
@@ -1434,6 +1496,14 @@ int tfidf_node_search_compound_batch(tfidf_node *n, const uint8_t *c_utf8, const
                                      const tfidf_clause *clauses, const uint64_t *q_clause_offsets, uint32_t n_q,
                                      uint64_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
                                      uint64_t *n_out, float *ms_device);
+/* tfidf_search_nested_batch over the node, built exactly as
+ * tfidf_node_search_compound_batch: every shard runs the batch, the host merges
+ * by (score bits descending, global id ascending), a shard's failure fails the
+ * call with that shard's code. */
+int tfidf_node_search_nested_batch(tfidf_node *n, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                   const tfidf_qnode *nodes, const uint64_t *q_node_offsets, uint32_t n_q,
+                                   uint64_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                                   uint64_t *n_out, float *ms_device);
 typedef struct tfidf_node_stats {
   uint64_t n_shards;
   uint64_t num_docs;      /* all shards */

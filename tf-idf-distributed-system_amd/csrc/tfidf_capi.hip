@@ -28,6 +28,7 @@
 #include "commit_plan.h"
 #include "compact_plan.h"
 #include "compound_plan.h"
+#include "compound_tree_plan.h"
 #include "fuzzy_plan.h"
 #include "fuzzy_search_plan.h"
 #include "wildcard_plan.h"
@@ -5554,14 +5555,20 @@ static int cq_run_slice(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_
   return TFIDF_OK;
 }
 
-static int compound_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *c_utf8, const uint64_t *c_offsets,
-                       const tfidf_clause *clauses, const uint64_t *q_coff, uint32_t n_q, uint32_t *doc_ids,
-                       float *scores, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out, float *ms_device) {
+// The rows of the call's clauses: the clauses grouped by kind, each group
+// through its route in slices, a failed slice run again clause by clause to name
+// the culprit as "query Q <unit> N:".  A nested call passes its nodes as
+// clauses; a group node (TFIDF_CLAUSE_GROUP) has no route and an empty row.
+// groups owns what rows points into.
+static int cq_run_routes(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                         const tfidf_clause *clauses, const uint64_t *q_coff, uint32_t n_q, const char *unit,
+                         std::vector<std::unique_ptr<CqGroup>> &groups, std::vector<CqRow> *rows_out,
+                         float *ms_routes_out) {
   const uint64_t n_c = n_q ? q_coff[n_q] : 0;
   // the groups: one per kind, the fuzzy clauses one per (max_edits, prefix_len, max_expansions)
-  std::vector<std::unique_ptr<CqGroup>> groups;
   for (uint64_t c = 0; c < n_c; c++) {
     const tfidf_clause &cl = clauses[c];
+    if (cl.kind == TFIDF_CLAUSE_GROUP) continue;
     const bool fz = cl.kind == TFIDF_CLAUSE_FUZZY;
     CqGroup *g = nullptr;
     for (auto &x : groups)
@@ -5600,13 +5607,14 @@ static int compound_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t
         if (cq_run_slice(ix, S, V, c_utf8, c_offsets, clauses, one, 0, 1, &ms1) == rc) {
           const uint32_t q = query_of(g.clause[i]);
           const std::string w1 = g_err;
-          return fail(rc, "query %u clause %u: %s", q, (uint32_t)(g.clause[i] - q_coff[q]), w1.c_str());
+          return fail(rc, "query %u %s %u: %s", q, unit, (uint32_t)(g.clause[i] - q_coff[q]), w1.c_str());
         }
       }
-      return fail(rc, "a clause of kind %u: %s", g.kind, why.c_str());
+      return fail(rc, "a %s of kind %u: %s", unit, g.kind, why.c_str());
     }
   }
-  std::vector<CqRow> rows(n_c);
+  std::vector<CqRow> &rows = *rows_out;
+  rows.assign(n_c, CqRow());
   for (auto &gp : groups)
     for (size_t i = 0; i < gp->clause.size(); i++) {
       CqRow &r = rows[gp->clause[i]];
@@ -5614,6 +5622,23 @@ static int compound_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t
       r.docs = gp->docs.data() + gp->off[i];
       r.scores = gp->scores.empty() ? nullptr : gp->scores.data() + gp->off[i];
     }
+  *ms_routes_out = ms_routes;
+  return TFIDF_OK;
+}
+
+// nodes: NULL for the flat call; else the nested call's trees, clauses holding every node's occur, kind and
+// parameters (q_coff then counts nodes)
+static int compound_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                       const tfidf_clause *clauses, const tfidf_qnode *nodes, const uint64_t *q_coff, uint32_t n_q,
+                       uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out,
+                       float *ms_device) {
+  const uint64_t n_c = n_q ? q_coff[n_q] : 0;
+  std::vector<std::unique_ptr<CqGroup>> groups;
+  std::vector<CqRow> rows;
+  float ms_routes = 0.0f;
+  if (int rc = cq_run_routes(ix, S, V, c_utf8, c_offsets, clauses, q_coff, n_q, nodes ? "node" : "clause", groups,
+                             &rows, &ms_routes))
+    return rc;
 
   for (uint32_t i = 0; i <= n_q; i++) hit_offsets[i] = 0;
   *n_out = 0;
@@ -5654,7 +5679,7 @@ static int compound_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t
   DeviceGuard dg(ix->cfg.device);
   std::vector<uint2> h_rows;
   std::vector<uint64_t> h_coff, qoff_h;
-  std::vector<uint32_t> h_occ, h_qc;
+  std::vector<uint32_t> h_occ, h_qc, h_tree;         // h_tree, nested only: the nodes' parents, then their min_should_match
   uint64_t total = 0;
   bool fits = true;
   for (size_t k = 0; k + 1 < cuts.size(); k++) {
@@ -5662,9 +5687,13 @@ static int compound_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t
     const uint64_t c_lo = q_coff[a], c_hi = q_coff[z];
     const uint32_t nc = (uint32_t)(c_hi - c_lo);
     uint64_t n_e = 0, bound = 0;
+    uint32_t levels = 1;                               // nested: the most groups a query of the chunk has open at once
     for (uint32_t q = a; q < z; q++) {
       n_e += q_entries[q];
-      bound += cq_hit_bound(clauses + q_coff[q], row_n.data() + q_coff[q], q_coff[q + 1] - q_coff[q], S.n_docs);
+      const uint64_t c0 = q_coff[q], n = q_coff[q + 1] - c0;
+      bound += nodes ? cqn_hit_bound(nodes + c0, row_n.data() + c0, (uint32_t)n, S.n_docs)
+                     : cq_hit_bound(clauses + c0, row_n.data() + c0, n, S.n_docs);
+      if (nodes) levels = std::max(levels, cqn_levels(nodes + c0, (uint32_t)n));
     }
     st_chunks++;
     st_entries += n_e;
@@ -5677,19 +5706,25 @@ static int compound_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t
     h_coff.assign((size_t)nc + 1, 0);
     h_occ.resize(nc);
     h_qc.resize((size_t)nq + 1);
+    if (nodes) h_tree.resize((size_t)nc * 2);
     uint64_t at = 0;
     for (uint32_t c = 0; c < nc; c++) {
       const CqRow &r = rows[c_lo + c];
       for (uint64_t i = 0; i < r.n; i++)
         h_rows[at++] = make_uint2(r.docs[i], r.scores ? cq_float_bits(r.scores[i]) : 0x3F800000u);
       h_coff[c + 1] = at;
-      h_occ[c] = clauses[c_lo + c].occur;
+      h_occ[c] = clauses[c_lo + c].occur | (clauses[c_lo + c].kind == TFIDF_CLAUSE_GROUP ? 0x100u : 0u);
+      if (nodes) {
+        h_tree[c] = nodes[c_lo + c].parent;
+        h_tree[(size_t)nc + c] = nodes[c_lo + c].min_should_match;
+      }
     }
     for (uint32_t i = 0; i <= nq; i++) h_qc[i] = (uint32_t)(q_coff[a + i] - c_lo);
     const uint64_t n_bins = (uint64_t)nc * R;
     const size_t runs = (size_t)nq * R2;
     const size_t in_coff = 0, in_occ = ((size_t)nc + 1) * 8, in_qc = in_occ + (((size_t)nc * 4 + 7) & ~(size_t)7),
-                 in_bytes = in_qc + ((size_t)nq + 1) * 4;
+                 in_tree = (in_qc + ((size_t)nq + 1) * 4 + 7) & ~(size_t)7,
+                 in_bytes = in_tree + (nodes ? (size_t)nc * 8 : 0);
     HIP_TRY(X.cq_in.reserve(in_bytes));
     HIP_TRY(X.cq_rows.reserve(n_e * 8));
     HIP_TRY(X.cq_binned.reserve(n_e * 8));
@@ -5705,8 +5740,14 @@ static int compound_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t
     HIP_TRY(hipMemcpyAsync(d_in + in_coff, h_coff.data(), ((size_t)nc + 1) * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_in + in_occ, h_occ.data(), (size_t)nc * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_in + in_qc, h_qc.data(), ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, s));
+    if (nodes) HIP_TRY(hipMemcpyAsync(d_in + in_tree, h_tree.data(), (size_t)nc * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(X.cq_rows.p, h_rows.data(), n_e * 8, hipMemcpyHostToDevice, s));
     CqPass p{};
+    if (nodes) {
+      p.c_parent = reinterpret_cast<const uint32_t *>(d_in + in_tree);
+      p.c_msm = p.c_parent + nc;
+      p.levels = levels;
+    }
     p.rows = X.cq_rows.as<uint2>();
     p.c_off = reinterpret_cast<const uint64_t *>(d_in + in_coff);
     p.c_occur = reinterpret_cast<const uint32_t *>(d_in + in_occ);
@@ -5784,8 +5825,8 @@ extern "C" int tfidf_search_compound_batch(tfidf_index *ix, const uint8_t *c_utf
   std::shared_ptr<StatsView> view;
   const std::shared_ptr<Snapshot> snap = current(ix, &view);
   if (!snap) return fail(TFIDF_E_STATE, "compound search before commit");
-  return compound_on(ix, *snap, *view, c_utf8, c_offsets, clauses, q_clause_offsets, n_q, doc_ids, scores, cap,
-                     hit_offsets, n_out, ms_device);
+  return compound_on(ix, *snap, *view, c_utf8, c_offsets, clauses, nullptr, q_clause_offsets, n_q, doc_ids, scores,
+                     cap, hit_offsets, n_out, ms_device);
 }
 
 extern "C" int tfidf_reader_search_compound_batch(tfidf_reader *rd, const uint8_t *c_utf8, const uint64_t *c_offsets,
@@ -5795,8 +5836,8 @@ extern "C" int tfidf_reader_search_compound_batch(tfidf_reader *rd, const uint8_
   if (int rc = compound_check(rd, c_utf8, c_offsets, clauses, q_clause_offsets, n_q, doc_ids, scores, cap, hit_offsets,
                               n_out))
     return rc;
-  return compound_on(rd->ix, *rd->S, *rd->V, c_utf8, c_offsets, clauses, q_clause_offsets, n_q, doc_ids, scores, cap,
-                     hit_offsets, n_out, ms_device);
+  return compound_on(rd->ix, *rd->S, *rd->V, c_utf8, c_offsets, clauses, nullptr, q_clause_offsets, n_q, doc_ids,
+                     scores, cap, hit_offsets, n_out, ms_device);
 }
 
 // the single forms: the batch of one query
@@ -5817,6 +5858,91 @@ extern "C" int tfidf_reader_search_compound(tfidf_reader *rd, const uint8_t *c_u
   uint64_t ho[2];
   return tfidf_reader_search_compound_batch(rd, c_utf8, c_offsets, clauses, qo, 1, doc_ids, scores, cap, ho, n_out,
                                             ms_device);
+}
+
+// nested compound queries ("Nested compound queries"; rules in compound_tree_plan.h): the
+// flat call's path with the nodes as its clauses, a group node's row empty, and k_cqn_combine as the combine
+static int nested_check(const void *h, const uint8_t *c_utf8, const uint64_t *c_offsets, const tfidf_qnode *nodes,
+                        const uint64_t *q_noff, uint32_t n_q, const uint32_t *doc_ids, const float *scores,
+                        uint64_t cap, const uint64_t *hit_offsets, const uint64_t *n_out) {
+  if (!h || !hit_offsets || !n_out || (n_q && !q_noff) || (cap && (!doc_ids || !scores)))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (n_q && n_q <= kCqMaxQueries && q_noff[n_q] && (!nodes || !c_offsets))
+    return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  uint64_t q = 0, i = 0;
+  const char *why = nullptr;
+  switch (cqn_check_args(c_offsets, nodes, q_noff, n_q, &q, &i)) {
+    case kCqnOk:
+      if (n_q && q_noff[n_q] && !c_utf8 && c_offsets[q_noff[n_q]]) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+      return TFIDF_OK;
+    case kCqnTooManyQueries: return fail(TFIDF_E_INVALID_ARG, "more than %u queries in one call", kCqMaxQueries);
+    case kCqnBadQueryOffsets: return fail(TFIDF_E_INVALID_ARG, "q_node_offsets do not start at 0 or decrease at query %llu", (unsigned long long)q);
+    case kCqnTooManyInQuery: return fail(TFIDF_E_INVALID_ARG, "query %llu has more than %u nodes", (unsigned long long)q, kCqnMaxNodes);
+    case kCqnTooManyNodes: return fail(TFIDF_E_INVALID_ARG, "more than 2^20 nodes in one call");
+    case kCqnBadPayloadOffsets: why = "c_offsets do not start at 0 or decrease"; break;
+    case kCqnBadOccur: why = "unknown occur"; break;
+    case kCqnBadKind: why = "unknown kind"; break;
+    case kCqnBadRoot: why = "node 0 is not a group, or has a parent"; break;
+    case kCqnBadParent: why = "the parent is not an earlier group that is the node before or one of its ancestors"; break;
+    case kCqnGroupPayload: why = "a group with a payload"; break;
+    default: why = "a group deeper than 3 or a leaf deeper than 4"; break;
+  }
+  return fail(TFIDF_E_INVALID_ARG, "query %llu node %llu: %s", (unsigned long long)q, (unsigned long long)i, why);
+}
+
+static int nested_on(tfidf_index *ix, Snapshot &S, StatsView &V, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                     const tfidf_qnode *nodes, const uint64_t *q_noff, uint32_t n_q, uint32_t *doc_ids, float *scores,
+                     uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out, float *ms_device) {
+  const uint64_t n_n = n_q ? q_noff[n_q] : 0;
+  std::vector<tfidf_clause> cl(n_n ? n_n : 1);
+  for (uint64_t i = 0; i < n_n; i++)
+    cl[i] = tfidf_clause{nodes[i].occur, nodes[i].kind, nodes[i].max_edits, nodes[i].max_expansions,
+                         nodes[i].prefix_len, nodes[i].slop};
+  return compound_on(ix, S, V, c_utf8, c_offsets, cl.data(), nodes, q_noff, n_q, doc_ids, scores, cap, hit_offsets,
+                     n_out, ms_device);
+}
+
+extern "C" int tfidf_search_nested_batch(tfidf_index *ix, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                         const tfidf_qnode *nodes, const uint64_t *q_node_offsets, uint32_t n_q,
+                                         uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                                         uint64_t *n_out, float *ms_device) {
+  if (int rc = nested_check(ix, c_utf8, c_offsets, nodes, q_node_offsets, n_q, doc_ids, scores, cap, hit_offsets, n_out))
+    return rc;
+  std::shared_ptr<StatsView> view;
+  const std::shared_ptr<Snapshot> snap = current(ix, &view);
+  if (!snap) return fail(TFIDF_E_STATE, "nested search before commit");
+  return nested_on(ix, *snap, *view, c_utf8, c_offsets, nodes, q_node_offsets, n_q, doc_ids, scores, cap, hit_offsets,
+                   n_out, ms_device);
+}
+
+extern "C" int tfidf_reader_search_nested_batch(tfidf_reader *rd, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                                const tfidf_qnode *nodes, const uint64_t *q_node_offsets, uint32_t n_q,
+                                                uint32_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                                                uint64_t *n_out, float *ms_device) {
+  if (int rc = nested_check(rd, c_utf8, c_offsets, nodes, q_node_offsets, n_q, doc_ids, scores, cap, hit_offsets, n_out))
+    return rc;
+  return nested_on(rd->ix, *rd->S, *rd->V, c_utf8, c_offsets, nodes, q_node_offsets, n_q, doc_ids, scores, cap,
+                   hit_offsets, n_out, ms_device);
+}
+
+// the single forms: the batch of one query
+extern "C" int tfidf_search_nested(tfidf_index *ix, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                   const tfidf_qnode *nodes, uint32_t n_nodes, uint32_t *doc_ids, float *scores,
+                                   uint64_t cap, uint64_t *n_out, float *ms_device) {
+  if (!n_out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t qo[2] = {0, n_nodes};
+  uint64_t ho[2];
+  return tfidf_search_nested_batch(ix, c_utf8, c_offsets, nodes, qo, 1, doc_ids, scores, cap, ho, n_out, ms_device);
+}
+
+extern "C" int tfidf_reader_search_nested(tfidf_reader *rd, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                          const tfidf_qnode *nodes, uint32_t n_nodes, uint32_t *doc_ids, float *scores,
+                                          uint64_t cap, uint64_t *n_out, float *ms_device) {
+  if (!n_out) return fail(TFIDF_E_INVALID_ARG, "NULL argument");
+  const uint64_t qo[2] = {0, n_nodes};
+  uint64_t ho[2];
+  return tfidf_reader_search_nested_batch(rd, c_utf8, c_offsets, nodes, qo, 1, doc_ids, scores, cap, ho, n_out,
+                                          ms_device);
 }
 
 extern "C" int tfidf_last_compound_stats(const tfidf_index *ix, uint64_t *row_entries, uint64_t *chunks,

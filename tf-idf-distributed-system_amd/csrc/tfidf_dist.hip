@@ -39,6 +39,7 @@
 #include "../../include/tfidf.h"
 #include "analysis.h"
 #include "compound_plan.h"
+#include "compound_tree_plan.h"
 #include "mlt_plan.h"
 #include "tfidf_common.h"
 #include "tfidf_internal.h"
@@ -2549,20 +2550,13 @@ extern "C" int tfidf_node_search_phrase_slop_batch(tfidf_node *n, const uint8_t 
 // vocabulary and the statistics in force); the host merges each query's ordered
 // lists by (score bits descending, global id ascending).
 
-extern "C" int tfidf_node_search_compound_batch(tfidf_node *n, const uint8_t *c_utf8, const uint64_t *c_offsets,
-                                                const tfidf_clause *clauses, const uint64_t *q_clause_offsets,
-                                                uint32_t n_q, uint64_t *doc_ids, float *scores, uint64_t cap,
-                                                uint64_t *hit_offsets, uint64_t *n_out, float *ms_device) {
-  if (!n || !hit_offsets || !n_out || (n_q && !q_clause_offsets) || (cap && (!doc_ids || !scores)))
-    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
-  if (n_q && n_q <= kCqMaxQueries && q_clause_offsets[n_q] && (!clauses || !c_offsets))
-    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
-  uint64_t bad = 0;
-  if (const int why = cq_check_args(c_offsets, clauses, q_clause_offsets, n_q, &bad))
-    return errf(TFIDF_E_INVALID_ARG, "compound arguments: rule %d broken at %llu (compound_plan.h)", why,
-                (unsigned long long)bad);
+// the validated batch on every shard and the merge; batch(ix, docs, scores, cap, hit_offsets, n_out, ms) is the
+// shard's call, what names it in the error before the first commit
+template <class Batch>
+static int node_compound_run(tfidf_node *n, const char *what, Batch batch, uint32_t n_q, uint64_t *doc_ids,
+                             float *scores, uint64_t cap, uint64_t *hit_offsets, uint64_t *n_out, float *ms_device) {
   std::lock_guard<std::mutex> lk(n->mu);
-  if (!n->committed) return errf(TFIDF_E_STATE, "compound search before tfidf_node_commit");
+  if (!n->committed) return errf(TFIDF_E_STATE, "%s search before tfidf_node_commit", what);
   struct ShardHits {
     std::vector<uint32_t> docs;
     std::vector<float> scores;
@@ -2583,8 +2577,7 @@ extern "C" int tfidf_node_search_compound_batch(tfidf_node *n, const uint8_t *c_
         for (int attempt = 0; attempt < 2; attempt++) {
           b.docs.resize(guess);
           b.scores.resize(guess);
-          rc = tfidf_search_compound_batch(ix, c_utf8, c_offsets, clauses, q_clause_offsets, n_q, b.docs.data(),
-                                           b.scores.data(), guess, b.off.data(), &total, &b.ms);
+          rc = batch(ix, b.docs.data(), b.scores.data(), guess, b.off.data(), &total, &b.ms);
           if (rc != TFIDF_E_BUFFER) break;
           guess = total;
         }
@@ -2627,6 +2620,49 @@ extern "C" int tfidf_node_search_compound_batch(tfidf_node *n, const uint8_t *c_
     }
   }
   return TFIDF_OK;
+}
+
+extern "C" int tfidf_node_search_compound_batch(tfidf_node *n, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                                const tfidf_clause *clauses, const uint64_t *q_clause_offsets,
+                                                uint32_t n_q, uint64_t *doc_ids, float *scores, uint64_t cap,
+                                                uint64_t *hit_offsets, uint64_t *n_out, float *ms_device) {
+  if (!n || !hit_offsets || !n_out || (n_q && !q_clause_offsets) || (cap && (!doc_ids || !scores)))
+    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (n_q && n_q <= kCqMaxQueries && q_clause_offsets[n_q] && (!clauses || !c_offsets))
+    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  uint64_t bad = 0;
+  if (const int why = cq_check_args(c_offsets, clauses, q_clause_offsets, n_q, &bad))
+    return errf(TFIDF_E_INVALID_ARG, "compound arguments: rule %d broken at %llu (compound_plan.h)", why,
+                (unsigned long long)bad);
+  return node_compound_run(
+      n, "compound",
+      [&](tfidf_index *ix, uint32_t *d, float *sc, uint64_t room, uint64_t *off, uint64_t *total, float *ms) {
+        return tfidf_search_compound_batch(ix, c_utf8, c_offsets, clauses, q_clause_offsets, n_q, d, sc, room, off,
+                                           total, ms);
+      },
+      n_q, doc_ids, scores, cap, hit_offsets, n_out, ms_device);
+}
+
+// nested compound queries over the node: the same fan-out and merge over tfidf_search_nested_batch
+extern "C" int tfidf_node_search_nested_batch(tfidf_node *n, const uint8_t *c_utf8, const uint64_t *c_offsets,
+                                              const tfidf_qnode *nodes, const uint64_t *q_node_offsets, uint32_t n_q,
+                                              uint64_t *doc_ids, float *scores, uint64_t cap, uint64_t *hit_offsets,
+                                              uint64_t *n_out, float *ms_device) {
+  if (!n || !hit_offsets || !n_out || (n_q && !q_node_offsets) || (cap && (!doc_ids || !scores)))
+    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  if (n_q && n_q <= kCqMaxQueries && q_node_offsets[n_q] && (!nodes || !c_offsets))
+    return errf(TFIDF_E_INVALID_ARG, "NULL argument");
+  uint64_t bad_q = 0, bad_n = 0;
+  if (const int why = cqn_check_args(c_offsets, nodes, q_node_offsets, n_q, &bad_q, &bad_n))
+    return errf(TFIDF_E_INVALID_ARG, "nested arguments: rule %d broken at query %llu node %llu (compound_tree_plan.h)",
+                why, (unsigned long long)bad_q, (unsigned long long)bad_n);
+  return node_compound_run(
+      n, "nested",
+      [&](tfidf_index *ix, uint32_t *d, float *sc, uint64_t room, uint64_t *off, uint64_t *total, float *ms) {
+        return tfidf_search_nested_batch(ix, c_utf8, c_offsets, nodes, q_node_offsets, n_q, d, sc, room, off, total,
+                                         ms);
+      },
+      n_q, doc_ids, scores, cap, hit_offsets, n_out, ms_device);
 }
 
 // ---------------------------------------------------------------------------

@@ -468,17 +468,25 @@ hipError_t launch_hits_order_batch(uint64_t *hits, const uint32_t *hits_n, uint3
 // per (query, block) into sorted runs in the batched all-hits layout (run
 // q * R2 + b of hits / hits_n; n_q * n_blocks < 2^31).  bin_cnt / bin_off:
 // n_c * n_blocks + 1 u64 each; binned: n_e entries.
+// A nested chunk (tfidf_search_nested*; rules in compound_tree_plan.h) is the
+// same with one "clause" per node of its queries' trees, a group's row empty,
+// and the node table beside the occurs: c_parent is set, and levels is the most
+// groups any query of the chunk has open at once.  launch_compound_pass then
+// combines with k_cqn_combine.
 struct CqPass {
   const uint2 *rows;
   const uint64_t *c_off;
-  const uint32_t *c_occur;    // per clause of the chunk: TFIDF_OCCUR_*
+  const uint32_t *c_occur;    // per clause of the chunk: TFIDF_OCCUR_*; nested: | 0x100 for a group
   const uint32_t *q_coff;     // [n_q + 1] first clause of each query
+  const uint32_t *c_parent;   // nested only: per node its parent within the query
+  const uint32_t *c_msm;      // nested only: per node min_should_match
   uint64_t *bin_cnt, *bin_off;
   uint2 *binned;
   uint64_t *hits;
   uint32_t *hits_n;
   uint64_t n_e;
   uint32_t n_c, n_q, n_blocks, R2, n_docs;
+  uint32_t levels;            // nested only: 1 .. kCqnMaxDepth
 };
 hipError_t launch_compound_pass(const CqPass &p, int grid, hipStream_t s);
 

@@ -165,6 +165,25 @@ def _compound_batch_sig(doc):
 
 _COMPOUND_SINGLE_SIG = (C.c_int, [VP, C.c_char_p, U64P, CLAUSEP, C.c_uint32, U32P, F32P, C.c_uint64, U64P, F32P])
 
+CLAUSE_GROUP = 5                 # TFIDF_CLAUSE_GROUP: nested calls only
+QNODE_ROOT = 0xFFFFFFFF          # TFIDF_QNODE_ROOT
+
+
+class QNode(C.Structure):
+    """tfidf_qnode (20 bytes)."""
+    _fields_ = Clause._fields_ + [("parent", C.c_uint32), ("min_should_match", C.c_uint32)]
+
+
+QNODEP = C.POINTER(QNode)
+
+
+def _nested_batch_sig(doc):
+    """tfidf_[reader_|node_]search_nested_batch; doc ids are u32 per shard, u64 over a node."""
+    return (C.c_int, [VP, C.c_char_p, U64P, QNODEP, U64P, C.c_uint32, doc, F32P, C.c_uint64, U64P, U64P, F32P])
+
+
+_NESTED_SINGLE_SIG = (C.c_int, [VP, C.c_char_p, U64P, QNODEP, C.c_uint32, U32P, F32P, C.c_uint64, U64P, F32P])
+
 SIGNATURES = {
     "tfidf_version": (C.c_char_p, []),
     "tfidf_last_error": (C.c_char_p, []),
@@ -260,6 +279,11 @@ SIGNATURES = {
     "tfidf_node_search_compound_batch": _compound_batch_sig(U64P),
     "tfidf_search_compound": _COMPOUND_SINGLE_SIG,
     "tfidf_reader_search_compound": _COMPOUND_SINGLE_SIG,
+    "tfidf_search_nested_batch": _nested_batch_sig(U32P),
+    "tfidf_reader_search_nested_batch": _nested_batch_sig(U32P),
+    "tfidf_node_search_nested_batch": _nested_batch_sig(U64P),
+    "tfidf_search_nested": _NESTED_SINGLE_SIG,
+    "tfidf_reader_search_nested": _NESTED_SINGLE_SIG,
     "tfidf_last_compound_stats": (C.c_int, [VP, U64P, U64P, U64P]),
     "tfidf_last_compound_ms": (C.c_int, [VP, F32P]),
     "tfidf_mlt_params_init": (C.c_int, [MLTP]),

@@ -560,6 +560,21 @@ class Node:
         from . import engine as E
         return E._compound_lists(self.search_compound_batch_arrays(queries))
 
+    def search_nested_batch_arrays(self, queries, cap=None):
+        """(global docs uint64[], scores float32[], hit offsets uint64[n_q + 1],
+        ms_device) of tfidf_node_search_nested_batch."""
+        from . import engine as E
+        return E._compound_arrays(L.load().tfidf_node_search_nested_batch, self._h, queries, cap, dtype=np.uint64,
+                                  arrays=E._qnode_arrays)
+
+    def search_nested_batch(self, queries):
+        """ShardIndex.search_nested_batch over the node, built as
+        search_compound_batch: every shard evaluates the trees on its own
+        documents and the host merges by (score descending, global id
+        ascending)."""
+        from . import engine as E
+        return E._compound_lists(self.search_nested_batch_arrays(queries))
+
     def more_like_this_batch(self, docs, k=10, exclude_seed=True, **params):
         """ShardIndex.more_like_this_batch over the node: ``docs`` are global
         ids; the owning shard picks a seed's interesting terms, every shard

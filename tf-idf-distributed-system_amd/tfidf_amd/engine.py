@@ -429,6 +429,23 @@ def filter_(clause):
     return (L.OCCUR_FILTER,) + tuple(clause)
 
 
+def group(children, min_should_match=0):
+    """A clause group of the nested calls: ``children`` are occurred clauses or
+    occurred groups, must(group([should(text(b"a")), should(text(b"b"))], 2))."""
+    return (L.CLAUSE_GROUP, tuple(children), int(min_should_match))
+
+
+def _fill_clause(rec, occur, kind, params):
+    if not (0 <= occur <= 255 and 0 <= kind <= 255):
+        raise ValueError("occur and kind are bytes")
+    rec.occur, rec.kind = occur, kind
+    if kind == L.CLAUSE_PHRASE:
+        rec.slop = params[0] if params else 0
+    elif kind == L.CLAUSE_FUZZY:
+        me, pl, mx = (tuple(params) + (2, 0, 50)[len(params):])[:3]
+        rec.max_edits, rec.prefix_len, rec.max_expansions = min(me, 255), pl, min(max(mx, 0), 255)
+
+
 def _clause_arrays(queries):
     """[[clause]] -> (payload blob, uint64 payload offsets, Clause array, uint64 clause offsets per query)."""
     flat = [c for q in queries for c in q]
@@ -438,24 +455,55 @@ def _clause_arrays(queries):
     blob, c_offs = _key_arrays([c[2] for c in flat])
     arr = (L.Clause * max(len(flat), 1))()
     for i, c in enumerate(flat):
-        occur, kind, params = int(c[0]), int(c[1]), c[3:]
-        if not (0 <= occur <= 255 and 0 <= kind <= 255):
-            raise ValueError("occur and kind are bytes")
-        arr[i].occur, arr[i].kind = occur, kind
-        if kind == L.CLAUSE_PHRASE:
-            arr[i].slop = params[0] if params else 0
-        elif kind == L.CLAUSE_FUZZY:
-            me, pl, mx = (tuple(params) + (2, 0, 50)[len(params):])[:3]
-            arr[i].max_edits, arr[i].prefix_len, arr[i].max_expansions = min(me, 255), pl, min(max(mx, 0), 255)
+        _fill_clause(arr[i], int(c[0]), int(c[1]), c[3:])
     return blob, c_offs, arr, q_offs
 
 
-def _compound_arrays(fn, handle, queries, cap=None, dtype=np.uint32):
+def _as_root(query):
+    """A nested query: a group(...) tuple, or a plain list of occurred clauses, which is a root with m = 0."""
+    if isinstance(query, tuple) and len(query) == 3 and query[0] == L.CLAUSE_GROUP:
+        return query
+    return group(query)
+
+
+def _qnode_arrays(queries):
+    """[nested query] -> (payload blob, uint64 payload offsets, QNode array, uint64 node offsets per query): every
+    tree in pre-order, the root first."""
+    flat, sizes = [], []                      # (occur, kind, payload, params, parent, m)
+
+    def walk(occur, node, parent, first):
+        kind = int(node[0])
+        at = len(flat) - first
+        if kind == L.CLAUSE_GROUP:
+            flat.append((occur, kind, b"", (), parent, int(node[2])))
+            for child in node[1]:
+                walk(int(child[0]), child[1:], at, first)
+        else:
+            flat.append((occur, kind, node[1], node[2:], parent, 0))
+
+    for q in queries:
+        first = len(flat)
+        walk(L.OCCUR_SHOULD, _as_root(q), L.QNODE_ROOT, first)
+        sizes.append(len(flat) - first)
+    q_offs = np.zeros(len(queries) + 1, np.uint64)
+    if len(queries):
+        q_offs[1:] = np.cumsum(sizes, dtype=np.uint64)
+    blob, c_offs = _key_arrays([n[2] for n in flat])
+    arr = (L.QNode * max(len(flat), 1))()
+    for i, (occur, kind, _, params, parent, m) in enumerate(flat):
+        _fill_clause(arr[i], occur, kind, params)
+        arr[i].parent, arr[i].min_should_match = parent, m
+    return blob, c_offs, arr, q_offs
+
+
+def _compound_arrays(fn, handle, queries, cap=None, dtype=np.uint32, arrays=None):
     """tfidf_[reader_|node_]search_compound_batch: one call with ``cap`` hit
     slots, once more with the size the library reports when that was too small.
-    -> (docs, scores float32[], hit offsets uint64[n_q + 1], ms_device)."""
-    queries = [list(q) for q in queries]
-    blob, c_offs, arr, q_offs = _clause_arrays(queries)
+    -> (docs, scores float32[], hit offsets uint64[n_q + 1], ms_device).
+    ``arrays``: the (blob, payload offsets, records, query offsets) builder;
+    _qnode_arrays for the nested calls."""
+    queries = list(queries) if arrays else [list(q) for q in queries]
+    blob, c_offs, arr, q_offs = (arrays or _clause_arrays)(queries)
     nq = len(queries)
     offs = np.zeros(nq + 1, np.uint64)
     total, ms = C.c_uint64(), C.c_float()
@@ -1051,6 +1099,24 @@ class ShardIndex:
         """search_compound_batch([clauses])[0]."""
         return self.search_compound_batch([clauses])[0]
 
+    def search_nested_batch_arrays(self, queries, cap=None):
+        """(docs uint32[], scores float32[], hit offsets uint64[n_q + 1], ms_device)
+        of tfidf_search_nested_batch.  A query is a group(children,
+        min_should_match) whose children are occurred clauses or occurred groups
+        (at most 64 nodes, groups nested at most 4 deep), or a plain list of
+        occurred clauses, which is a root group with min_should_match 0."""
+        return _compound_arrays(L.load().tfidf_search_nested_batch, self._h, queries, cap, arrays=_qnode_arrays)
+
+    def search_nested_batch(self, queries):
+        """Per query [(doc, score)]: every hit of the clause tree, a group
+        combining its children by the flat rule with its min_should_match, score
+        descending, doc ascending."""
+        return _compound_lists(self.search_nested_batch_arrays(queries))
+
+    def search_nested(self, query):
+        """search_nested_batch([query])[0]."""
+        return self.search_nested_batch([query])[0]
+
     def last_compound_stats(self):
         """(clause-row entries, chunks, (query, block) pairs, combine pass ms) of
         the last compound call on this index or one of its readers
@@ -1616,6 +1682,18 @@ class Reader:
     def search_compound(self, clauses):
         """ShardIndex.search_compound on this reader's snapshot."""
         return self.search_compound_batch([clauses])[0]
+
+    def search_nested_batch_arrays(self, queries, cap=None):
+        """ShardIndex.search_nested_batch_arrays on this reader's snapshot."""
+        return _compound_arrays(L.load().tfidf_reader_search_nested_batch, self._h, queries, cap, arrays=_qnode_arrays)
+
+    def search_nested_batch(self, queries):
+        """ShardIndex.search_nested_batch on this reader's snapshot."""
+        return _compound_lists(self.search_nested_batch_arrays(queries))
+
+    def search_nested(self, query):
+        """ShardIndex.search_nested on this reader's snapshot."""
+        return self.search_nested_batch([query])[0]
 
     def more_like_this(self, doc, k=10, exclude_seed=True, **params):
         """ShardIndex.more_like_this on this reader's snapshot."""

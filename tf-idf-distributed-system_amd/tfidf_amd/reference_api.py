@@ -46,6 +46,61 @@ def _syntax(msg):
     return L.QuerySyntaxError(L.E_QUERY_SYNTAX, msg)
 
 
+def _parse_clause(text, i, tree):
+    """The clause that starts at text[i], after its occur prefix -> (clause, index after it).  ``tree``: the
+    grammar of parse_query_tree, where an unescaped ``)`` ends a token and may follow a closing quote or slash."""
+    from . import engine as E
+    n = len(text)
+
+    def ends(j):
+        return j >= n or text[j].isspace() or (tree and text[j] == ")")
+
+    if text[i] == '"':
+        j = text.find('"', i + 1)
+        if j < 0:
+            raise _syntax("unclosed quote at %d" % i)
+        body, i = text[i + 1:j], j + 1
+        m = re.match(r"~(\d+)", text[i:])
+        slop = 0
+        if m:
+            slop, i = int(m.group(1)), i + m.end()
+        if not ends(i):
+            raise _syntax("text after the closing quote at %d" % i)
+        return E.phrase(body.encode(), min(slop, 0x7FFFFFFF)), i
+    if text[i] == "/":
+        j, body = i + 1, []
+        while j < n and text[j] != "/":
+            if text[j] == "\\" and j + 1 < n and text[j + 1] == "/":
+                body.append("/")
+                j += 2
+                continue
+            if text[j] == "\\" and j + 1 < n:          # any other escape stays the pattern's own
+                body.append(text[j:j + 2])
+                j += 2
+                continue
+            body.append(text[j])
+            j += 1
+        if j >= n:
+            raise _syntax("unclosed slash at %d" % i)
+        i = j + 1
+        if not ends(i):
+            raise _syntax("text after the closing slash at %d" % i)
+        return E.regex("".join(body).encode()), i
+    j = i
+    while not ends(j):
+        j += 2 if tree and text[j] == "\\" and j + 1 < n and not text[j + 1].isspace() else 1
+    tok, i = text[i:j], j
+    m = re.match(r"^(.+)~(\d*)$", tok, re.S)
+    if m:
+        edits = int(m.group(2)) if m.group(2) else 2
+        if edits > 2:
+            raise _syntax("fuzzy edits %d above 2 in '%s'" % (edits, tok))
+        return E.fuzzy(m.group(1).lower().encode(), edits), i
+    if re.search(r"(?<!\\)(?:\\\\)*[*?]", tok):
+        return E.wildcard(tok.encode()), i
+    return E.text(tok.encode()), i
+
+
 def parse_compound_query(text: str):
     """Worker.search_query's grammar: one query string -> the clause list of
     ShardIndex.search_compound, on the host.  Clauses are separated by
@@ -57,7 +112,6 @@ def parse_compound_query(text: str):
     is a one-token text clause, handed on as search_index hands its query.  An
     unclosed quote or slash, a prefix without a clause, text glued to a closing
     quote or slash, or an edit count above 2 raises QuerySyntaxError."""
-    from . import engine as E
     out, i, n = [], 0, len(text)
     while i < n:
         if text[i].isspace():
@@ -69,54 +123,65 @@ def parse_compound_query(text: str):
             i += 1
             if i >= n or text[i].isspace():
                 raise _syntax("a '%s' without a clause at %d" % (text[i - 1], i - 1))
-        if text[i] == '"':
-            j = text.find('"', i + 1)
-            if j < 0:
-                raise _syntax("unclosed quote at %d" % i)
-            body, i = text[i + 1:j], j + 1
-            m = re.match(r"~(\d+)", text[i:])
-            slop = 0
-            if m:
-                slop, i = int(m.group(1)), i + m.end()
-            if i < n and not text[i].isspace():
-                raise _syntax("text after the closing quote at %d" % i)
-            clause = E.phrase(body.encode(), min(slop, 0x7FFFFFFF))
-        elif text[i] == "/":
-            j, body = i + 1, []
-            while j < n and text[j] != "/":
-                if text[j] == "\\" and j + 1 < n and text[j + 1] == "/":
-                    body.append("/")
-                    j += 2
-                    continue
-                if text[j] == "\\" and j + 1 < n:          # any other escape stays the pattern's own
-                    body.append(text[j:j + 2])
-                    j += 2
-                    continue
-                body.append(text[j])
-                j += 1
-            if j >= n:
-                raise _syntax("unclosed slash at %d" % i)
-            i = j + 1
-            if i < n and not text[i].isspace():
-                raise _syntax("text after the closing slash at %d" % i)
-            clause = E.regex("".join(body).encode())
-        else:
-            j = i
-            while j < n and not text[j].isspace():
-                j += 1
-            tok, i = text[i:j], j
-            m = re.match(r"^(.+)~(\d*)$", tok, re.S)
-            if m:
-                edits = int(m.group(2)) if m.group(2) else 2
-                if edits > 2:
-                    raise _syntax("fuzzy edits %d above 2 in '%s'" % (edits, tok))
-                clause = E.fuzzy(m.group(1).lower().encode(), edits)
-            elif re.search(r"(?<!\\)(?:\\\\)*[*?]", tok):
-                clause = E.wildcard(tok.encode())
-            else:
-                clause = E.text(tok.encode())
+        clause, i = _parse_clause(text, i, False)
         out.append((occur,) + clause)
     return out
+
+
+MAX_GROUP_DEPTH = 3          # kCqnMaxDepth - 1: the root is depth 0, a group at depth 4 is invalid
+
+
+def parse_query_tree(text: str):
+    """Worker.search_expr's grammar: one query string -> the group(...) of
+    ShardIndex.search_nested.  It is parse_compound_query's grammar plus
+    groups: outside quotes and slashes, an unescaped ``(`` at the start of a
+    clause, after the optional occur prefix, opens a group; an unescaped ``)``
+    ends the current token and closes the group; ``~N`` right after the ``)``
+    sets the group's min_should_match.  After ``)`` or ``)~N`` only whitespace,
+    another ``)`` or the end may follow.  ``\\(`` and ``\\)`` stay in the token as
+    written; ``()`` is an empty group.  Unbalanced parentheses, groups nested
+    deeper than 3 below the root, a prefix before ``)`` and text glued after
+    ``)`` raise QuerySyntaxError, beside what parse_compound_query raises.  A
+    string without groups parses to group(parse_compound_query(text))."""
+    from . import engine as E
+    n = len(text)
+
+    def children_from(i, depth):
+        """-> (children, index after them, whether a ')' closed them)."""
+        out = []
+        while i < n:
+            if text[i].isspace():
+                i += 1
+                continue
+            if text[i] == ")":
+                if depth == 0:
+                    raise _syntax("a ')' without its '(' at %d" % i)
+                return out, i + 1, True
+            occur = L.OCCUR_SHOULD
+            if text[i] in _OCCUR_PREFIX:
+                occur = _OCCUR_PREFIX[text[i]]
+                i += 1
+                if i >= n or text[i].isspace() or text[i] == ")":
+                    raise _syntax("a '%s' without a clause at %d" % (text[i - 1], i - 1))
+            if text[i] != "(":
+                clause, i = _parse_clause(text, i, True)
+                out.append((occur,) + clause)
+                continue
+            if depth >= MAX_GROUP_DEPTH:
+                raise _syntax("groups nested deeper than %d at %d" % (MAX_GROUP_DEPTH, i))
+            sub, j, closed = children_from(i + 1, depth + 1)
+            if not closed:
+                raise _syntax("unclosed '(' at %d" % i)
+            i, m = j, re.match(r"~(\d+)", text[j:])
+            msm = 0
+            if m:
+                msm, i = min(int(m.group(1)), 0xFFFFFFFF), i + m.end()
+            if i < n and not text[i].isspace() and text[i] != ")":
+                raise _syntax("text after the closing ')' at %d" % i)
+            out.append((occur,) + E.group(sub, msm))
+        return out, i, False
+
+    return E.group(children_from(0, 0)[0])
 
 
 class Worker:
@@ -270,6 +335,16 @@ class Worker:
         clauses = parse_compound_query(text)
         with self.index.reader() as rd:
             hits = rd.search_compound(clauses)
+            return [document_score_info(rd.doc_key(d).decode(), s) for d, s in (hits[:k] if k else hits)]
+
+    # search_query with clause groups: ``(...)`` groups clauses, ``)~N`` asks for
+    # N of the group's SHOULD clauses (parse_query_tree); ``min_should_match``
+    # is the whole string's.  The tree is evaluated on the device as written.
+    def search_expr(self, text: str, k=10, min_should_match=0):
+        from . import engine as E
+        query = E.group(parse_query_tree(text)[1], min_should_match)
+        with self.index.reader() as rd:
+            hits = rd.search_nested(query)
             return [document_score_info(rd.doc_key(d).decode(), s) for d, s in (hits[:k] if k else hits)]
 
     # No reference counterpart ("contents" has no term vectors, so Lucene's
